@@ -23,7 +23,14 @@ The N == 1 line also carries `scale_base_n1`: the 3840x2160 frame on this one GP
 of the N > 1 lines. Rays = primary rays + secondary rays actually traced, counted on the device by an instrumented
 launch outside the timed region (and checked against the oracle in tests/).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the line: the headline, `config`, `steady_state`, `kernel_ms` and the
+roofline object from this run's own events and the committed profiles. Everything else below that takes runs of its own (the
+synchronous frames, the clock probe, the N > 1 single-GPU / delivered / RGBA8 legs, the sub-records, the CPU baseline and the
+live PMC passes) needs `--full`; `--no-extras`, `--no-config5` and `--no-cpu-baseline` then take parts of it away again.
+`--dump-outputs DIR` writes the frame of the last timed step as DIR/frame.npy (float32, height x width x 4; with ranks, each
+rank's own rows as frame_rank<r>.npy + frame_rank<r>_rows.npy), a fixed seeded row sample where it exceeds 60 MiB in all.
+
+The JSON line (with --full) also carries
   roofline     : the contract's HBM roofline of the dominant kernel (crt_trace_kernel): `bound` "hbm", `achieved` = bytes that really
                  leave L2 per launch (`traffic`: FETCH_SIZE + WRITE_SIZE of rocprofv3 --pmc passes of this command -- measured by two short child runs
                  spawned at the very END of this run, when every other number is final and the session is closed (`traffic_live_ok`, `traffic_source`
@@ -61,6 +68,27 @@ sys.path.insert(0, ROOT)
 from clraytracer_amd.measure import (HBM_PEAK_GBS, GATHER_CEILING_UNIFORM, GATHER_DIVERGENT_L2, COUNTER_KEYS, aggregate, algorithmic_bytes, chain_ceiling,
                                       cpu_model, hbm_object, live_pmc_traffic, pmc_traffic, pmc_valu, pmc_vmem, secondary_ceilings, usable_cpus)
 
+DUMP_BUDGET = 60 << 20      # bytes --dump-outputs may write in all (over every rank)
+
+
+def dump_outputs(dirpath, name, frame, rows, budget, seed):
+    """Write `frame` (rows x width x 4 float32) as dirpath/<name>.npy. `rows` names the frame rows it holds (None: the whole frame, in order);
+    beyond `budget` bytes a fixed sample of rows (RandomState(seed)) is kept. Row numbers, when needed, go to <name>_rows.npy as float64."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    frame = np.ascontiguousarray(frame, np.float32)
+    if rows is None:
+        rows = np.arange(len(frame))
+    row_bytes = frame[0].nbytes + 8
+    if len(frame) * row_bytes > budget:
+        keep = np.sort(np.random.RandomState(seed).choice(len(frame), budget // row_bytes, replace=False))
+        frame, rows, sampled = frame[keep], rows[keep], True
+    else:
+        sampled = False
+    np.save(os.path.join(dirpath, name + ".npy"), frame)
+    if sampled or not np.array_equal(rows, np.arange(len(rows))):
+        np.save(os.path.join(dirpath, name + "_rows.npy"), rows.astype(np.float64))
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -85,7 +113,12 @@ def main():
     ap.add_argument("--live-pmc", action="store_true", help="run the live PMC passes even with --no-extras (tests)")
     ap.add_argument("--no-live-pmc", action="store_true", help="take roofline.traffic from the committed profile instead of measuring it now with two short rocprofv3 --pmc child runs")
     ap.add_argument("--cpu-threads", type=int, default=0)
+    ap.add_argument("--full", action="store_true", help="also measure everything outside the headline (synchronous frames, clock probe, N > 1 legs, "
+                                                         "sub-records, CPU baseline, live PMC passes); a plain run times the K steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the frame of the last timed step to DIR/*.npy (float32)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_extras, args.no_cpu_baseline = True, True
     if args.diag_mix3:
         args.frames_in_flight, args.no_extras, args.no_cpu_baseline = 1, True, True
     if args.timed_region_only:
@@ -195,7 +228,7 @@ def main():
         sc = scenes.get(args.scene)
 
     single = None
-    if inproc:
+    if inproc and args.full:
         # the same workload on ONE GPU first (own session: the library drives one session at a time)
         with driver.Session(width, height, device=inproc_devices[0]) as s1:
             s1.load_scene(sc)
@@ -285,12 +318,20 @@ def main():
     # steady state: the first frame's latency is the pipeline's fill time; what follows it is K - 1 frames at the steady cadence.
     # A 20-step run and a 200-step run agree on this figure; the contract's `value` includes the fill.
     steady_ms = (stats.extentMs - stats.firstFrameMs) / max(1, stats.frames - 1) if stats.frames > 1 else extent_ms
+    if args.dump_outputs:
+        # the frame of the last timed step (crt_read_output: the most recently submitted frame), before anything else renders
+        if inproc:
+            dump_outputs(args.dump_outputs, "frame", s.read_output(), None, DUMP_BUDGET, 0)
+        else:
+            rows = np.array([y for y in range(height) if hip.crt_row_owner(y, args.band_rows, n) == rank], np.int64)
+            dump_outputs(args.dump_outputs, "frame" if n == 1 else f"frame_rank{rank}", s.read_output()[rows],
+                         None if len(rows) == height else rows, DUMP_BUDGET // n, rank)
 
     # N > 1: the same workload on ONE GPU -- rank 0 renders the whole frame, untimed by the contract clock, while the others wait at the
     # next barrier -- so the line carries its own strong-scaling reference. Like for like (r6): the same region shape as the timed one
     # (W warm-up frames, K frames + sync, fill included) on clocks the timed region has just warmed; rounds 1-5 timed 3 + 10 frames
     # BEFORE the pre-warm, which under-read the single GPU (11.1-11.5 vs 12.3 Gray/s) and so flattered the speed-up by 7-10 %.
-    if n > 1 and rank == 0 and not inproc:
+    if n > 1 and rank == 0 and not inproc and args.full:
         s.set_row_bands(args.band_rows, 0, 1)
         for _ in range(max(args.warmup, 3)):
             _lib.check(crt_render(p_args, p_iv, p_ip, flags), "crt_render")
@@ -332,7 +373,7 @@ def main():
     # the same K frames the reference's way -- one at a time, Render() + clFinish (Renderer.cpp:305-367) -- reported
     # next to the headline as `synchronous_frames` (not part of the contract's timed region above)
     sync_elapsed = None
-    if flight > 1 and not args.timed_region_only:
+    if flight > 1 and not args.timed_region_only and args.full:
         sflags = flags & ~4
         for _ in range(min(args.warmup, 3)):
             _lib.check(crt_render(p_args, p_iv, p_ip, sflags), "crt_render")
@@ -347,7 +388,7 @@ def main():
     # the shader clock the device holds while such frames are in flight: one probe wave per XCD watches s_memtime against the
     # 100 MHz s_memrealtime for 300 us on its own stream while 24 frames run (cycle-based figures below use this, not 2.4 GHz)
     clock_meas = None
-    if rank == 0 and not args.timed_region_only:
+    if rank == 0 and not args.timed_region_only and args.full:
         for _ in range(24):
             crt_render(p_args, p_iv, p_ip, flags)
         ghz = C.c_double(0.0)
@@ -362,7 +403,7 @@ def main():
     # stops. The headline above leaves the tiles in each rank's HBM; this is the rate at which a whole frame reaches
     # one place (host memory of the node) that a consumer can read.
     deliver_elapsed = deliver8_elapsed = None
-    if n > 1 and not inproc:
+    if n > 1 and not inproc and args.full:
         def delivered(dflags):
             ptr, nbytes = C.c_void_p(), C.c_size_t()
             for _ in range(min(args.warmup, 3)):
@@ -388,6 +429,8 @@ def main():
     inproc_gather = None
     if inproc:
         gb, bpp = s.last_gather()
+        inproc_gather = {"gather_bytes_per_frame": gb, "bytes_per_pixel": bpp, "path": hip.crt_gather_path().decode()}
+    if inproc and args.full:
         for _ in range(min(args.warmup, 3)):
             _lib.check(crt_render(p_args, p_iv, p_ip, flags | 64), "crt_render")
         _lib.check(hip.crt_sync(), "crt_sync")
@@ -398,10 +441,9 @@ def main():
         dt8 = time.perf_counter() - t0
         _lib.check(rc, "crt_render"); _lib.check(rc2, "crt_sync")
         gb8, bpp8 = s.last_gather()
-        inproc_gather = {"gather_bytes_per_frame": gb, "bytes_per_pixel": bpp, "path": hip.crt_gather_path().decode(),
-                         "rgba8_frames": {"gather_bytes_per_frame": gb8, "bytes_per_pixel": bpp8, "ms_per_step": round(dt8 * 1e3 / args.steps, 4),
-                                          "note": "the same K frames with CRT_RENDER_UNORM8 (upstream's RGBA8 render target, Renderer.cpp:63,192): the bytes are gathered, "
-                                                  "the float frame is rebuilt on the first device only when it is read"}}
+        inproc_gather["rgba8_frames"] = {"gather_bytes_per_frame": gb8, "bytes_per_pixel": bpp8, "ms_per_step": round(dt8 * 1e3 / args.steps, 4),
+                                         "note": "the same K frames with CRT_RENDER_UNORM8 (upstream's RGBA8 render target, Renderer.cpp:63,192): the bytes are gathered, "
+                                                 "the float frame is rebuilt on the first device only when it is read"}
 
     tot, elapsed_max, kernel_ms_max = aggregate(dist, cnt, own_rows * width, elapsed, extent_ms, red_device, ctl)
     if sync_elapsed is not None:
@@ -455,10 +497,11 @@ def main():
                 except Exception:
                     continue
         clock_ghz = float(os.environ["CRT_SCLK_GHZ"]) if "CRT_SCLK_GHZ" in os.environ else (clock_meas or (committed_clock[0] if committed_clock else 2.4))
+        no_probe = ("--timed-region-only: probe skipped" if args.timed_region_only else "probe failed") if args.full else "plain run: probe skipped (--full runs it)"
         clock_src = "CRT_SCLK_GHZ" if "CRT_SCLK_GHZ" in os.environ else (
             "crt_debug_measure_clock: s_memtime / s_memrealtime beside 24 frames in flight" if clock_meas else (
-                f"not measured in this run ({'--timed-region-only: probe skipped' if args.timed_region_only else 'probe failed'}); taken from the un-profiled line {committed_clock[1]}"
-                if committed_clock else f"NOMINAL 2.4 GHz ({'--timed-region-only: probe skipped' if args.timed_region_only else 'probe failed'}, no committed line to take it from): cycle-based figures are approximate"))
+                f"not measured in this run ({no_probe}); taken from the un-profiled line {committed_clock[1]}"
+                if committed_clock else f"NOMINAL 2.4 GHz ({no_probe}, no committed line to take it from): cycle-based figures are approximate"))
         ndev_here = n if inproc else 1                                          # in-process: counters are summed over the devices
         gather_rate = pair_fetches / ndev_here / (dev_s * clock_ghz * 1e9 * num_cus)   # 64-B records per cycle per CU
         warnings = []
@@ -522,7 +565,7 @@ def main():
                          "achieved": None if hbm_achieved is None else round(hbm_achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": None if hbm_frac is None else round(hbm_frac, 4),
                          "traffic": traffic, "traffic_source": traffic_src,
-                         "traffic_committed_profile": traffic_committed, "traffic_live_ok": False, "traffic_live_note": None if want_live else "not attempted (--no-live-pmc / --no-extras / --shadows / N > 1)",
+                         "traffic_committed_profile": traffic_committed, "traffic_live_ok": False, "traffic_live_note": None if want_live else "not attempted (plain run / --no-live-pmc / --no-extras / --shadows / N > 1)",
                          "traffic_live_child_rc": [],
                          "frac_definition": "achieved / peak with achieved = `traffic` (FETCH_SIZE + WRITE_SIZE bytes per launch from rocprofv3 --pmc passes of this command -- measured by "
                                             "two child runs of this very run when traffic_source says `live`, else the committed profile: every byte that leaves L2, Infinity-Cache hits included, so an upper bound on HBM bytes) / device_time_per_launch_ms "
@@ -561,7 +604,8 @@ def main():
             if inproc:
                 out["config"]["peer_access"] = [int(hip.crt_peer_access(d)) for d in range(n)]
                 ig = inproc_gather
-                ig["rgba8_frames"]["value"] = round(rays_per_frame * args.steps / (ig["rgba8_frames"]["ms_per_step"] * 1e-3 * args.steps) / 1e6, 2)
+                if "rgba8_frames" in ig:
+                    ig["rgba8_frames"]["value"] = round(rays_per_frame * args.steps / (ig["rgba8_frames"]["ms_per_step"] * 1e-3 * args.steps) / 1e6, 2)
                 out["inprocess_gather"] = ig
         if sync_elapsed is not None:
             out["synchronous_frames"] = {"value": round(rays_per_frame * args.steps / sync_elapsed / 1e6, 2), "unit": "Mrays/s",

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -38,7 +39,7 @@ def check_common(d, n):
 
 
 def test_in_process_two_device_states():
-    d = run_bench([sys.executable, "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "2"])
+    d = run_bench([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "6", "--warmup", "2"])
     check_common(d, 2)
     assert d["config"]["peer_access"] == [2, 2] and "same-device" in d["config"]["gather_path"]
     assert "crt_init_devices" in d["config"]["tiling"] and d["config"]["control_plane"] in (None, "gloo")
@@ -52,7 +53,7 @@ def test_in_process_two_device_states():
 
 def test_in_process_eight_device_states():
     """The driver's N = 8 command line as ONE process (no launcher): eight device states behind crt_init_devices, eight frame slots each."""
-    d = run_bench([sys.executable, "bench.py", "--gpus", "8", "--steps", "4", "--warmup", "1", "--prewarm-ms", "5"])
+    d = run_bench([sys.executable, "bench.py", "--full", "--gpus", "8", "--steps", "4", "--warmup", "1", "--prewarm-ms", "5"])
     check_common(d, 8)
     assert d["config"]["peer_access"] == [2] * 8 and d["config"]["frames_in_flight"] == 8
     assert d["imbalance_max_over_mean"] is None                             # one process: no per-rank clocks
@@ -61,11 +62,12 @@ def test_in_process_eight_device_states():
 
 
 @pytest.mark.parametrize("ranks", [2, 4])
-def test_ranks_under_torch_distributed_run(ranks):
+def test_ranks_under_torch_distributed_run(ranks, tmp_path):
     """The driver's launcher form. (Eight ranks cannot be rehearsed here: the box allows six processes on its one card, and this
     test process is one of them; 4 ranks exercise the N >= 4 rule -- eight frames in flight -- and the per-rank fields.)"""
     d = run_bench([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
-                   "--master-port", str(29571 + ranks), "bench.py", "--gpus", str(ranks), "--steps", "6", "--warmup", "2", "--prewarm-ms", "5"])
+                   "--master-port", str(29571 + ranks), "bench.py", "--full", "--gpus", str(ranks), "--steps", "6", "--warmup", "2", "--prewarm-ms", "5",
+                   "--dump-outputs", str(tmp_path)])
     check_common(d, ranks)
     assert d["config"]["control_plane"] == "gloo"                           # the rehearsal never uses RCCL (all ranks sit on GPU 0)
     # the timed regions are bracketed in shared memory, not over TCP -- wherever the ranks can share a POSIX shm object (every box so far); the line says which
@@ -78,12 +80,18 @@ def test_ranks_under_torch_distributed_run(ranks):
     assert d["config"]["frames_in_flight"] == (3 if ranks < 4 else 8)
     assert len(d["per_rank_ms_per_step"]) == ranks and d["imbalance_max_over_mean"] >= 1.0
     assert abs(max(d["per_rank_ms_per_step"]) - d["ms_per_step"]) <= 0.25 * d["ms_per_step"] + 0.05   # value is taken over the slowest rank's clock
+    # --dump-outputs: every rank writes rows of its own bands only (a seeded sample: the 3840x2160 frame exceeds the budget), 60 MiB in all
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 60 << 20
+    for r in range(ranks):
+        frame, rows = np.load(tmp_path / f"frame_rank{r}.npy"), np.load(tmp_path / f"frame_rank{r}_rows.npy")
+        assert frame.dtype == np.float32 and frame.shape == (len(rows), 3840, 4) and rows.dtype == np.float64 and len(rows) > 0
+        assert np.all(np.diff(rows) > 0) and all((int(y) // 16) % ranks == r for y in rows) and np.isfinite(frame).all()
 
 
 def test_single_gpu_line_carries_the_contract_and_the_round_3_objects():
     """The N = 1 line the driver records: the contract's keys, the roofline object against the ceiling that binds (with the HBM
     figure beside it), the sub-records for BASELINE's literal and hard configurations, and the CPU baseline incl. config 1."""
-    d = run_bench([sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--prewarm-ms", "10"], {"CRT_BENCH_REHEARSE": "0"})
+    d = run_bench([sys.executable, "bench.py", "--full", "--steps", "6", "--warmup", "2", "--prewarm-ms", "10"], {"CRT_BENCH_REHEARSE": "0"})
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["dtype"] == "f32" and d["vs_baseline"] is None
@@ -140,9 +148,30 @@ def test_line_is_whole_without_the_profiler(tmp_path):
     """The live PMC passes are a measurement aid: with no rocprofv3 on PATH the N = 1 line must still come out whole, its `traffic` from the
     committed profile, and say what happened (VERDICT r4 #4d)."""
     clean = os.pathsep.join(p for p in os.environ.get("PATH", "").split(os.pathsep) if p and not os.path.exists(os.path.join(p, "rocprofv3")))
-    d = run_bench([sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--prewarm-ms", "10", "--no-extras", "--live-pmc"],
+    d = run_bench([sys.executable, "bench.py", "--full", "--steps", "6", "--warmup", "2", "--prewarm-ms", "10", "--no-extras", "--live-pmc"],
                   {"CRT_BENCH_REHEARSE": "0", "PATH": clean})
     r = d["roofline"]
     assert r["traffic_live_ok"] is False and "rocprofv3 not found" in r["traffic_live_note"] and r["traffic_live_child_rc"] == []
     assert r["traffic"] == r["traffic_committed_profile"] and r["traffic_source"].startswith("profiles/") and 0 < r["frac"] <= 1.0 and r["error"] is None
     assert d["value"] > 0 and d["synchronous_frames"]["value"] > 0
+
+
+def test_plain_line_times_only_the_steps_and_dumps_the_last_frame(tmp_path):
+    """A plain run (no --full) prints the contract's keys for exactly --steps timed steps and none of the legs that need runs of their own;
+    --dump-outputs writes the frame of the last timed step, the same bits the library renders for that scene and camera."""
+    from clraytracer_amd import driver, scenes
+    d = run_bench([sys.executable, "bench.py", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path)], {"CRT_BENCH_REHEARSE": "0"})
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in d, k
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    for k in ("synchronous_frames", "cpu_baseline", "scale_base_n1", "with_shadow_rays", "many_instances", "bvh_build"):
+        assert k not in d, k
+    assert d["roofline"]["traffic_live_ok"] is False and d["roofline"]["traffic_live_child_rc"] == []
+    assert sorted(os.listdir(tmp_path)) == ["frame.npy"]
+    frame = np.load(tmp_path / "frame.npy")
+    assert frame.dtype == np.float32 and frame.shape == (1080, 1920, 4)
+    with driver.Session(1920, 1080, device=0) as s:
+        s.load_scene(scenes.get("multi-1M"))
+        s.render_raw(0)
+        ref = s.read_output()
+    assert np.array_equal(frame.view(np.uint32), ref.view(np.uint32))

@@ -4,9 +4,10 @@ stb_image v2.27). The product's own decoder (clraytracer_amd/host/JpegDecode.cpp
 What pins what:
 * tests/golden/jpeg_stb.json holds, for every JPEG the reference ships, the SHA-256 of the bytes the REFERENCE's decoder
   produces (tests/golden/make_jpeg_golden.py runs the reference's stb_image.h, compiled as it lies into oracle/_ref/).
-* The JPEGs the asset scenes use are committed under assets/ at the repository root (data) -> checked everywhere, CPU only.
-* Where /root/reference is mounted, all 47 shipped JPEGs are checked, and where oracle/_ref/libstb_image_ref.so exists the
-  two decoders are also compared live, byte for byte, including on damaged streams (same pixels whenever both decode).
+* The JPEGs the asset scenes use are committed under assets/ at the repository root (data), the other shipped ones under
+  tests/golden/jpeg/ (files above 1 MiB as .part0, .part1, ... to be joined) -> all 47 checked everywhere, CPU only.
+* Where oracle/_ref/libstb_image_ref.so exists the two decoders are also compared live, byte for byte, including on
+  damaged streams (same pixels whenever both decode).
 Coverage of the shipped set: baseline and progressive, 4:4:4 and 4:2:0, grey-scale, restart intervals, Adobe APP14,
 odd sizes (155x23 ... 8192x4096)."""
 import ctypes as C
@@ -22,7 +23,7 @@ from clraytracer_amd import _lib, driver
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = json.load(open(os.path.join(HERE, "golden", "jpeg_stb.json")))
 FIXTURES = os.path.join(os.path.dirname(HERE), "assets", "Assets")
-REF_ASSETS = "/root/reference/CLRayTracer/Assets"
+GOLDEN_JPEG = os.path.join(HERE, "golden", "jpeg")
 REF_SO = os.path.join(_lib.ROOT, "oracle", "_ref", "libstb_image_ref.so")
 
 
@@ -39,21 +40,23 @@ def decode(data):
     return buf.raw, tuple(info)
 
 
-def locate(rel):
-    for base in (FIXTURES, REF_ASSETS):
-        p = os.path.join(base, rel)
+def read_fixture(rel):
+    """The bytes of a shipped JPEG: from assets/, or from tests/golden/jpeg/ (whole, or joined from its parts)."""
+    for p in (os.path.join(FIXTURES, rel), os.path.join(GOLDEN_JPEG, rel)):
         if os.path.exists(p):
-            return p
-    return None
+            return open(p, "rb").read()
+    parts, k = [], 0
+    while os.path.exists(os.path.join(GOLDEN_JPEG, f"{rel}.part{k}")):
+        parts.append(open(os.path.join(GOLDEN_JPEG, f"{rel}.part{k}"), "rb").read())
+        k += 1
+    return b"".join(parts) if parts else None
 
 
 @pytest.mark.parametrize("rel", sorted(GOLD))
 def test_decoder_matches_reference_stb_image_hashes(rel):
-    path = locate(rel)
-    if path is None:
-        pytest.skip("not among the committed fixtures and the reference tree is not mounted")
+    data = read_fixture(rel)
+    assert data is not None, f"{rel}: no committed fixture"
     g = GOLD[rel]
-    data = open(path, "rb").read()
     assert hashlib.sha256(data).hexdigest() == g["file_sha256"]
     rgb, info = decode(data)
     assert rgb is not None, info

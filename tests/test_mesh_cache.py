@@ -12,6 +12,7 @@ from clraytracer_amd import _lib, driver, scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libquicklz_ref.so")
+REF_GOLD = os.path.join(ROOT, "tests", "golden", "qlz_ref.json")   # the same codec's answers, recorded by tests/golden/make_qlz_golden.py
 REF_ASSETS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets", "Assets")   # the caches upstream ships, committed as data fixtures
 
 
@@ -153,6 +154,40 @@ def _clm_stream(blob):
     return nt, at + 8, comp
 
 
+def _recorded():
+    import json
+    return json.load(open(REF_GOLD))
+
+
+def ref_decoded_sha256(rel):
+    """SHA-256 of what the reference's qlz_decompress makes of a shipped cache's stream: live where oracle/_ref is built, else as recorded."""
+    import hashlib
+    if not os.path.exists(REF_SO):
+        return _recorded()["caches"][rel]["decoded_sha256"]
+    R = C.CDLL(REF_SO)
+    R.qlz_get_setting.restype = C.c_int
+    R.qlz_decompress.restype = C.c_size_t
+    R.qlz_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    blob = open(os.path.join(FIXTURE_ASSETS, rel), "rb").read()
+    nt, at, comp = _clm_stream(blob)
+    ref = C.create_string_buffer(nt * 80)
+    assert R.qlz_decompress(blob[at:at + comp], ref, C.create_string_buffer(R.qlz_get_setting(2))) == nt * 80
+    return hashlib.sha256(ref.raw).hexdigest()
+
+
+@pytest.mark.parametrize("rel", FIXTURE_CLMS)
+def test_shipped_caches_decode_like_the_reference_codec_anywhere(rel):
+    """The product's decoder on the caches upstream ships against the reference's own quicklz.c -- live where it is built, else its
+    recorded answers (tests/golden/qlz_ref.json): identical bytes."""
+    import hashlib
+    blob = open(os.path.join(FIXTURE_ASSETS, rel), "rb").read()
+    nt, at, comp = _clm_stream(blob)
+    n, got = qlz_decompress(blob[at:at + comp], nt * 80)
+    assert n == nt * 80 and hashlib.sha256(got.tobytes()).hexdigest() == ref_decoded_sha256(rel)
+    tris = np.frombuffer(got.tobytes(), _lib.TRI_DTYPE)
+    assert np.isfinite(tris["v0"]).all() and np.isfinite(tris["v1"]).all() and np.isfinite(tris["v2"]).all()
+
+
 @pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref/libquicklz_ref.so is only built where the reference tree is mounted")
 @pytest.mark.parametrize("rel", FIXTURE_CLMS)
 def test_shipped_caches_decode_like_the_reference_codec(rel):
@@ -251,6 +286,25 @@ def test_compressor_against_the_reference_codec():
         got_n, got = qlz_decompress(mine, len(raw))
         assert got_n == len(raw) and got.tobytes() == raw
     assert kinds == {0x47, 0x46, 0x45, 0x44} or kinds >= {0x47, 0x46, 0x45}     # long/short header, compressed/stored
+
+
+def compressor_inputs():
+    with driver.Session(64, 48, host_only=True) as s:
+        s.load_scene(scenes.get("tiny"))
+        tris = s.arenas()["tris"].copy()
+    return [tris.tobytes()] + list(_compressor_samples())
+
+
+def test_compressor_matches_the_recorded_reference_output():
+    """Byte-for-byte against the reference's qlz_compress as recorded in tests/golden/qlz_ref.json (length and SHA-256 of its output
+    for every input of test_compressor_against_the_reference_codec): the same check where the reference tree is not mounted."""
+    import hashlib
+    rec = _recorded()["compress"]
+    inputs = compressor_inputs()
+    assert len(rec) == len(inputs)
+    for raw, r in zip(inputs, rec):
+        mine = qlz_compress(raw)
+        assert (len(raw), len(mine), hashlib.sha256(mine).hexdigest()) == (r["raw_len"], r["comp_len"], r["sha256"]), len(raw)
 
 
 def test_compressor_round_trips_without_the_reference():

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 for form in "$@"; do
   line="$form"
   for sc in ${AB_SCENES:-multi-1M multi-1M-dense sponza-sibenik}; do
-    line="$line | $sc $(CRT_KERNEL=$form timeout -k 10 240 python bench.py --scene $sc --no-cpu-baseline --no-extras $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['synchronous_frames']['value'])")"
+    line="$line | $sc $(CRT_KERNEL=$form timeout -k 10 240 python bench.py --full --scene $sc --no-cpu-baseline --no-extras $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['synchronous_frames']['value'])")"
   done
   echo "$line" | tee -a gpurun_out/ab_forms.txt
 done

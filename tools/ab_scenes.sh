@@ -18,7 +18,7 @@ for name in "$@"; do
   cp build/ab/$name/libcrt_hip.so clraytracer_amd/csrc/libcrt_hip.so
   line="$name"
   for sc in ${AB_SCENES:-multi-1M sponza-sibenik multi-1M-dense nanosuit-demo}; do
-    line="$line | $sc $(timeout -k 10 240 python bench.py --scene $sc --no-cpu-baseline --no-extras $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['synchronous_frames']['value'])")"
+    line="$line | $sc $(timeout -k 10 240 python bench.py --full --scene $sc --no-cpu-baseline --no-extras $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['synchronous_frames']['value'])")"
   done
   echo "$line" | tee -a gpurun_out/ab_scenes.txt
 done

@@ -4,6 +4,15 @@
 #pragma once
 namespace {
 
+// the device counters of the last counted launch -> g.lastCounters, g.lastCulled
+static void unpack_counters(const unsigned long long c[CRT_NUM_COUNTERS])
+{
+    CrtCounters& o = g.lastCounters;
+    o.rays = c[0]; o.primary = c[1]; o.secondary = c[2]; o.hits = c[3]; o.misses = c[4]; o.traversals = c[5];
+    o.pops = c[6]; o.innerVisits = c[7]; o.triTests = c[8]; o.capHits = c[9]; o.stackOverflows = c[10]; o.maxStack = c[11];
+    o.shadowRays = c[12]; o.shadowHits = c[13]; g.lastCulled = c[14];
+}
+
 // Event timing is read back lazily: when the slot is about to be reused (which also bounds the frames in flight to
 // one per slot), or when somebody asks. Synchronous frames are complete by then, so this never blocks them.
 int collect_set(EventSet& es)
@@ -34,10 +43,7 @@ int collect_set(EventSet& es)
     if (es.flags & CRT_RENDER_COUNTERS) {
         unsigned long long c[CRT_NUM_COUNTERS];
         HIPCHK(hipMemcpy(c, g.counters, sizeof c, hipMemcpyDeviceToHost));
-        CrtCounters& o = g.lastCounters;
-        o.rays = c[0]; o.primary = c[1]; o.secondary = c[2]; o.hits = c[3]; o.misses = c[4]; o.traversals = c[5];
-        o.pops = c[6]; o.innerVisits = c[7]; o.triTests = c[8]; o.capHits = c[9]; o.stackOverflows = c[10]; o.maxStack = c[11];
-        o.shadowRays = c[12]; o.shadowHits = c[13]; g.lastCulled = c[14];
+        unpack_counters(c);
     }
     es.pending = false;
     return CRT_OK;
@@ -54,56 +60,54 @@ int collect_timing()
     return CRT_OK;
 }
 
+// Whether a frame with these flags rotates over the frame slots (crt1_render and the multi-device dispatcher). Everything
+// else -- synchronous frames, the diagnostic flags (they share the counters, the stamp and ray buffers) -- runs on slot 0.
+static bool frame_is_pipelined(int flags) { return (flags & CRT_RENDER_ASYNC) && !(flags & (CRT_RENDER_WRITE_RAYS | CRT_RENDER_COUNTERS | CRT_RENDER_STAMPS)); }
+
 // Feedback launch lists for the megakernel (lane_pixel / crt_order_kernel). Buffers follow the frame geometry; a
 // change of geometry resets to the identity order. The previous frame's per-tile costs are turned into this frame's
 // lists (and the costs zeroed) by a sort that is queued right AFTER the previous frame's last kernel and its end
 // event (sort_for_next_frame), so it runs while the host is between two crt1_render calls and is off the frame's
-// critical path (it used to open every frame: 10 us + a launch gap of a 0.5 ms synchronous frame).
+// critical path.
+// One allocation per slot (FrameSlot::lists), for n = 8 x listCap entries: order[n] | per-tile costs[n] | sort keys[n] | the 8 list lengths.
 // this frame's per-tile costs -> the next frame's lists; with g.costSpread > 0 a tile is ranked by its neighbours' costs too
-static void launch_order_kernel(const CrtFrame& F, FrameSlot& fs, bool pipelined, bool noSplit = false)
+static void launch_order_kernel(const CrtFrame& F, FrameSlot& fs, bool pipelined, bool noSplit)
 {
-    const uint32_t* key = fs.cost;
+    const size_t n = (size_t)8 * (size_t)F.listCap;
+    uint32_t* cost = fs.lists + n; uint32_t* key = cost;
     if (g.costSpread > 0.0f && g.viewMoved) {
-        uint32_t* k2 = fs.cost + fs.orderCap;                   // second half of the cost allocation
-        crt_cost_spread_kernel<<<(8 * F.slotsPerXcd + 255) / 256, 256, 0, fs.stream>>>(fs.cost, k2, F.slotsPerXcd, F.tilesX, g.costSpread);
-        key = k2;
+        key = cost + n;
+        crt_cost_spread_kernel<<<(8 * F.slotsPerXcd + 255) / 256, 256, 0, fs.stream>>>(cost, key, F.slotsPerXcd, F.tilesX, g.costSpread);
     }
-    crt_order_kernel<<<8, 1024, 0, fs.stream>>>(fs.cost, key, fs.order, fs.len, F.slotsPerXcd, F.listCap, noSplit ? 0u : (uint32_t)(pipelined ? g.maxSplitPipelined : g.maxSplit),
+    crt_order_kernel<<<8, 1024, 0, fs.stream>>>(cost, key, fs.lists, fs.lists + 3 * n, F.slotsPerXcd, F.listCap, noSplit ? 0u : (uint32_t)(pipelined ? g.maxSplitPipelined : g.maxSplit),
                                                  (pipelined ? g.splitBetaAsync : g.splitBeta) / (float)((g.numCUs / 8) * 4 * CRT_WAVES_PER_SIMD));
 }
 
+// noSplit: the lists of the refill / block forms, whose entries are blocks of tiles, are never split
 static int prepare_launch_lists(CrtFrame& F, unsigned& grid, FrameSlot& fs, bool pipelined, bool noSplit = false)
 {
     const int key[6] = { g.width, g.height, g.bandRows, g.rank, g.nRanks, F.slotsPerXcd };
     F.listCap = F.slotsPerXcd + 3 * CRT_MAX_SPLIT;
-    const size_t need = (size_t)8 * (size_t)F.listCap;
-    if (need > fs.orderCap) {
-        if (fs.order) (void)hipFree(fs.order);
-        if (fs.len) (void)hipFree(fs.len);
-        if (fs.cost) (void)hipFree(fs.cost);
-        fs.order = nullptr; fs.len = nullptr; fs.cost = nullptr; fs.orderCap = 0;
-        HIPCHK(hipMalloc(&fs.order, sizeof(uint32_t) * need));
-        HIPCHK(hipMalloc(&fs.len, sizeof(uint32_t) * 8));
-        HIPCHK(hipMalloc(&fs.cost, sizeof(uint32_t) * need * 2));        // costs, then the sort keys derived from them
-        fs.orderCap = need; fs.orderSlots = -1;
-    }
+    const size_t n = (size_t)8 * (size_t)F.listCap;
+    if (3 * n + 8 > fs.listsCap) fs.orderSlots = -1;     // new memory: start from the identity order
+    RCCHK(grow(fs.lists, fs.listsCap, 3 * n + 8, fs.stream));
     if (fs.orderSlots != F.slotsPerXcd || memcmp(key, fs.orderKey, sizeof key) != 0) {
-        HIPCHK(hipMemsetAsync(fs.cost, 0, sizeof(uint32_t) * need, fs.stream));
-        crt_identity_order_kernel<<<(8 * F.slotsPerXcd + 255) / 256, 256, 0, fs.stream>>>(fs.order, fs.len, F.slotsPerXcd, F.listCap);
+        HIPCHK(hipMemsetAsync(fs.lists + n, 0, sizeof(uint32_t) * n, fs.stream));
+        crt_identity_order_kernel<<<(8 * F.slotsPerXcd + 255) / 256, 256, 0, fs.stream>>>(fs.lists, fs.lists + 3 * n, F.slotsPerXcd, F.listCap);
         fs.orderSlots = F.slotsPerXcd; memcpy(fs.orderKey, key, sizeof key);
     } else if (!fs.listsReady) {
         launch_order_kernel(F, fs, pipelined, noSplit);
     }
     fs.listsReady = false;
     HIPCHK(hipGetLastError());
-    F.order = fs.order; F.listLen = fs.len; F.cost = fs.cost;
+    F.order = fs.lists; F.cost = fs.lists + n; F.listLen = fs.lists + 3 * n;
     grid = 8u * (unsigned)F.listCap;
     return CRT_OK;
 }
 
 // Queued behind a frame's last kernel: this frame's costs -> the next frame's lists (same geometry assumed; a change is
 // caught by the key in prepare_launch_lists, which then starts from the identity order again).
-static int sort_for_next_frame(const CrtFrame& F, FrameSlot& fs, bool pipelined, bool noSplit = false)
+static int sort_for_next_frame(const CrtFrame& F, FrameSlot& fs, bool pipelined, bool noSplit)
 {
     launch_order_kernel(F, fs, pipelined, noSplit);
     HIPCHK(hipGetLastError());
@@ -111,62 +115,122 @@ static int sort_for_next_frame(const CrtFrame& F, FrameSlot& fs, bool pipelined,
     return CRT_OK;
 }
 
-// The Trace launch(es) of one frame, by kernel structure (default: megakernel with feedback launch lists).
-// `out`: the frame the launch writes (the slot's frame, or its unfiltered copy when FXAA follows).
-// *epilogueApplied: the launch was the default megakernel, which applies F.epilogue (RGBA8 target / PostProcess) itself
-static int launch_trace(const CrtDevScene& S, const CrtFrame& F, int flags, unsigned grid, FrameSlot& fs, float4* out, bool* epilogueApplied, bool refill = false)
+// CRT_RENDER_DIAG_MIX3: three copies of the plain row-interleaved order, copy j starting a third of the XCD's list later:
+// entry 3 i + j = tile (i + j S / 3) mod S. One allocation: the 8 lists, then their 8 lengths.
+static int prepare_mix3_lists(CrtFrame& F, unsigned& grid, FrameSlot& fs)
 {
-    *epilogueApplied = false;
-    const bool count = (flags & CRT_RENDER_COUNTERS) != 0;
-    const bool stamped = (flags & CRT_RENDER_STAMPS) != 0;
-    // crt_debug_last_kernel: the Trace launch(es) of this frame under the names rocprofv3 prints for them
-    if (refill) snprintf(g.lastKernel, sizeof g.lastKernel, "%s<%d,%d>", g.refill == 2 ? "crt_trace_block_kernel" : "crt_trace_refill_kernel", stamped ? 0 : (int)count, (int)stamped);
-    else if (g.wavefront) snprintf(g.lastKernel, sizeof g.lastKernel, "crt_primary_kernel<%d>+crt_wavefront_scan_kernel+crt_bounce_kernel<%d>", (int)count, (int)count);
-    else if (g.ldstop) snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_ldstop_kernel<%d>", (int)count);
+    const int S = F.slotsPerXcd, S3 = 3 * S;
+    const size_t entries = (size_t)8 * S3;
+    if (entries + 8 > fs.mixCap) fs.mixSlots = -1;       // new memory: write the lists
+    RCCHK(grow(fs.mixOrder, fs.mixCap, entries + 8, fs.stream));
+    if (fs.mixSlots != S) {
+        std::vector<uint32_t> h(entries + 8, (uint32_t)S3);
+        for (int x = 0; x < 8; ++x)
+            for (int i = 0; i < S; ++i)
+                for (int j = 0; j < 3; ++j) h[(size_t)x * S3 + 3 * i + j] = (uint32_t)((i + j * (S / 3)) % S);
+        HIPCHK(hipMemcpyAsync(fs.mixOrder, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, fs.stream));
+        HIPCHK(hipStreamSynchronize(fs.stream));      // the host vector goes out of scope
+        fs.mixSlots = S;
+    }
+    F.order = fs.mixOrder; F.listLen = fs.mixOrder + entries; F.listCap = S3; F.cost = nullptr;
+    grid = 8u * (unsigned)S3;
+    return CRT_OK;
+}
+
+// CRT_KERNEL=ldstop: one workgroup per CRT_TOP_WAVES tiles of each XCD's list
+static unsigned ldstop_grid(const CrtFrame& F) { return (unsigned)((F.slotsPerXcd + CRT_TOP_WAVES - 1) / CRT_TOP_WAVES) * 8u; }
+
+// TLAS: more than CRT_TLAS_MIN_INSTANCES instances and an instance tree to walk (CRT_TLAS=0/1 forces). S.tlasNodes = 0: no
+// tree, or a launch without the cull.
+static bool use_tlas(const CrtDevScene& S) { return S.tlasNodes > 0 && S.numInstances <= g.instHigh && (g.forceTlas >= 0 ? g.forceTlas != 0 : S.numInstances > CRT_TLAS_MIN_INSTANCES); }
+
+// F in plain row-interleaved order (no launch lists); `whole`: every tile row of the frame, as if one rank rendered it all
+static CrtFrame plain_frame(const CrtFrame& F, bool whole)
+{
+    CrtFrame P = F;
+    P.order = nullptr; P.cost = nullptr; P.listLen = nullptr;
+    if (whole) { P.rank = 0; P.nRanks = 1; set_tile_grid(P, (g.height + CRT_TILE - 1) / CRT_TILE, P.tilesX); }
+    return P;
+}
+
+static bool is_primary() { return g.groupSize > 1 && g.primary == G; }
+static bool is_secondary() { return g.groupSize > 1 && g.primary != G; }
+
+// In a multi-device session the dispatcher (crt_render) decides once per frame what every device must agree on and hands it
+// to each device's crt1_render: the frame slot (so a device that owned no rows of some frame, or failed one, cannot fall out
+// of step with the primary's slot rotation) and whether the call may return before the device has finished (secondaries
+// never wait on the host: the primary's end-of-frame event waits for their partDone events, which is what gives a
+// synchronous N-device frame the duration of the longest share instead of the sum of two).
+struct RenderPlan { int slot; bool noHostWait; };
+
+// What the stages of one crt1_render share
+struct FrameCtx {
+    int flags = 0; const RenderPlan* plan = nullptr; bool pipelined = false;
+    int slot = 0; FrameSlot* fs = nullptr; EventSet* es = nullptr;
+    CrtFrame F; unsigned grid = 0;       // the frame in tiles (RayGen, the per-pixel stages); its workgroups: one per tile or list entry
+    CrtFrame T; unsigned gridT = 0;      // the Trace launch: F, or for refill / block the same frame in blocks of tiles
+    CrtDevScene S;
+    // fused: the Trace launch applied F.epilogue itself; gather8: frame_gathers_rgba8; packInKernel: the kernel that stores a
+    // final pixel stores its RGBA8 bytes too
+    bool fused = false, gather8 = false, packInKernel = false;
+};
+
+// The Trace launch(es) of one frame, by kernel form, on c.T and c.gridT. `out`: the frame the launch writes (the slot's frame,
+// or its unfiltered copy when FXAA follows). Sets c.fused: every form but wavefront applies T.epilogue (RGBA8 target /
+// PostProcess) in the Trace kernel.
+static int launch_trace(FrameCtx& c, float4* out)
+{
+    const CrtDevScene& S = c.S; const CrtFrame& T = c.T; const unsigned grid = c.gridT; FrameSlot& fs = *c.fs;
+    const bool count = (c.flags & CRT_RENDER_COUNTERS) != 0;
     if (count) HIPCHK(hipMemsetAsync(g.counters, 0, CRT_NUM_COUNTERS * sizeof(unsigned long long), fs.stream));
-    if (flags & CRT_RENDER_STAMPS) {                      // diagnostic launch with per-wave stamps
-        const size_t need = (16 + (size_t)grid * 8) * sizeof(unsigned long long);
-        if (need > g.stampBytes) {
-            if (g.stamps) (void)hipFree(g.stamps);
-            g.stamps = nullptr; g.stampBytes = 0;
-            HIPCHK(hipMalloc(&g.stamps, need));
-            g.stampBytes = need;
-        }
+    c.fused = true;
+    if (c.flags & CRT_RENDER_STAMPS) {   // diagnostic launch with per-wave stamps (megakernel, refill, block): the stamped instantiation applies T.epilogue too
+        const size_t words = 16 + (size_t)grid * 8;
+        RCCHK(grow(g.stamps, g.stampCap, words, fs.stream));
         g.stampWaves = grid;
-        HIPCHK(hipMemsetAsync(g.stamps, 0, need, fs.stream));
-        if (refill && g.refill == 2) crt_trace_block_kernel<false, true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, F, out, g.stamps, fs.blockQueue);
-        else if (refill) crt_trace_refill_kernel<false, true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, F, out, g.stamps);
-        else { crt_trace_kernel<false, true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, F, out, g.stamps); snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_kernel<0,1,0,0,0>"); }
-        *epilogueApplied = true;                           // the same kernel template: F.epilogue is applied there
-    } else if (refill) {                                   // in-tile lane refill (crt_refill.h); F counts blocks, not tiles
-        *epilogueApplied = true;
-        if (g.refill == 2) {
-            if (count) crt_trace_block_kernel<true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, F, out, g.counters, fs.blockQueue);
-            else crt_trace_block_kernel<false><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, F, out, g.counters, fs.blockQueue);
-        } else if (count) crt_trace_refill_kernel<true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, F, out, g.counters);
-        else crt_trace_refill_kernel<false><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, F, out, g.counters);
-    } else if (g.ldstop) {                                 // four tiles per workgroup sharing an LDS copy of the tree tops (crt_ldstop.h)
-        *epilogueApplied = true;
-        const unsigned gridW = (unsigned)((F.slotsPerXcd + CRT_TOP_WAVES - 1) / CRT_TOP_WAVES) * 8u;
-        if (count) crt_trace_ldstop_kernel<true><<<gridW, CRT_BLOCK * CRT_TOP_WAVES, 0, fs.stream>>>(S, F, out, g.counters);
-        else crt_trace_ldstop_kernel<false><<<gridW, CRT_BLOCK * CRT_TOP_WAVES, 0, fs.stream>>>(S, F, out, g.counters);
-    } else if (g.wavefront) {                              // bounce 0, ballot compaction, bounce 1
-        // per-slot state (crt1_render sized it): queue = one 64-record range per primary wave; counts, offsets, per-XCD totals
+        HIPCHK(hipMemsetAsync(g.stamps, 0, words * sizeof(unsigned long long), fs.stream));
+        if (g.form == Form::Block) crt_trace_block_kernel<false, true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.stamps, fs.blockQueue);
+        else if (g.form == Form::Refill) crt_trace_refill_kernel<false, true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.stamps);
+        else crt_trace_kernel<false, true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.stamps);
+        snprintf(g.lastKernel, sizeof g.lastKernel, "%s", g.form == Form::Block ? "crt_trace_block_kernel<0,1>" : g.form == Form::Refill ? "crt_trace_refill_kernel<0,1>" : "crt_trace_kernel<0,1,0,0,0>");
+        HIPCHK(hipGetLastError());
+        return CRT_OK;
+    }
+    // crt_debug_last_kernel: the Trace launch(es) of this frame under the names rocprofv3 prints for them
+    switch (g.form) {
+    case Form::Refill:
+    case Form::Block:                    // in-tile lane refill / block compaction (crt_refill.h); T counts blocks, not tiles
+        snprintf(g.lastKernel, sizeof g.lastKernel, "%s<%d,0>", g.form == Form::Block ? "crt_trace_block_kernel" : "crt_trace_refill_kernel", (int)count);
+        if (g.form == Form::Block) {
+            if (count) crt_trace_block_kernel<true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue);
+            else crt_trace_block_kernel<false><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue);
+        } else {
+            if (count) crt_trace_refill_kernel<true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters);
+            else crt_trace_refill_kernel<false><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters);
+        }
+        break;
+    case Form::LdsTop:                   // four tiles per workgroup sharing an LDS copy of the tree tops (crt_ldstop.h)
+        snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_ldstop_kernel<%d>", (int)count);
+        if (count) crt_trace_ldstop_kernel<true><<<ldstop_grid(T), CRT_BLOCK * CRT_TOP_WAVES, 0, fs.stream>>>(S, T, out, g.counters);
+        else crt_trace_ldstop_kernel<false><<<ldstop_grid(T), CRT_BLOCK * CRT_TOP_WAVES, 0, fs.stream>>>(S, T, out, g.counters);
+        break;
+    case Form::Wavefront: {              // bounce 0, ballot compaction, bounce 1
+        c.fused = false;
+        snprintf(g.lastKernel, sizeof g.lastKernel, "crt_primary_kernel<%d>+crt_wavefront_scan_kernel+crt_bounce_kernel<%d>", (int)count, (int)count);
+        // per-slot state (prepare_lists sized it): queue = one 64-record range per primary wave; counts, offsets, per-XCD totals
         uint32_t* cnt = fs.wfCount; uint32_t* offs = cnt + grid; uint32_t* total = offs + grid;
-        if (count) crt_primary_kernel<true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, F, out, g.counters, fs.blockQueue, cnt);
-        else crt_primary_kernel<false><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, F, out, g.counters, fs.blockQueue, cnt);
-        crt_wavefront_scan_kernel<<<8, 1024, 0, fs.stream>>>(cnt, offs, total, F.slotsPerXcd);
+        if (count) crt_primary_kernel<true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue, cnt);
+        else crt_primary_kernel<false><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue, cnt);
+        crt_wavefront_scan_kernel<<<8, 1024, 0, fs.stream>>>(cnt, offs, total, T.slotsPerXcd);
         // an XCD's tiles can all continue: the bounce launch has the primary launch's shape (waves past their XCD's total leave at once)
-        if (count) crt_bounce_kernel<true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, F, out, g.counters, fs.blockQueue, offs, total);
-        else crt_bounce_kernel<false><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, F, out, g.counters, fs.blockQueue, offs, total);
-    } else {
-        // default megakernel: <COUNT, STAMP, SHADOW, TLAS, REFRACT>
-        *epilogueApplied = true;
-        const bool shadow = (flags & CRT_RENDER_SHADOWS) != 0, refract = (flags & CRT_RENDER_REFRACTION) != 0;
-        // TLAS: more than CRT_TLAS_MIN_INSTANCES instances and an instance tree to walk (CRT_TLAS=0/1 forces)
-        const bool tlas = S.tlasNodes > 0 && (g.forceTlas >= 0 ? (g.forceTlas != 0 && S.numInstances <= g.instHigh) : (S.numInstances > CRT_TLAS_MIN_INSTANCES && S.numInstances <= g.instHigh));      // (S.tlasNodes = 0: no tree, or a frame without the cull)
+        if (count) crt_bounce_kernel<true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue, offs, total);
+        else crt_bounce_kernel<false><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue, offs, total);
+        break;
+    }
+    case Form::Mega: {                   // <COUNT, STAMP, SHADOW, TLAS, REFRACT>
+        const bool shadow = (c.flags & CRT_RENDER_SHADOWS) != 0, refract = (c.flags & CRT_RENDER_REFRACTION) != 0, tlas = use_tlas(S);
         snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_kernel<%d,0,%d,%d,%d>", (int)count, (int)shadow, (int)tlas, (int)refract);
-#define CRT_LAUNCH_TRACE3(C_, S_, T_, R_) crt_trace_kernel<C_, false, S_, T_, R_><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, F, out, g.counters)
+#define CRT_LAUNCH_TRACE3(C_, S_, T_, R_) crt_trace_kernel<C_, false, S_, T_, R_><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters)
 #define CRT_LAUNCH_TRACE2(C_, S_, T_) do { if (refract) CRT_LAUNCH_TRACE3(C_, S_, T_, true); else CRT_LAUNCH_TRACE3(C_, S_, T_, false); } while (0)
 #define CRT_LAUNCH_TRACE(C_, S_) do { if (tlas) CRT_LAUNCH_TRACE2(C_, S_, true); else CRT_LAUNCH_TRACE2(C_, S_, false); } while (0)
         if (count) { if (shadow) CRT_LAUNCH_TRACE(true, true); else CRT_LAUNCH_TRACE(true, false); }
@@ -174,22 +238,47 @@ static int launch_trace(const CrtDevScene& S, const CrtFrame& F, int flags, unsi
 #undef CRT_LAUNCH_TRACE
 #undef CRT_LAUNCH_TRACE2
 #undef CRT_LAUNCH_TRACE3
+        break;
+    }
     }
     HIPCHK(hipGetLastError());
     return CRT_OK;
 }
 
-// this slot's RGBA8 byte frame (4 B per pixel of the whole frame)
-static int ensure_pack(FrameSlot& fs, size_t framePixels)
+// The frame's launch lists, then what its kernel form's Trace launch needs: its frame and grid (c.T, c.gridT), its queues,
+// and the slot's traversal-stack overflow area. Feedback launch lists serve synchronous frames, whose end is decided by their
+// slowest waves. With frames in flight the tail is hidden by the next frame and the lists only cost (cost atomics, the sort
+// launch, quadrant waves at a quarter of the lane utilisation): 7.58 with, 7.72 Gray/s without on multi-1M -> pipelined
+// frames use the plain row-interleaved order.
+static int prepare_lists(FrameCtx& c)
 {
-    if (framePixels * 4 <= fs.packCap) return CRT_OK;
-    HIPCHK(hipStreamSynchronize(fs.stream));
-    if (fs.packBuf) (void)hipFree(fs.packBuf);
-    fs.packBuf = nullptr; fs.packCap = 0;
-    HIPCHK(hipMalloc(&fs.packBuf, framePixels * 4));
-    fs.packCap = framePixels * 4;
-    return CRT_OK;
+    FrameSlot& fs = *c.fs;
+    const bool feedback = g.feedback && (!c.pipelined || g.feedbackAsync);
+    c.grid = (unsigned)c.F.gridBlocks;
+    if (c.flags & CRT_RENDER_DIAG_MIX3) RCCHK(prepare_mix3_lists(c.F, c.grid, fs));
+    else if (feedback && g.form == Form::Mega) RCCHK(prepare_launch_lists(c.F, c.grid, fs, c.pipelined));
+    c.T = c.F; c.gridT = c.grid;
+    size_t ovfBlocks = c.grid;           // one overflow block per workgroup of the largest launch of this frame
+    switch (g.form) {
+    case Form::Mega: break;
+    case Form::Refill:
+    case Form::Block: {                  // the Trace launch (and its feedback lists) count blocks of tiles where F counts tiles
+        const int tiles = g.form == Form::Block ? CRT_BLOCK_TILES : CRT_REFILL_TILES;
+        set_tile_grid(c.T, c.F.ownedTileRows, (c.F.tilesX + tiles - 1) / tiles);
+        c.gridT = (unsigned)c.T.gridBlocks;
+        if (feedback) RCCHK(prepare_launch_lists(c.T, c.gridT, fs, c.pipelined, true));
+        if (g.form == Form::Block) RCCHK(grow(fs.blockQueue, fs.blockQueueCap, (size_t)c.T.gridBlocks * CRT_BLOCK_PIXELS, fs.stream));
+        break;
+    }
+    case Form::Wavefront:                // this slot's queue (64 records per primary wave), counts + offsets + per-XCD totals
+        RCCHK(grow(fs.blockQueue, fs.blockQueueCap, (size_t)c.grid * 64, fs.stream));
+        RCCHK(grow(fs.wfCount, fs.wfCap, (size_t)c.grid * 2 + 8, fs.stream));
+        break;
+    case Form::LdsTop: ovfBlocks = (size_t)ldstop_grid(c.F) * CRT_TOP_WAVES; break;   // one block per WAVE of the four-wave workgroups
+    }
+    return ensure_overflow(fs, ovfBlocks);
 }
+
 // Multi-device session: does a frame with these flags travel to the primary as RGBA8 bytes (4 B per pixel) instead of float4 (16 B)?
 // Upstream's render target IS RGBA8 (Renderer.cpp:63,192), CRT_RENDER_UNORM8 quantises every pixel in the Trace epilogue anyway, so the
 // bytes carry the whole frame: at 8 GPUs 7 x 4.1 MB instead of 7 x 16.6 MB per 3840x2160 frame converge on the primary's links. FXAA
@@ -199,7 +288,7 @@ static bool frame_gathers_rgba8(int flags) { return g.groupSize > 1 && g.gather8
 int crt1_prepare_gather8(void)
 {
     if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    for (int i = 0; i < g.nSlots; ++i) RCCHK(ensure_pack(g.slot[i], (size_t)g.width * (size_t)g.height));
+    for (int i = 0; i < g.nSlots; ++i) RCCHK(grow(g.slot[i].packBuf, g.slot[i].packCap, (size_t)g.width * (size_t)g.height, g.slot[i].stream));
     return CRT_OK;
 }
 // the float frame of slot `fs` from its byte frame, if the last frame on it was gathered as RGBA8 (the caller has drained the streams)
@@ -222,148 +311,68 @@ __global__ void crt_delay_kernel(unsigned long long ticks)
     while (__builtin_amdgcn_s_memrealtime() - r0 < ticks && guard < (1ull << 22)) { __builtin_amdgcn_s_sleep(16); ++guard; }
 }
 
-// In a multi-device session the dispatcher (crt_render) decides once per frame what every device must agree on and hands it
-// to each device's crt1_render: the frame slot (so a device that owned no rows of some frame, or failed one, cannot fall out
-// of step with the primary's slot rotation) and whether the call may return before the device has finished (secondaries
-// never wait on the host: the primary's end-of-frame event waits for their partDone events, which is what gives a
-// synchronous N-device frame the duration of the longest share instead of the sum of two).
-struct RenderPlan { int slot; bool noHostWait; };
-
-int crt1_render(const CrtTraceArgs* args, const float invView[16], const float invProj[16], int flags, const RenderPlan* plan = nullptr)
+// A device that owns no rows of this frame still takes part in the frame's hand-shake: its "bands have arrived" event is
+// recorded on the planned slot, so the primary's wait refers to this frame, not to an older one.
+static int record_empty_share(const RenderPlan* plan)
 {
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (!args || !invView || !invProj) return CRT_E_BAD_ARGUMENT;
-    if (args->numMeshes > CRT_MAX_INSTANCES) return CRT_E_OUT_OF_RANGE;
-    if (!g.sceneValid) return CRT_E_BAD_ARGUMENT;
-    int rc = CRT_OK;
-    CrtFrame F; fill_frame(F, args, invView, invProj);
-    if (F.gridBlocks == 0) {
-        // a device that owns no rows of this frame still takes part in the frame's hand-shake: its "bands have arrived"
-        // event is recorded on the planned slot so the primary's wait refers to this frame, not to an older one
-        if (plan && g.groupSize > 1 && g.primary != G && plan->slot >= 0 && plan->slot < g.nSlots) {
-            FrameSlot& efs = g.slot[plan->slot];
-            if (plan->slot != 0) g.othersBusy = true;
-            HIPCHK(hipEventRecord(efs.partDone, efs.stream));
-        }
-        return CRT_OK;
+    if (plan && is_secondary() && plan->slot >= 0 && plan->slot < g.nSlots) {
+        FrameSlot& fs = g.slot[plan->slot];
+        if (plan->slot != 0) g.othersBusy = true;
+        HIPCHK(hipEventRecord(fs.partDone, fs.stream));
     }
-    unsigned grid = (unsigned)F.gridBlocks;
+    return CRT_OK;
+}
 
-    // Slot choice: plain ASYNC frames of the default kernel rotate over the frame slots so consecutive frames
-    // overlap (each slot has its own stream, output buffer and launch lists). Everything else -- synchronous frames,
-    // diagnostic flags (they share the counters / the stamp and ray buffers) -- runs on slot 0. (Round 5: the wavefront form's queue belongs to
-    // the frame slot, so it keeps frames in flight like the default kernel.)
-    const bool variant = g.wavefront != 0;
-    if ((flags & (CRT_RENDER_SHADOWS | CRT_RENDER_REFRACTION)) && (flags & CRT_RENDER_STAMPS)) return CRT_E_UNSUPPORTED;   // the stamped instantiation is the plain one
-    // ONE rule for the opt-in kernel forms (CRT_KERNEL=wavefront / refill / block / ldstop; VERDICT r5 #1b): a frame the selected form cannot
-    // render is refused with CRT_E_UNSUPPORTED -- never rendered by another kernel behind the caller's back. What they lack: shadow rays,
-    // refraction, the three-frame diagnostic mix, the instance tree (CRT_TLAS=1); wavefront / ldstop: the stamped launch; refill / block: more than
-    // 64 instances (one 64-bit candidate mask per lane).
-    if (variant || g.refill || g.ldstop) {
+// Every CRT_E_UNSUPPORTED rule of a frame, checked before the frame changes any state. A frame the session's kernel form
+// cannot render is refused, never rendered by another kernel behind the caller's back.
+static int refuse_unsupported(int flags, uint32_t numMeshes)
+{
+    const bool stamped = (flags & CRT_RENDER_STAMPS) != 0;
+    if ((flags & (CRT_RENDER_SHADOWS | CRT_RENDER_REFRACTION)) && stamped) return CRT_E_UNSUPPORTED;   // the stamped instantiation is the plain one
+    // The opt-in forms lack shadow rays, refraction, the three-frame diagnostic mix and the instance tree (CRT_TLAS=1);
+    // wavefront and ldstop the stamped launch; refill and block more than 64 instances (one 64-bit candidate mask per lane).
+    if (g.form != Form::Mega) {
         if (flags & (CRT_RENDER_SHADOWS | CRT_RENDER_REFRACTION | CRT_RENDER_DIAG_MIX3)) return CRT_E_UNSUPPORTED;
         if (g.forceTlas == 1) return CRT_E_UNSUPPORTED;
-        if ((variant || g.ldstop) && (flags & CRT_RENDER_STAMPS)) return CRT_E_UNSUPPORTED;
-        if (g.refill && args->numMeshes > 64u) return CRT_E_UNSUPPORTED;
+        if ((g.form == Form::Wavefront || g.form == Form::LdsTop) && stamped) return CRT_E_UNSUPPORTED;
+        if ((g.form == Form::Refill || g.form == Form::Block) && numMeshes > 64u) return CRT_E_UNSUPPORTED;
     }
-    const bool refill = g.refill != 0;
-    const bool fxaa = (flags & CRT_RENDER_FXAA) != 0;
-    if (fxaa && g.groupSize <= 1 && g.nRanks > 1) return CRT_E_UNSUPPORTED;                  // the filter reads across band edges
-    const bool pipelined = (flags & CRT_RENDER_ASYNC)
-                        && !(flags & (CRT_RENDER_WRITE_RAYS | CRT_RENDER_COUNTERS | CRT_RENDER_STAMPS));
-    int slot = 0;
-    if (plan) {                              // multi-device session: the dispatcher chose the slot for every device
-        slot = pipelined ? plan->slot : 0;
-        if (slot < 0 || slot >= g.nSlots) return CRT_E_BAD_ARGUMENT;
-        if (!pipelined) { rc = quiesce(); if (rc) return rc; }
-    } else if (pipelined) slot = (int)(g.asyncSeq++ % (unsigned)g.nSlots);
-    else { rc = quiesce(); if (rc) return rc; }
-    FrameSlot& fs = g.slot[slot];
-    EventSet& es = fs.es[fs.frames & 1u];
-    rc = collect_set(es);                    // waits for the frame two back on this slot: at most two queued per slot
-    if (rc) return rc;
-    if (flags & CRT_RENDER_COUNTERS) { rc = collect_timing(); if (rc) return rc; }
-    if (slot != 0) g.othersBusy = true;
-    rc = ensure_slot_instances(fs);          // this slot's instance tables, refreshed on its stream if an upload happened since
-    if (rc) return rc;
-    CrtDevScene S;
-    // Feedback launch lists serve synchronous frames, whose end is decided by their slowest waves. With frames in flight the
-    // tail is hidden by the next frame and the lists only cost (cost atomics, the sort launch, quadrant waves at a quarter
-    // of the lane utilisation): 7.58 with, 7.72 Gray/s without on multi-1M -> pipelined frames use the plain row-interleaved order.
-    const bool mix3 = (flags & CRT_RENDER_DIAG_MIX3) != 0;
-    if (mix3) {
-        if (pipelined || variant || g.groupSize > 1 || (flags & (CRT_RENDER_STAMPS | CRT_RENDER_WRITE_RAYS | CRT_RENDER_FXAA))) return CRT_E_UNSUPPORTED;
-        // three copies of the plain row-interleaved order, copy j starting a third of the XCD's list later: entry 3 i + j = tile (i + j S / 3) mod S
-        const int S3 = 3 * F.slotsPerXcd;
-        if ((size_t)8 * S3 > fs.mixCap) {
-            HIPCHK(hipStreamSynchronize(fs.stream));
-            if (fs.mixOrder) (void)hipFree(fs.mixOrder);
-            if (fs.mixLen) (void)hipFree(fs.mixLen);
-            fs.mixOrder = nullptr; fs.mixLen = nullptr; fs.mixCap = 0; fs.mixSlots = -1;
-            HIPCHK(hipMalloc(&fs.mixOrder, sizeof(uint32_t) * 8 * (size_t)S3));
-            HIPCHK(hipMalloc(&fs.mixLen, sizeof(uint32_t) * 8));
-            fs.mixCap = (size_t)8 * S3;
-        }
-        if (fs.mixSlots != F.slotsPerXcd) {
-            std::vector<uint32_t> h((size_t)8 * S3), len(8, (uint32_t)S3);
-            for (int x = 0; x < 8; ++x)
-                for (int i = 0; i < F.slotsPerXcd; ++i)
-                    for (int j = 0; j < 3; ++j) h[(size_t)x * S3 + 3 * i + j] = (uint32_t)((i + j * (F.slotsPerXcd / 3)) % F.slotsPerXcd);
-            HIPCHK(hipMemcpyAsync(fs.mixOrder, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, fs.stream));
-            HIPCHK(hipMemcpyAsync(fs.mixLen, len.data(), 8 * sizeof(uint32_t), hipMemcpyHostToDevice, fs.stream));
-            HIPCHK(hipStreamSynchronize(fs.stream));      // the host vectors go out of scope
-            fs.mixSlots = F.slotsPerXcd;
-        }
-        F.order = fs.mixOrder; F.listLen = fs.mixLen; F.listCap = S3; F.cost = nullptr;
-        grid = 8u * (unsigned)S3;
-    } else
-    if (g.feedback && !g.wavefront && !g.ldstop && !refill && (!pipelined || g.feedbackAsync)) { rc = prepare_launch_lists(F, grid, fs, pipelined); if (rc) return rc; }
-    // CRT_KERNEL=refill: the Trace launch (and its feedback lists) count BLOCKS of CRT_REFILL_TILES tiles where F counts tiles
-    CrtFrame FB = F; unsigned gridB = grid;
-    if (refill) {
-        const int tiles = g.refill == 2 ? CRT_BLOCK_TILES : CRT_REFILL_TILES;
-        FB.tilesX = (F.tilesX + tiles - 1) / tiles;
-        FB.gridBlocks = ((F.ownedTileRows + 7) / 8) * 8 * FB.tilesX;
-        FB.slotsPerXcd = FB.gridBlocks / 8; FB.listCap = FB.slotsPerXcd;
-        gridB = (unsigned)FB.gridBlocks;
-        if (g.feedback && (!pipelined || g.feedbackAsync)) { rc = prepare_launch_lists(FB, gridB, fs, pipelined, true); if (rc) return rc; }
-        if (g.refill == 2) {
-            const size_t need = (size_t)FB.gridBlocks * CRT_BLOCK_PIXELS;
-            if (need > fs.blockQueueCap) {
-                HIPCHK(hipStreamSynchronize(fs.stream));
-                if (fs.blockQueue) (void)hipFree(fs.blockQueue);
-                fs.blockQueue = nullptr; fs.blockQueueCap = 0;
-                HIPCHK(hipMalloc(&fs.blockQueue, need * sizeof(CrtBounceRay)));
-                fs.blockQueueCap = need;
-            }
-        }
-    }
-    if (variant) {                           // CRT_KERNEL=wavefront: this slot's queue (64 records per primary wave), counts + offsets + totals
-        const size_t need = (size_t)grid * 64, needCnt = (size_t)grid * 2 + 8;
-        if (need > fs.blockQueueCap || needCnt > fs.wfCap) {
-            HIPCHK(hipStreamSynchronize(fs.stream));
-            if (fs.blockQueue) (void)hipFree(fs.blockQueue);
-            if (fs.wfCount) (void)hipFree(fs.wfCount);
-            fs.blockQueue = nullptr; fs.blockQueueCap = 0; fs.wfCount = nullptr; fs.wfCap = 0;
-            HIPCHK(hipMalloc(&fs.blockQueue, need * sizeof(CrtBounceRay)));
-            fs.blockQueueCap = need;
-            HIPCHK(hipMalloc(&fs.wfCount, needCnt * sizeof(uint32_t)));
-            fs.wfCap = needCnt;
-        }
-    }
-    {   // overflow blocks: one per workgroup of the largest launch of this frame
-        size_t blocks = grid;
-        if (g.ldstop) blocks = (size_t)((F.slotsPerXcd + CRT_TOP_WAVES - 1) / CRT_TOP_WAVES) * CRT_TOP_WAVES * 8;   // one block per WAVE of the four-wave workgroups
-        rc = ensure_overflow(fs, blocks); if (rc) return rc;
-    }
-    fill_scene(S, args->numMeshes, fs, beyond_cull_range(sqrt((double)args->cameraPos[0] * args->cameraPos[0] + (double)args->cameraPos[1] * args->cameraPos[1] + (double)args->cameraPos[2] * args->cameraPos[2])));
+    if ((flags & CRT_RENDER_FXAA) && g.groupSize <= 1 && g.nRanks > 1) return CRT_E_UNSUPPORTED;   // the filter reads across band edges
+    // the three-frame mix: a synchronous frame of one device, without the other diagnostics or FXAA
+    if ((flags & CRT_RENDER_DIAG_MIX3) && (frame_is_pipelined(flags) || g.groupSize > 1 || (flags & (CRT_RENDER_STAMPS | CRT_RENDER_WRITE_RAYS | CRT_RENDER_FXAA))))
+        return CRT_E_UNSUPPORTED;
+    return CRT_OK;
+}
 
-    // events: [0] frame start, [1] Trace start, [2] Trace end, [3] end of PostProcess = frame end.
-    // A plain frame records only two (RayGen is fused, PostProcess off): [0] == [1], [2] == [3].
+// Slot choice: pipelined frames rotate over the frame slots so consecutive frames overlap (each slot has its own stream,
+// output buffer, launch lists and queues); every other frame runs on slot 0 once the other slots have drained.
+static int choose_slot(FrameCtx& c)
+{
+    c.pipelined = frame_is_pipelined(c.flags);
+    c.slot = 0;
+    if (c.pipelined) c.slot = c.plan ? c.plan->slot : (int)(g.asyncSeq++ % (unsigned)g.nSlots);   // a session's dispatcher chose it for every device
+    if (c.slot < 0 || c.slot >= g.nSlots) return CRT_E_BAD_ARGUMENT;
+    if (!c.pipelined) RCCHK(quiesce());
+    c.fs = &g.slot[c.slot];
+    c.es = &c.fs->es[c.fs->frames & 1u];
+    RCCHK(collect_set(*c.es));               // waits for the frame two back on this slot: at most two queued per slot
+    if (c.flags & CRT_RENDER_COUNTERS) RCCHK(collect_timing());
+    if (c.slot != 0) g.othersBusy = true;
+    return ensure_slot_instances(*c.fs);     // this slot's instance tables, refreshed on its stream if an upload happened since
+}
+
+// The scene as this frame sees it, the start of the statistics extent, the start-up stagger, the frame's first event and RayGen.
+// events: [0] frame start, [1] Trace start, [2] Trace end, [3] end of PostProcess = frame end.
+// A plain frame records only two (RayGen is fused, PostProcess off): [0] == [1], [2] == [3].
+static int begin_frame(FrameCtx& c, const CrtTraceArgs* args)
+{
+    FrameSlot& fs = *c.fs; EventSet& es = *c.es;
+    fill_scene(c.S, args->numMeshes, fs, beyond_cull_range(sqrt((double)args->cameraPos[0] * args->cameraPos[0] + (double)args->cameraPos[1] * args->cameraPos[1] + (double)args->cameraPos[2] * args->cameraPos[2])));
     if (g.statStartArmed) {                  // first frame since the statistics were reset: start of the extent
         HIPCHK(hipEventRecord(g.statStart, fs.stream));
         g.statStartArmed = false; g.statStartValid = true; g.statStartSeq = g.frameSeq + 1; g.statExtent = 0; g.statFirstMs = 0; g.frameLogN = 0;
     }
-    if (pipelined) {
+    if (c.pipelined) {
         // first frame of this slot in a burst that starts from an idle device: hold it back so the slots do not run in lockstep
         const unsigned k = g.burstFrames++;
         // (automatic only with up to three slots: with eight -- a rank's small share of a tiled frame, where one frame cannot fill the
@@ -375,113 +384,115 @@ int crt1_render(const CrtTraceArgs* args, const float invView[16], const float i
             if (us >= 5.0) { crt_delay_kernel<<<1, 64, 0, fs.stream>>>((unsigned long long)(us * 100.0)); HIPCHK(hipGetLastError()); g.staggeredFrames++; }
         }
     } else { if (g.burstFrames) g.prevBurstFrames = g.burstFrames; g.burstFrames = 0; }
-    es.evRaygen = (flags & CRT_RENDER_WRITE_RAYS) != 0;
-    es.evPost = (flags & (CRT_RENDER_POSTPROCESS | CRT_RENDER_UNORM8 | CRT_RENDER_FXAA)) != 0;
+    es.evRaygen = (c.flags & CRT_RENDER_WRITE_RAYS) != 0;
+    es.evPost = (c.flags & (CRT_RENDER_POSTPROCESS | CRT_RENDER_UNORM8 | CRT_RENDER_FXAA)) != 0;
     HIPCHK(hipEventRecord(es.ev[0], fs.stream));
     if (es.evRaygen) {
-        crt_raygen_kernel<<<grid, CRT_BLOCK, 0, fs.stream>>>(F, g.rays);
+        crt_raygen_kernel<<<c.grid, CRT_BLOCK, 0, fs.stream>>>(c.F, g.rays);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(es.ev[1], fs.stream));
     }
-    // upstream's per-pixel stages behind Trace (its RGBA8 render target, PostProcess) ride in the Trace kernel's epilogue
-    // unless a kernel variant without the epilogue is selected. FXAA sits between them and reads neighbours: on one device
-    // Trace then writes the slot's second buffer (its pixels already through the RGBA8 target) and the filter writes the
-    // frame, applying PostProcess and the final RGBA8 store in ITS epilogue -- two launches, no copy.
-    const bool unorm = (flags & CRT_RENDER_UNORM8) != 0, post = (flags & CRT_RENDER_POSTPROCESS) != 0;
+    return CRT_OK;
+}
+
+// In-process multi-GPU, primary device: the frame is complete when every secondary's bands have arrived -- its last event is
+// recorded behind waits for their partDone events (recorded before this call: the dispatcher submits the secondaries first).
+static int wait_for_parts(const FrameCtx& c)
+{
+    for (int d = 1; d < g.groupSize; ++d) HIPCHK(hipStreamWaitEvent(c.fs->stream, g.group[d]->slot[c.slot].partDone, 0));
+    return CRT_OK;
+}
+
+// The Trace launch and the per-pixel stages behind it, up to the frame's end event. Upstream's stages behind Trace (its RGBA8
+// render target, PostProcess) ride in the Trace kernel's epilogue unless the kernel form has none. FXAA sits between them and
+// reads neighbours: on one device Trace then writes the slot's second buffer (its pixels already through the RGBA8 target) and
+// the filter writes the frame, applying PostProcess and the final RGBA8 store in ITS epilogue -- two launches, no copy.
+static int launch_passes(FrameCtx& c)
+{
+    FrameSlot& fs = *c.fs; EventSet& es = *c.es; CrtFrame& F = c.F;
+    const bool unorm = (c.flags & CRT_RENDER_UNORM8) != 0, post = (c.flags & CRT_RENDER_POSTPROCESS) != 0, fxaa = (c.flags & CRT_RENDER_FXAA) != 0;
     const bool fxaaLocal = fxaa && g.groupSize <= 1;
     const size_t framePixels = (size_t)g.width * (size_t)g.height;
-    if (fxaa && !(g.groupSize > 1 && g.primary != G) && fs.auxPixels < framePixels) {
-        HIPCHK(hipStreamSynchronize(fs.stream));
-        if (fs.aux) (void)hipFree(fs.aux);
-        fs.aux = nullptr; fs.auxPixels = 0;
-        HIPCHK(hipMalloc(&fs.aux, framePixels * sizeof(float4)));
-        fs.auxPixels = framePixels;
-    }
+    if (fxaa && !is_secondary()) RCCHK(grow(fs.aux, fs.auxPixels, framePixels, fs.stream));
     if (!fxaa) F.epilogue = (unorm ? CRT_EPILOGUE_QUANTIZE : 0u) | (post ? CRT_EPILOGUE_POST : 0u);
     else if (fxaaLocal) F.epilogue = unorm ? CRT_EPILOGUE_QUANTIZE : 0u;
-    // a read-back of the RGBA8 frame: the kernel that stores the final pixel stores its four bytes too (one device; a
-    // multi-device session packs the gathered frame on its first device)
-    // ... a multi-device session's RGBA8 frame: every device's kernel stores its pixels' bytes and the BYTES are gathered (frame_gathers_rgba8)
-    const bool gather8 = frame_gathers_rgba8(flags);
-    const bool packInKernel = unorm && (((flags & CRT_RENDER_READBACK) && g.groupSize <= 1) || gather8);
-    if (packInKernel) RCCHK(ensure_pack(fs, framePixels));
-    if (packInKernel && !fxaa) F.packOut = fs.packBuf;
-    bool fused = false;
-    if (refill) { FB.epilogue = F.epilogue; FB.packOut = F.packOut; }
-    rc = launch_trace(S, refill ? FB : F, flags, refill ? gridB : grid, fs, fxaaLocal ? fs.aux : fs.out, &fused, refill);
-    if (rc) return rc;
-    // in-process multi-GPU, primary device: the frame is complete when every secondary's bands have arrived -- its last
-    // event is recorded behind waits for their partDone events (recorded before this call: the dispatcher submits the
-    // secondaries first)
-    const bool isPrimary = g.groupSize > 1 && g.primary == G, isSecondary = g.groupSize > 1 && g.primary != G;
-    auto wait_for_parts = [&]() -> int {
-        for (int d = 1; d < g.groupSize; ++d) HIPCHK(hipStreamWaitEvent(fs.stream, g.group[d]->slot[slot].partDone, 0));
-        return CRT_OK;
-    };
-    if (isPrimary && !es.evPost) RCCHK(wait_for_parts());
+    // the kernel that stores the final pixel stores its four bytes too: for a read-back of the RGBA8 frame on one device (a
+    // multi-device session packs the gathered frame on its first device), and on every device of a session whose RGBA8 frames
+    // are gathered as bytes
+    c.gather8 = frame_gathers_rgba8(c.flags);
+    c.packInKernel = unorm && (((c.flags & CRT_RENDER_READBACK) && g.groupSize <= 1) || c.gather8);
+    if (c.packInKernel) RCCHK(grow(fs.packBuf, fs.packCap, framePixels, fs.stream));
+    if (c.packInKernel && !fxaa) F.packOut = fs.packBuf;
+    c.T.epilogue = F.epilogue; c.T.packOut = F.packOut;
+    RCCHK(launch_trace(c, fxaaLocal ? fs.aux : fs.out));
+    if (is_primary() && !es.evPost) RCCHK(wait_for_parts(c));
     HIPCHK(hipEventRecord(es.ev[2], fs.stream));
-    if (es.evPost) {
+    if (!es.evPost) return CRT_OK;
+    if (!fxaa) {
         // upstream: Trace write_imagef's into an RGBA8 texture, PostProcess read_imagef's it back and write_imagef's again
-        if (!fxaa) {
-            if (!fused) {
-                if (unorm) crt_quantize_kernel<<<grid, CRT_BLOCK, 0, fs.stream>>>(F, fs.out);
-                if (post) crt_postprocess_kernel<<<grid, CRT_BLOCK, 0, fs.stream>>>(F, fs.out);
-                if (unorm && post) crt_quantize_kernel<<<grid, CRT_BLOCK, 0, fs.stream>>>(F, fs.out);
-                // RGBA8 gather behind a kernel form without the epilogue (wavefront): the bytes as a launch of their own (rows of other
-                // devices are not touched: on the primary their bytes may already have arrived)
-                if (gather8) { CrtFrame FP = F; FP.order = nullptr; FP.cost = nullptr; FP.listLen = nullptr; crt_pack_owned_kernel<<<(unsigned)F.gridBlocks, CRT_BLOCK, 0, fs.stream>>>(FP, fs.out, fs.packBuf); }
-                HIPCHK(hipGetLastError());
-            }
-            if (isPrimary) RCCHK(wait_for_parts());
-        } else if (!isSecondary) {
-            // FXAA reads up to 5 pixels around its own in the Trace result, so it runs on the whole frame: a multi-device
-            // session gathers the raw bands first (the secondaries skip their per-pixel stages) and its first device filters
-            if (isPrimary) RCCHK(wait_for_parts());
-            CrtFrame FF = F;                                // every tile row, plain order
-            FF.order = nullptr; FF.cost = nullptr; FF.listLen = nullptr;
-            FF.rank = 0; FF.nRanks = 1;
-            FF.ownedTileRows = (g.height + CRT_TILE - 1) / CRT_TILE;
-            FF.gridBlocks = ((FF.ownedTileRows + 7) / 8) * 8 * FF.tilesX;
-            FF.slotsPerXcd = FF.gridBlocks / 8; FF.listCap = FF.slotsPerXcd;
-            const unsigned gridAll = (unsigned)FF.gridBlocks;
-            if (fxaaLocal) {
-                if (unorm && !fused) crt_quantize_kernel<<<gridAll, CRT_BLOCK, 0, fs.stream>>>(FF, fs.aux);
-            } else {
-                if (unorm) crt_quantize_kernel<<<gridAll, CRT_BLOCK, 0, fs.stream>>>(FF, fs.out);
-                HIPCHK(hipMemcpyAsync(fs.aux, fs.out, framePixels * sizeof(float4), hipMemcpyDeviceToDevice, fs.stream));
-            }
-            FF.epilogue = (unorm ? CRT_EPILOGUE_QUANTIZE : 0u) | (post ? CRT_EPILOGUE_POST : 0u);
-            FF.packOut = packInKernel ? fs.packBuf : nullptr;
-            crt_fxaa_kernel<<<gridAll, CRT_BLOCK, 0, fs.stream>>>(FF, fs.aux, fs.out);
+        if (!c.fused) {
+            if (unorm) crt_quantize_kernel<<<c.grid, CRT_BLOCK, 0, fs.stream>>>(F, fs.out);
+            if (post) crt_postprocess_kernel<<<c.grid, CRT_BLOCK, 0, fs.stream>>>(F, fs.out);
+            if (unorm && post) crt_quantize_kernel<<<c.grid, CRT_BLOCK, 0, fs.stream>>>(F, fs.out);
+            // RGBA8 gather behind a kernel form without the epilogue (wavefront): the bytes as a launch of their own (rows of other
+            // devices are not touched: on the primary their bytes may already have arrived)
+            if (c.gather8) crt_pack_owned_kernel<<<(unsigned)F.gridBlocks, CRT_BLOCK, 0, fs.stream>>>(plain_frame(F, false), fs.out, fs.packBuf);
             HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipEventRecord(es.ev[3], fs.stream));
+        if (is_primary()) RCCHK(wait_for_parts(c));
+    } else if (!is_secondary()) {
+        // FXAA reads up to 5 pixels around its own in the Trace result, so it runs on the whole frame: a multi-device session
+        // gathers the raw bands first (the secondaries skip their per-pixel stages) and its first device filters
+        if (is_primary()) RCCHK(wait_for_parts(c));
+        CrtFrame FF = plain_frame(F, true);
+        const unsigned gridAll = (unsigned)FF.gridBlocks;
+        if (fxaaLocal) {
+            if (unorm && !c.fused) crt_quantize_kernel<<<gridAll, CRT_BLOCK, 0, fs.stream>>>(FF, fs.aux);
+        } else {
+            if (unorm) crt_quantize_kernel<<<gridAll, CRT_BLOCK, 0, fs.stream>>>(FF, fs.out);
+            HIPCHK(hipMemcpyAsync(fs.aux, fs.out, framePixels * sizeof(float4), hipMemcpyDeviceToDevice, fs.stream));
+        }
+        FF.epilogue = (unorm ? CRT_EPILOGUE_QUANTIZE : 0u) | (post ? CRT_EPILOGUE_POST : 0u);
+        FF.packOut = c.packInKernel ? fs.packBuf : nullptr;
+        crt_fxaa_kernel<<<gridAll, CRT_BLOCK, 0, fs.stream>>>(FF, fs.aux, fs.out);
+        HIPCHK(hipGetLastError());
     }
-    if (isSecondary) {
-        // gather: this device's bands go into the primary's frame of the same slot (peer copy over xGMI), once the primary
-        // is done with whatever the slot's previous frame still had queued (its read-back)
-        FrameSlot& pfs = g.primary->slot[slot];
-        HIPCHK(hipStreamWaitEvent(fs.stream, pfs.slotDone, 0));
-        if (gather8) RCCHK(copy_owned_rows_async(pfs.packBuf, fs.packBuf, 4, hipMemcpyDeviceToDevice, fs.stream));
-        else RCCHK(copy_owned_rows_async(pfs.out, fs.out, 16, hipMemcpyDeviceToDevice, fs.stream));
-        HIPCHK(hipEventRecord(fs.partDone, fs.stream));
-    }
-    fs.frameIs8 = gather8;
-    g.cur = slot;
-    es.pending = true; es.flags = flags; es.seq = ++g.frameSeq; fs.frames++;
-    const bool sorted = (refill ? FB.order : F.order) != nullptr && !mix3;
-    if (sorted) {
+    HIPCHK(hipEventRecord(es.ev[3], fs.stream));
+    return CRT_OK;
+}
+
+// Secondary device: this device's bands go into the primary's frame of the same slot (peer copy over xGMI), once the primary
+// is done with whatever the slot's previous frame still had queued (its read-back).
+static int gather_to_primary(const FrameCtx& c)
+{
+    FrameSlot& fs = *c.fs; FrameSlot& pfs = g.primary->slot[c.slot];
+    HIPCHK(hipStreamWaitEvent(fs.stream, pfs.slotDone, 0));
+    if (c.gather8) RCCHK(copy_owned_rows_async(pfs.packBuf, fs.packBuf, 4, hipMemcpyDeviceToDevice, fs.stream));
+    else RCCHK(copy_owned_rows_async(pfs.out, fs.out, 16, hipMemcpyDeviceToDevice, fs.stream));
+    HIPCHK(hipEventRecord(fs.partDone, fs.stream));
+    return CRT_OK;
+}
+
+// The frame is queued: its bookkeeping, the sort for the next frame, the read-back (CRT_RENDER_READBACK), and for a
+// synchronous frame the reference's clFinish (Renderer.cpp:367).
+static int finish_frame(const FrameCtx& c)
+{
+    FrameSlot& fs = *c.fs; EventSet& es = *c.es;
+    fs.frameIs8 = c.gather8;
+    g.cur = c.slot;
+    es.pending = true; es.flags = c.flags; es.seq = ++g.frameSeq; fs.frames++;
+    if (c.T.order != nullptr && !(c.flags & CRT_RENDER_DIAG_MIX3)) {
         // did the view change since the last sorted frame? (camera matrices and position, instance tables)
         float view[35];
-        memcpy(view, F.invView, 64); memcpy(view + 16, F.invProj, 64); memcpy(view + 32, F.camPos, 12);
+        memcpy(view, c.F.invView, 64); memcpy(view + 16, c.F.invProj, 64); memcpy(view + 32, c.F.camPos, 12);
         g.viewMoved = memcmp(view, g.lastView, sizeof view) != 0 || g.lastViewInst != g.instVersion;
         memcpy(g.lastView, view, sizeof view); g.lastViewInst = g.instVersion;
-        rc = sort_for_next_frame(refill ? FB : F, fs, pipelined, refill); if (rc) return rc;
+        RCCHK(sort_for_next_frame(c.T, fs, c.pipelined, g.form != Form::Mega));
     }
-    if (flags & CRT_RENDER_READBACK) {
+    if (c.flags & CRT_RENDER_READBACK) {
         // the frame travels to pinned host memory behind its own kernels; the other slots' frames keep the GPU busy meanwhile
         const size_t pixels = (size_t)g.width * (size_t)g.height;
-        const bool bytes8 = (flags & CRT_RENDER_UNORM8) != 0;
+        const bool bytes8 = (c.flags & CRT_RENDER_UNORM8) != 0;
         const size_t bytes = pixels * (bytes8 ? 4 : 16);
         if (bytes > fs.hostCap) {
             if (fs.hostBuf) (void)hipHostFree(fs.hostBuf);
@@ -492,28 +503,41 @@ int crt1_render(const CrtTraceArgs* args, const float invView[16], const float i
         if (!fs.copied) HIPCHK(hipEventCreateWithFlags(&fs.copied, hipEventDisableTiming));
         const void* src = fs.out;
         if (bytes8) {
-            RCCHK(ensure_pack(fs, pixels));
-            const bool packed = (packInKernel && (fxaa || fused)) || gather8;     // the Trace (or FXAA) kernel stored the bytes already / the byte frame was gathered
+            RCCHK(grow(fs.packBuf, fs.packCap, pixels, fs.stream));
+            // the Trace (or FXAA) kernel stored the bytes already / the byte frame was gathered
+            const bool packed = (c.packInKernel && ((c.flags & CRT_RENDER_FXAA) || c.fused)) || c.gather8;
             if (!packed) crt_pack_unorm8_kernel<<<(unsigned)((pixels + 255) / 256), 256, 0, fs.stream>>>(fs.out, fs.packBuf, pixels);
             HIPCHK(hipGetLastError());
             src = fs.packBuf;
         }
         // only the rows this rank renders travel (the host buffer keeps the full-frame layout)
-        RCCHK(copy_owned_rows_async(fs.hostBuf, src, bytes8 ? 4 : 16, hipMemcpyDeviceToHost, fs.stream, isPrimary));
+        RCCHK(copy_owned_rows_async(fs.hostBuf, src, bytes8 ? 4 : 16, hipMemcpyDeviceToHost, fs.stream, is_primary()));
         HIPCHK(hipEventRecord(fs.copied, fs.stream));
-        fs.hostBytes = bytes; g.readbackRing[g.readbackCount++ % CRT_MAX_FRAMES_IN_FLIGHT] = slot;
+        fs.hostBytes = bytes; g.readbackRing[g.readbackCount++ % CRT_MAX_FRAMES_IN_FLIGHT] = c.slot;
     }
-    if (isPrimary) HIPCHK(hipEventRecord(fs.slotDone, fs.stream));
-    // the reference's clFinish (Renderer.cpp:367): wait for the frame's end event -- the sort for the next frame that is
-    // queued behind it needs no waiting for
-    if (!(flags & CRT_RENDER_ASYNC) && !(plan && plan->noHostWait)) HIPCHK(hipEventSynchronize(es.evPost ? es.ev[3] : es.ev[2]));
+    if (is_primary()) HIPCHK(hipEventRecord(fs.slotDone, fs.stream));
+    // wait for the frame's end event -- the sort for the next frame that is queued behind it needs no waiting for
+    if (!(c.flags & CRT_RENDER_ASYNC) && !(c.plan && c.plan->noHostWait)) HIPCHK(hipEventSynchronize(es.evPost ? es.ev[3] : es.ev[2]));
     return CRT_OK;
 }
 
-// Whether a frame with these flags rotates over the frame slots (the rule of crt1_render, for the dispatcher)
-static bool frame_is_pipelined(int flags)
+int crt1_render(const CrtTraceArgs* args, const float invView[16], const float invProj[16], int flags, const RenderPlan* plan = nullptr)
 {
-    return (flags & CRT_RENDER_ASYNC) && !(flags & (CRT_RENDER_WRITE_RAYS | CRT_RENDER_COUNTERS | CRT_RENDER_STAMPS));
+    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
+    if (!args || !invView || !invProj) return CRT_E_BAD_ARGUMENT;
+    if (args->numMeshes > CRT_MAX_INSTANCES) return CRT_E_OUT_OF_RANGE;
+    if (!g.sceneValid) return CRT_E_BAD_ARGUMENT;
+    FrameCtx c;
+    c.flags = flags; c.plan = plan;
+    fill_frame(c.F, args, invView, invProj);
+    if (c.F.gridBlocks == 0) return record_empty_share(plan);
+    RCCHK(refuse_unsupported(flags, args->numMeshes));
+    RCCHK(choose_slot(c));
+    RCCHK(prepare_lists(c));
+    RCCHK(begin_frame(c, args));
+    RCCHK(launch_passes(c));
+    if (is_secondary()) RCCHK(gather_to_primary(c));
+    return finish_frame(c);
 }
 
 // Diagnostic: the shader clock under whatever load the device carries right now. One wave per XCD spins for `micros`
@@ -564,17 +588,11 @@ int crt1_query_hits(const float* origins, const float* dirs, int n, uint32_t num
     if (n <= 0) return CRT_OK;
     if (!origins || !dirs || !out || numInstances > CRT_MAX_INSTANCES) return CRT_E_BAD_ARGUMENT;
     if (!g.sceneValid) return CRT_E_BAD_ARGUMENT;
-    int rc = collect_timing();
-    if (rc) return rc;
+    RCCHK(collect_timing());
     RCCHK(quiesce());
     const size_t rayBytes = sizeof(float) * 3 * (size_t)n, need = rayBytes * 2 + sizeof(CrtRayHit) * (size_t)n;
-    if (need > g.queryBytes) {
-        if (g.queryBuf) (void)hipFree(g.queryBuf);
-        g.queryBuf = nullptr; g.queryBytes = 0;
-        HIPCHK(hipMalloc(&g.queryBuf, need));
-        g.queryBytes = need;
-    }
-    float* dO = static_cast<float*>(g.queryBuf);
+    RCCHK(grow(g.queryBuf, g.queryBytes, need, g.stream));
+    float* dO = reinterpret_cast<float*>(g.queryBuf);
     float* dD = dO + 3 * (size_t)n;
     CrtRayHit* dH = reinterpret_cast<CrtRayHit*>(dD + 3 * (size_t)n);
     HIPCHK(hipMemcpyAsync(dO, origins, rayBytes, hipMemcpyHostToDevice, g.stream));
@@ -589,18 +607,14 @@ int crt1_query_hits(const float* origins, const float* dirs, int n, uint32_t num
         if (!(d2 <= farthest2)) farthest2 = d2;      // (NaN sticks)
     }
     CrtDevScene S; fill_scene(S, numInstances, fs, beyond_cull_range(sqrt(farthest2)));
-    const bool tlas = S.tlasNodes > 0 && (g.forceTlas >= 0 ? (g.forceTlas != 0 && numInstances <= g.instHigh) : (numInstances > CRT_TLAS_MIN_INSTANCES && numInstances <= g.instHigh));
-    if (tlas) crt_query_kernel<true><<<(unsigned)((n + CRT_BLOCK - 1) / CRT_BLOCK), CRT_BLOCK, 0, g.stream>>>(S, dO, dD, n, dH, g.counters);
+    if (use_tlas(S)) crt_query_kernel<true><<<(unsigned)((n + CRT_BLOCK - 1) / CRT_BLOCK), CRT_BLOCK, 0, g.stream>>>(S, dO, dD, n, dH, g.counters);
     else crt_query_kernel<false><<<(unsigned)((n + CRT_BLOCK - 1) / CRT_BLOCK), CRT_BLOCK, 0, g.stream>>>(S, dO, dD, n, dH, g.counters);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dH, sizeof(CrtRayHit) * (size_t)n, hipMemcpyDeviceToHost, g.stream));
     unsigned long long c[CRT_NUM_COUNTERS];
     HIPCHK(hipMemcpyAsync(c, g.counters, sizeof c, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
-    CrtCounters& o = g.lastCounters;
-    o.rays = c[0]; o.primary = c[1]; o.secondary = c[2]; o.hits = c[3]; o.misses = c[4]; o.traversals = c[5];
-    o.pops = c[6]; o.innerVisits = c[7]; o.triTests = c[8]; o.capHits = c[9]; o.stackOverflows = c[10]; o.maxStack = c[11];
-    o.shadowRays = c[12]; o.shadowHits = c[13]; g.lastCulled = c[14];
+    unpack_counters(c);
     return CRT_OK;
 }
 
@@ -634,13 +648,8 @@ int crt1_read_output_rgba8(uint8_t* dst, size_t bytes)
         HIPCHK(hipMemcpy(dst, g.slot[g.cur].packBuf, pixels * 4, hipMemcpyDeviceToHost));
         return CRT_OK;
     }
-    if (pixels * 4 > g.queryBytes) {                       // shares the query scratch buffer
-        if (g.queryBuf) (void)hipFree(g.queryBuf);
-        g.queryBuf = nullptr; g.queryBytes = 0;
-        HIPCHK(hipMalloc(&g.queryBuf, pixels * 4));
-        g.queryBytes = pixels * 4;
-    }
-    crt_pack_unorm8_kernel<<<(unsigned)((pixels + 255) / 256), 256, 0, g.stream>>>(g.slot[g.cur].out, static_cast<uint32_t*>(g.queryBuf), pixels);
+    RCCHK(grow(g.queryBuf, g.queryBytes, pixels * 4, g.stream));   // shares the query scratch buffer
+    crt_pack_unorm8_kernel<<<(unsigned)((pixels + 255) / 256), 256, 0, g.stream>>>(g.slot[g.cur].out, reinterpret_cast<uint32_t*>(g.queryBuf), pixels);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(dst, g.queryBuf, pixels * 4, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
@@ -731,8 +740,7 @@ int crt1_get_culled_visits(uint64_t* out)
 {
     if (!g.initialized) return CRT_E_NOT_INITIALIZED;
     if (!out) return CRT_E_BAD_ARGUMENT;
-    int rc = collect_timing();
-    if (rc) return rc;
+    RCCHK(collect_timing());
     *out = g.lastCulled;
     return CRT_OK;
 }
@@ -755,8 +763,7 @@ int crt1_get_counters(CrtCounters* out)
 {
     if (!g.initialized) return CRT_E_NOT_INITIALIZED;
     if (!out) return CRT_E_BAD_ARGUMENT;
-    int rc = collect_timing();
-    if (rc) return rc;
+    RCCHK(collect_timing());
     *out = g.lastCounters;
     return CRT_OK;
 }

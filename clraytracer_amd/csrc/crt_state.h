@@ -10,6 +10,12 @@ namespace {
 #define CRT_MAX_FRAMES_IN_FLIGHT 8
 #define CRT_MAX_DEVICES 16
 
+// The Trace kernel structure of a session (CRT_KERNEL). Mega: the megakernel with feedback launch lists (the default).
+// The opt-in forms: Wavefront, one launch per bounce with ordered ballot compaction in between (crt_kernels.h); Refill, in-tile
+// lane refill, and Block, phase-separated block compaction (crt_refill.h); LdsTop, four-wave workgroups sharing an LDS copy of
+// the tree tops (crt_ldstop.h).
+enum class Form { Mega, Wavefront, Refill, Block, LdsTop };
+
 struct EventSet {
     hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
     bool pending = false; int flags = 0; bool evRaygen = false, evPost = false;   // timing not yet read back
@@ -24,11 +30,12 @@ struct FrameSlot {
     float4* aux = nullptr; size_t auxPixels = 0;   // CRT_RENDER_FXAA: the unfiltered frame the filter reads (allocated on first use)
     CrtBounceRay* blockQueue = nullptr; size_t blockQueueCap = 0;   // CRT_KERNEL=block / wavefront: bounce-ray queue, one 64- or 128-record range per workgroup of the primary launch
     uint32_t* wfCount = nullptr; size_t wfCap = 0;                  // CRT_KERNEL=wavefront: per primary wave {continuing rays}, {offset within its XCD}, then the 8 per-XCD totals
-    uint32_t* ovf = nullptr; size_t ovfBlocks = 0;   // traversal-stack overflow area of this slot's launches (CrtStack), one block per workgroup
-    uint32_t* order = nullptr; uint32_t* len = nullptr; uint32_t* cost = nullptr;   // feedback launch lists
-    size_t orderCap = 0; int orderSlots = -1; int orderKey[6] = { 0, 0, 0, 0, 0, 0 };
+    uint32_t* ovf = nullptr; size_t ovfWords = 0;   // traversal-stack overflow area of this slot's launches (CrtStack), one block per workgroup
+    uint32_t* lists = nullptr; size_t listsCap = 0;   // feedback launch lists: order, costs, sort keys, lengths (prepare_launch_lists)
+    int orderSlots = -1; int orderKey[6] = { 0, 0, 0, 0, 0, 0 };
     bool listsReady = false;                   // the lists for the next frame were already sorted at the end of the last one
-    // CRT_RENDER_READBACK: pinned host copy of this slot's frame, queued behind the frame on the slot's stream
+    // CRT_RENDER_READBACK: pinned host copy of this slot's frame, queued behind the frame on the slot's stream; packBuf: the
+    // frame's RGBA8 bytes, packCap pixels
     void* hostBuf = nullptr; size_t hostCap = 0, hostBytes = 0; uint32_t* packBuf = nullptr; size_t packCap = 0; hipEvent_t copied = nullptr;
     // This slot's copy of the instance tables (reference-layout records, device records, bounding spheres, instance tree,
     // never-culled list), refreshed on the slot's own stream from the host master when it is stale (ensure_slot_instances):
@@ -37,7 +44,7 @@ struct FrameSlot {
     CrtMeshInstance* instances = nullptr; CrtDevInstance* devInstances = nullptr; float4* instBounds = nullptr;
     CrtTlasNode* tlas = nullptr; uint32_t* alwaysList = nullptr; uint32_t tlasNodes = 0, numAlways = 0;
     unsigned long long instVersion = 0;        // 0 = never filled (the master starts at 1)
-    uint32_t* mixOrder = nullptr; uint32_t* mixLen = nullptr; size_t mixCap = 0; int mixSlots = -1;   // CRT_RENDER_DIAG_MIX3 launch lists
+    uint32_t* mixOrder = nullptr; size_t mixCap = 0; int mixSlots = -1;   // CRT_RENDER_DIAG_MIX3 launch lists, then their 8 lengths
     char* stagingDev = nullptr;                // the staging block as the device sees it
     char* staging = nullptr; hipEvent_t staged = nullptr;   // pinned staging block and "its copies have been issued and done" event
     // in-process multi-GPU (crt_init_devices): a secondary device records `partDone` behind the copy of its bands into the
@@ -96,7 +103,7 @@ struct State {
     CrtMeshInstance hInstances[CRT_MAX_INSTANCES]; uint32_t hRoots[CRT_MAX_MESHES]; uint32_t instHigh = 0;
     float* rays = nullptr;
     unsigned long long* counters = nullptr; int* err = nullptr;
-    unsigned long long* stamps = nullptr; size_t stampBytes = 0, stampWaves = 0;
+    unsigned long long* stamps = nullptr; size_t stampCap = 0, stampWaves = 0;
     int numCUs = 0;
     int forceTlas = -1;   // CRT_TLAS=0/1: force the linear / tree candidate search (tests); default: by instance count
     int feedbackAsync = 0; int feedback = 1; int maxSplit = CRT_MAX_SPLIT, maxSplitPipelined = CRT_MAX_SPLIT_PIPELINED;
@@ -105,12 +112,10 @@ struct State {
     float costSpread = 0.8f;
     float lastView[35] = { 0 }; unsigned long long lastViewInst = 0; bool viewMoved = false;   // camera matrices + position / instance version of the last sorted frame
     float splitBeta = CRT_SPLIT_BETA, splitBetaAsync = CRT_SPLIT_BETA_ASYNC;   // split a tile whose wave would run longer than beta x the XCD's time for the frame
-    int refill = 0;                            // CRT_KERNEL=refill / block: 1 = in-tile lane refill, 2 = phase-separated block compaction (crt_refill.h), every frame (one they cannot render is refused)
-    int ldstop = 0;                            // CRT_KERNEL=ldstop: four-wave workgroups sharing an LDS copy of the tree tops (crt_ldstop.h)
+    Form form = Form::Mega;                    // CRT_KERNEL: the Trace kernel structure of every frame (one the form cannot render is refused)
     float4* topPairs = nullptr; uint32_t* topRootRefs = nullptr;   // the tree-top table (CRT_TOP_PAIRS records) and every mesh's entry into it, rebuilt with the BVH layout
-    int wavefront = 0;                         // CRT_KERNEL=wavefront: one launch per bounce, ordered ballot compaction in between (crt_kernels.h)
     char lastKernel[128] = { 0 };              // crt_debug_last_kernel: the Trace launch(es) of the most recently submitted frame
-    void* queryBuf = nullptr; size_t queryBytes = 0;
+    char* queryBuf = nullptr; size_t queryBytes = 0;
     void* buildBuf = nullptr; size_t buildBytes = 0;          // crt_build_bvh scratch
     std::vector<CrtBuildCtl> buildReplay; unsigned long long buildReplayKey = 0;   // CRT_DEBUG_BVH_REPLAY (crt_bvh_driver.h): the level records of the last build
     unsigned buildLaunches = 0, buildLevels = 0;   // crt_debug_build_stats: kernel launches and levels of the last crt_build_bvh (before the re-layout)
@@ -149,6 +154,19 @@ static inline void crt_cpu_relax()
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { return (int)e_; } } while (0)
 #define RCCHK(x) do { int r_ = (x); if (r_ != CRT_OK) { return r_; } } while (0)
 
+// Grows device buffer `p` to hold `count` elements (no-op when `cap` already does): waits for `s`, the stream that last used it,
+// frees it and allocates anew. Contents are not kept. On failure p == nullptr, cap == 0.
+template <class T> int grow(T*& p, size_t& cap, size_t count, hipStream_t s)
+{
+    if (count <= cap) return CRT_OK;
+    HIPCHK(hipStreamSynchronize(s));
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    HIPCHK(hipMalloc(&p, count * sizeof(T)));
+    cap = count;
+    return CRT_OK;
+}
+
 // Wait for frames still running on the second slot before anything touches shared device state.
 int quiesce()
 {
@@ -177,6 +195,16 @@ int owned_tile_rows()
     return n;
 }
 
+// F's launch geometry for `tileRows` x `tilesX` tiles: the tile rows rounded up to a multiple of 8, dealt over the 8 XCDs
+void set_tile_grid(CrtFrame& F, int tileRows, int tilesX)
+{
+    F.tilesX = tilesX;
+    F.ownedTileRows = tileRows;
+    F.gridBlocks = ((tileRows + 7) / 8) * 8 * tilesX;
+    F.slotsPerXcd = F.gridBlocks / 8;
+    F.listCap = F.slotsPerXcd;
+}
+
 void fill_frame(CrtFrame& F, const CrtTraceArgs* args, const float* invView, const float* invProj)
 {
     memset(&F, 0, sizeof F);
@@ -188,11 +216,7 @@ void fill_frame(CrtFrame& F, const CrtTraceArgs* args, const float* invView, con
         F.lightZ = (float)cos((double)args->sunAngle);
     }
     F.width = g.width; F.height = g.height;
-    F.tilesX = (g.width + CRT_TILE - 1) / CRT_TILE;
-    F.ownedTileRows = owned_tile_rows();
-    F.gridBlocks = ((F.ownedTileRows + 7) / 8) * 8 * F.tilesX;
-    F.slotsPerXcd = F.gridBlocks / 8;
-    F.order = nullptr; F.cost = nullptr; F.listLen = nullptr; F.listCap = F.slotsPerXcd;
+    set_tile_grid(F, owned_tile_rows(), (g.width + CRT_TILE - 1) / CRT_TILE);
     F.tileRowsPerBand = g.bandRows / CRT_TILE;
     F.rank = g.rank; F.nRanks = g.nRanks;
 }
@@ -213,17 +237,9 @@ void fill_scene(CrtDevScene& S, uint32_t numInstances, const FrameSlot& fs, bool
 // true when a ray origin this far from the world origin is outside the proven range (NaN counts as outside)
 bool beyond_cull_range(double originNorm) { return !(originNorm <= (double)g.cullOriginLimit); }
 
-// The traversal-stack overflow area of a slot must hold one block per workgroup of its largest launch.
-int ensure_overflow(FrameSlot& fs, size_t blocks)
-{
-    if (blocks <= fs.ovfBlocks) return CRT_OK;
-    HIPCHK(hipStreamSynchronize(fs.stream));
-    if (fs.ovf) (void)hipFree(fs.ovf);
-    fs.ovf = nullptr; fs.ovfBlocks = 0;
-    HIPCHK(hipMalloc(&fs.ovf, blocks * CRT_OVF_WORDS_PER_BLOCK * sizeof(uint32_t)));   // never initialised: entries are written before they are read
-    fs.ovfBlocks = blocks;
-    return CRT_OK;
-}
+// The traversal-stack overflow area of a slot must hold one block per workgroup of its largest launch. It is never
+// initialised: entries are written before they are read.
+int ensure_overflow(FrameSlot& fs, size_t blocks) { return grow(fs.ovf, fs.ovfWords, blocks * CRT_OVF_WORDS_PER_BLOCK, fs.stream); }
 
 // New frame buffers are allocated first and swapped in only when every allocation succeeded: a failed resize leaves
 // the old frame size fully usable (crt_resize returns the error).

@@ -78,14 +78,14 @@ static int init_impl(int device, int width, int height)
     g.numCUs = prop.multiProcessorCount;
     {   // CRT_KERNEL: the Trace kernel structure of this session. Unset / "" / "default": the megakernel (faster);
         // "wavefront", "refill", "block": the opt-in compaction forms, "ldstop": tree tops staged in LDS. Anything else is a typo, not a wish for
-        // the default: the session refuses to start (VERDICT r5 #3 -- a variant test must not pass because the name stopped matching).
+        // the default: the session refuses to start, so a form's test cannot pass on the megakernel because the name stopped matching.
         const char* e = getenv("CRT_KERNEL");
-        g.wavefront = 0; g.refill = 0; g.ldstop = 0;
+        g.form = Form::Mega;
         if (e && *e && strcmp(e, "default") != 0) {
-            if (strcmp(e, "wavefront") == 0) g.wavefront = 1;
-            else if (strcmp(e, "ldstop") == 0) g.ldstop = 1;
-            else if (strcmp(e, "refill") == 0) g.refill = 1;
-            else if (strcmp(e, "block") == 0) g.refill = 2;
+            if (strcmp(e, "wavefront") == 0) g.form = Form::Wavefront;
+            else if (strcmp(e, "ldstop") == 0) g.form = Form::LdsTop;
+            else if (strcmp(e, "refill") == 0) g.form = Form::Refill;
+            else if (strcmp(e, "block") == 0) g.form = Form::Block;
             else { fprintf(stderr, "crt_init: CRT_KERNEL=%s is not one of default, wavefront, refill, block, ldstop\n", e); return CRT_E_BAD_ARGUMENT; }
         }
     }
@@ -127,7 +127,7 @@ static void release_all()
                      g.texels, g.materials, g.textures, g.rays, g.counters, g.err, g.triReachBits, g.topPairs, g.topRootRefs,
                      g.queryBuf, g.buildBuf, g.buildTris, g.stamps, g.noCullBounds };
     for (FrameSlot& fs : g.slot) {
-        void* q[] = { fs.out, fs.aux, fs.blockQueue, fs.wfCount, fs.ovf, fs.order, fs.len, fs.cost, fs.mixOrder, fs.mixLen, fs.packBuf, fs.instBlock, fs.devInstances };
+        void* q[] = { fs.out, fs.aux, fs.blockQueue, fs.wfCount, fs.ovf, fs.lists, fs.mixOrder, fs.packBuf, fs.instBlock, fs.devInstances };
         for (void* p : q) if (p) (void)hipFree(p);
         if (fs.staging) (void)hipHostFree(fs.staging);
         if (fs.staged) (void)hipEventDestroy(fs.staged);

@@ -162,6 +162,8 @@ struct CrtFrame {
     int listCap;              // capacity of one XCD's list = slotsPerXcd + 3 * CRT_MAX_SPLIT
     uint32_t* cost;           // per tile: shader cycles the wave spent on it this frame (feeds the next frame's order)
     uint32_t epilogue;        // crt_trace_kernel: per-pixel stages applied before the pixel is stored (CRT_EPILOGUE_*); 0 = the plain HDR value
+    int ss;                   // crt_trace_ssaa_kernel: k of k x k supersampling (CRT_RENDER_SSAA2/4), 1 otherwise. It sits in the padding before
+                              // packOut, so the struct's size -- and with it the offsets of every kernel argument behind F -- is unchanged
     uint32_t* packOut;        // with CRT_EPILOGUE_QUANTIZE: also store the pixel's RGBA8 bytes here (the frame a read-back delivers); or null
 };
 

@@ -86,7 +86,7 @@ static void launch_order_kernel(const CrtFrame& F, FrameSlot& fs, bool pipelined
 // noSplit: the lists of the refill / block forms, whose entries are blocks of tiles, are never split
 static int prepare_launch_lists(CrtFrame& F, unsigned& grid, FrameSlot& fs, bool pipelined, bool noSplit = false)
 {
-    const int key[6] = { g.width, g.height, g.bandRows, g.rank, g.nRanks, F.slotsPerXcd };
+    const int key[7] = { g.width, g.height, g.bandRows, g.rank, g.nRanks, F.slotsPerXcd, F.ss };   // ss: another factor is another tile grid
     F.listCap = F.slotsPerXcd + 3 * CRT_MAX_SPLIT;
     const size_t n = (size_t)8 * (size_t)F.listCap;
     if (3 * n + 8 > fs.listsCap) fs.orderSlots = -1;     // new memory: start from the identity order
@@ -144,11 +144,16 @@ static unsigned ldstop_grid(const CrtFrame& F) { return (unsigned)((F.slotsPerXc
 // tree, or a launch without the cull.
 static bool use_tlas(const CrtDevScene& S) { return S.tlasNodes > 0 && S.numInstances <= g.instHigh && (g.forceTlas >= 0 ? g.forceTlas != 0 : S.numInstances > CRT_TLAS_MIN_INSTANCES); }
 
-// F in plain row-interleaved order (no launch lists); `whole`: every tile row of the frame, as if one rank rendered it all
+// F in plain row-interleaved order (no launch lists); `whole`: every tile row of the frame, as if one rank rendered it all.
+// Of an SSAA frame: the output frame W x H (the per-pixel stages behind Trace run on the resolved pixels).
 static CrtFrame plain_frame(const CrtFrame& F, bool whole)
 {
     CrtFrame P = F;
     P.order = nullptr; P.cost = nullptr; P.listLen = nullptr;
+    if (F.ss > 1) {
+        P.ss = 1; P.width = g.width; P.height = g.height; P.tileRowsPerBand = g.bandRows / CRT_TILE;
+        set_tile_grid(P, owned_tile_rows(g.height, g.bandRows), (g.width + CRT_TILE - 1) / CRT_TILE);
+    }
     if (whole) { P.rank = 0; P.nRanks = 1; set_tile_grid(P, (g.height + CRT_TILE - 1) / CRT_TILE, P.tilesX); }
     return P;
 }
@@ -174,6 +179,8 @@ struct FrameCtx {
     // final pixel stores its RGBA8 bytes too
     bool fused = false, gather8 = false, packInKernel = false;
 };
+
+static int launch_trace_ssaa(FrameCtx& c, float4* out, bool count, bool shadow, bool refract, bool tlas);
 
 // The Trace launch(es) of one frame, by kernel form, on c.T and c.gridT. `out`: the frame the launch writes (the slot's frame,
 // or its unfiltered copy when FXAA follows). Sets c.fused: every form but wavefront applies T.epilogue (RGBA8 target /
@@ -229,6 +236,7 @@ static int launch_trace(FrameCtx& c, float4* out)
     }
     case Form::Mega: {                   // <COUNT, STAMP, SHADOW, TLAS, REFRACT>
         const bool shadow = (c.flags & CRT_RENDER_SHADOWS) != 0, refract = (c.flags & CRT_RENDER_REFRACTION) != 0, tlas = use_tlas(S);
+        if (T.ss > 1) return launch_trace_ssaa(c, out, count, shadow, refract, tlas);   // CRT_RENDER_SSAA2 / SSAA4
         snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_kernel<%d,0,%d,%d,%d>", (int)count, (int)shadow, (int)tlas, (int)refract);
 #define CRT_LAUNCH_TRACE3(C_, S_, T_, R_) crt_trace_kernel<C_, false, S_, T_, R_><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters)
 #define CRT_LAUNCH_TRACE2(C_, S_, T_) do { if (refract) CRT_LAUNCH_TRACE3(C_, S_, T_, true); else CRT_LAUNCH_TRACE3(C_, S_, T_, false); } while (0)
@@ -241,6 +249,24 @@ static int launch_trace(FrameCtx& c, float4* out)
         break;
     }
     }
+    HIPCHK(hipGetLastError());
+    return CRT_OK;
+}
+
+// The Trace launch of a supersampled frame (the default form only; refuse_ssaa): c.T is the virtual frame. (Defined behind
+// launch_trace so that its kernels are emitted behind crt_trace_kernel's: the existing kernels keep their code addresses.)
+static int launch_trace_ssaa(FrameCtx& c, float4* out, bool count, bool shadow, bool refract, bool tlas)
+{
+    const CrtDevScene& S = c.S; const CrtFrame& T = c.T; const unsigned grid = c.gridT; FrameSlot& fs = *c.fs;
+    snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_ssaa_kernel<%d,%d,%d,%d>", (int)count, (int)shadow, (int)tlas, (int)refract);
+#define CRT_LAUNCH_SSAA3(C_, S_, T_, R_) crt_trace_ssaa_kernel<C_, S_, T_, R_><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters)
+#define CRT_LAUNCH_SSAA2(C_, S_, T_) do { if (refract) CRT_LAUNCH_SSAA3(C_, S_, T_, true); else CRT_LAUNCH_SSAA3(C_, S_, T_, false); } while (0)
+#define CRT_LAUNCH_SSAA(C_, S_) do { if (tlas) CRT_LAUNCH_SSAA2(C_, S_, true); else CRT_LAUNCH_SSAA2(C_, S_, false); } while (0)
+    if (count) { if (shadow) CRT_LAUNCH_SSAA(true, true); else CRT_LAUNCH_SSAA(true, false); }
+    else       { if (shadow) CRT_LAUNCH_SSAA(false, true); else CRT_LAUNCH_SSAA(false, false); }
+#undef CRT_LAUNCH_SSAA
+#undef CRT_LAUNCH_SSAA2
+#undef CRT_LAUNCH_SSAA3
     HIPCHK(hipGetLastError());
     return CRT_OK;
 }
@@ -323,6 +349,22 @@ static int record_empty_share(const RenderPlan* plan)
     return CRT_OK;
 }
 
+// k of a frame's k x k supersampling (CRT_RENDER_SSAA2 / SSAA4; both at once is refused by crt1_render before this is asked)
+static int ssaa_factor(int flags) { return (flags & CRT_RENDER_SSAA4) ? 4 : (flags & CRT_RENDER_SSAA2) ? 2 : 1; }
+#define CRT_SSAA_MAX_PIXELS (7680ull * 4320ull)
+
+// The frame's supersampling rules (CRT_E_UNSUPPORTED): the default kernel form only; no per-wave stamps, no ray buffer (it is W x H),
+// no three-frame mix; a virtual frame of at most 7680 x 4320 pixels (the traversal-stack overflow area is sized per workgroup of the
+// virtual grid: 2.3 GB per slot at that size). The multi-device dispatcher asks too, before it advances the slot rotation.
+static int refuse_ssaa(int flags)
+{
+    const int ss = ssaa_factor(flags);
+    if (ss == 1) return CRT_OK;
+    if (g.form != Form::Mega || (flags & (CRT_RENDER_STAMPS | CRT_RENDER_WRITE_RAYS | CRT_RENDER_DIAG_MIX3))) return CRT_E_UNSUPPORTED;
+    if ((unsigned long long)g.width * (unsigned long long)g.height * (unsigned long long)(ss * ss) > CRT_SSAA_MAX_PIXELS) return CRT_E_UNSUPPORTED;
+    return CRT_OK;
+}
+
 // Every CRT_E_UNSUPPORTED rule of a frame, checked before the frame changes any state. A frame the session's kernel form
 // cannot render is refused, never rendered by another kernel behind the caller's back.
 static int refuse_unsupported(int flags, uint32_t numMeshes)
@@ -338,6 +380,7 @@ static int refuse_unsupported(int flags, uint32_t numMeshes)
         if ((g.form == Form::Refill || g.form == Form::Block) && numMeshes > 64u) return CRT_E_UNSUPPORTED;
     }
     if ((flags & CRT_RENDER_FXAA) && g.groupSize <= 1 && g.nRanks > 1) return CRT_E_UNSUPPORTED;   // the filter reads across band edges
+    RCCHK(refuse_ssaa(flags));
     // the three-frame mix: a synchronous frame of one device, without the other diagnostics or FXAA
     if ((flags & CRT_RENDER_DIAG_MIX3) && (frame_is_pipelined(flags) || g.groupSize > 1 || (flags & (CRT_RENDER_STAMPS | CRT_RENDER_WRITE_RAYS | CRT_RENDER_FXAA))))
         return CRT_E_UNSUPPORTED;
@@ -527,9 +570,10 @@ int crt1_render(const CrtTraceArgs* args, const float invView[16], const float i
     if (!args || !invView || !invProj) return CRT_E_BAD_ARGUMENT;
     if (args->numMeshes > CRT_MAX_INSTANCES) return CRT_E_OUT_OF_RANGE;
     if (!g.sceneValid) return CRT_E_BAD_ARGUMENT;
+    if ((flags & CRT_RENDER_SSAA2) && (flags & CRT_RENDER_SSAA4)) return CRT_E_BAD_ARGUMENT;
     FrameCtx c;
     c.flags = flags; c.plan = plan;
-    fill_frame(c.F, args, invView, invProj);
+    fill_frame(c.F, args, invView, invProj, ssaa_factor(flags));
     if (c.F.gridBlocks == 0) return record_empty_share(plan);
     RCCHK(refuse_unsupported(flags, args->numMeshes));
     RCCHK(choose_slot(c));

@@ -1,6 +1,7 @@
 // crt_kernels.h -- the per-frame kernels of the MI355X ray-trace path (gfx950).
 //
 //   crt_trace_kernel        RayGen + Trace megakernel (kernel_main.cl:164-287), the default and dominant launch
+//   crt_trace_ssaa_kernel   the same over a k x k supersampled frame, resolved in registers (CRT_RENDER_SSAA2 / SSAA4)
 //   crt_primary_kernel /    wavefront form: one launch per bounce with ballot compaction (CRT_KERNEL=wavefront)
 //   crt_bounce_kernel
 //   crt_raygen_kernel       RayGen alone (kernel_main.cl:277-287), only for CRT_RENDER_WRITE_RAYS
@@ -324,6 +325,94 @@ void crt_trace_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out, unsig
             st[3] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 32);
         }
     }
+}
+
+// (v + v of lane ^ M) per channel, for the SSAA resolve: ds_swizzle in bit mode, and_mask 0x1F, or_mask 0, xor_mask M (M < 32)
+template <int M> __device__ __forceinline__ float xor_add(float v) { return v + __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x1F | (M << 10))); }
+template <int M> __device__ __forceinline__ v3 xor_add3(v3 v) { return mk3(xor_add<M>(v.x), xor_add<M>(v.y), xor_add<M>(v.z)); }
+
+// Supersampled Trace (CRT_RENDER_SSAA2 / SSAA4, k = F.ss): F describes the VIRTUAL frame kW x kH -- its tile grid, raygen_dir's
+// width and height -- and every lane traces virtual pixel (k x + sx, k y + sy) exactly as crt_trace_kernel traces a pixel of a
+// kW x kH frame. The k x k subsamples of output pixel (x, y) are Morton lanes 4p..4p+3 (k = 2) or 16q..16q+15 (k = 4) of one wave,
+// all active or all inactive (kW, kH are multiples of k, k divides the 8x8 tile). The epilogue resolves them in registers in a
+// fixed order -- lane ^ 1 (sx bit 0), ^ 2 (sy bit 0), ^ 4 (sx bit 1), ^ 8 (sy bit 1), then x 1/k^2 (exact) -- and the lane of
+// sub-index 0 applies the stages behind Trace at OUTPUT coordinates and stores the W x H pixel. No stamps (refused).
+// The bounce loop is crt_trace_kernel's, kept as a copy: sharing it through a function reorders that kernel's code.
+// Counted instantiations are bounded at 5 waves/SIMD (96 VGPRs), not 6: at 80 VGPRs the counted instance-tree traversal spills
+// 32-48 B per lane (as crt_trace_kernel's counted TLAS instantiations do); the others still fit 80 and run at 6.
+template <bool COUNT, bool SHADOW, bool TLAS, bool REFRACT>
+__global__ __launch_bounds__(CRT_BLOCK, COUNT ? CRT_WAVES_PER_SIMD_COUNT - 1 : CRT_WAVES_PER_SIMD)
+void crt_trace_ssaa_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out, unsigned long long* __restrict__ counters)
+{
+    __shared__ uint32_t s_stack[CRT_LDS_SLOTS * CRT_BLOCK];
+    constexpr int kParkNdl = TLAS ? CRT_TLAS_PARK : 0;
+    typedef CrtStackT<kParkNdl + (SHADOW ? 1 : 0)> Stack;
+    const Stack stack = { (crt_lds_u32_ptr)s_stack + threadIdx.x, S.stackOverflow };
+    LaneCounters lc; zero_counters(lc);
+    int px, py, costSlot = -1;
+    bool isQuadrant = false;
+    const unsigned long long tc0 = F.cost ? __builtin_amdgcn_s_memtime() : 0ull;
+    const bool active = lane_pixel(F, px, py, &costSlot, &isQuadrant);
+    if (active) {
+        PathState ps;
+        ps.o = mk3(F.camPos[0], F.camPos[1], F.camPos[2]);
+        ps.d = raygen_dir(F, px, py);
+        ps.result = mk3(0.0f, 0.0f, 0.0f);
+        ps.energy = 1.0f;
+        for (int bounce = 0; bounce < 2; ++bounce) {
+            if (COUNT) { lc.rays++; if (bounce == 0) lc.primary++; else lc.secondary++; }
+            if (SHADOW) stack.park(kParkNdl, __float_as_uint(ps.energy));
+            Closest c = closest_hit<COUNT, false, false, TLAS>(S, ps.o, ps.d, stack, lc);
+            if (SHADOW) ps.energy = __uint_as_float(stack.parked(kParkNdl));
+            float ndl = 0.0f;
+            const int cont = shade_bounce<SHADOW, REFRACT>(S, c, ps, bounce, F.lightY, F.lightZ, &ndl);
+            if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
+            if (!cont) break;
+            if (SHADOW && cont == 1) {
+                if (bounce == 0) {
+                    float shadow = 1.0f;
+                    if (ndl > 0.0f) {
+                        if (COUNT) { lc.rays++; lc.shadowRays++; }
+                        stack.park(kParkNdl, __float_as_uint(ndl));
+                        const Closest sc = closest_hit<COUNT, false, true, TLAS>(S, ps.o, neg3(mk3(0.0f, F.lightY, F.lightZ)), stack, lc);
+                        if (sc.anyHit) { shadow = 0.0f; if (COUNT) lc.shadowHits++; }
+                        ndl = __uint_as_float(stack.parked(kParkNdl));
+                    }
+                    ps.energy = specular_x(ndl, shadow);
+                } else ps.energy = ps.energy * specular_x(ndl, 1.0f);
+            }
+        }
+        // resolve: every lane of the k x k group is active here (see above), so each swizzle reads a partner of the same pixel
+        const int k = F.ss;                                   // wave-uniform: 2 or 4
+        v3 rgb = xor_add3<2>(xor_add3<1>(ps.result));
+        if (k == 4) rgb = xor_add3<8>(xor_add3<4>(rgb));
+        rgb = scale3(rgb, k == 4 ? 1.0f / 16.0f : 0.25f);
+        // the virtual pixel recomputed behind an opaque copy of the block index and lane (as in crt_trace_kernel)
+        int b2 = blockIdx.x, lane2 = (int)(threadIdx.x & 63);
+        asm volatile("" : "+s"(b2), "+v"(lane2));
+        int qx, qy;
+        (void)lane_pixel(F, qx, qy, nullptr, nullptr, b2, lane2);
+        if ((lane2 & (k * k - 1)) == 0) {                     // Morton sub-index 0: virtual pixel (k x, k y)
+            const int sh = k == 4 ? 2 : 1;
+            int w2 = F.width >> sh, h2 = F.height >> sh;       // the output frame W x H
+            asm volatile("" : "+s"(w2), "+s"(h2));
+            const int ox = qx >> sh, oy = qy >> sh;
+            if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = mk3(quantize1(rgb.x), quantize1(rgb.y), quantize1(rgb.z));
+            if (F.epilogue & CRT_EPILOGUE_POST) {
+                rgb = post_pixel(rgb, ox, oy, w2, h2);
+                if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = mk3(quantize1(rgb.x), quantize1(rgb.y), quantize1(rgb.z));
+            }
+            const size_t idx = (size_t)oy * (size_t)w2 + (size_t)ox;
+            out[idx] = make_float4(rgb.x, rgb.y, rgb.z, 1.0f);
+            if (F.packOut) F.packOut[idx] = unorm8(rgb.x) | (unorm8(rgb.y) << 8) | (unorm8(rgb.z) << 16) | 0xFF000000u;
+        }
+    }
+    if (F.cost && costSlot >= 0) {      // per-tile cost, as in crt_trace_kernel
+        unsigned long long dt = __builtin_amdgcn_s_memtime() - tc0;
+        if (isQuadrant) dt >>= 1;
+        if ((threadIdx.x & 63) == 0) atomicAdd(&F.cost[costSlot], dt > 0x0FFFFFFFull ? 0x0FFFFFFFu : (uint32_t)dt);
+    }
+    if (COUNT) flush_counters(lc, counters);
 }
 
 // ---- wavefront form of Trace: one launch per bounce with ballot compaction in between ----------------

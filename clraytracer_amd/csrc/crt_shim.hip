@@ -239,6 +239,8 @@ int crt_render(const CrtTraceArgs* args, const float invView[16], const float in
     if (M.broken) return CRT_E_BAD_ARGUMENT;                 // a failed resize left the devices at different frame sizes
     if (!args || !invView || !invProj) return CRT_E_BAD_ARGUMENT;
     if (flags & (CRT_RENDER_WRITE_RAYS | CRT_RENDER_STAMPS)) return CRT_E_UNSUPPORTED;   // single-device diagnostics
+    if ((flags & CRT_RENDER_SSAA2) && (flags & CRT_RENDER_SSAA4)) return CRT_E_BAD_ARGUMENT;
+    { Use u(0); RCCHK(refuse_ssaa(flags)); }
     // The dispatcher decides the frame slot once for every device (the devices' own rotation counters are not used in a
     // session: a device that owns no rows of a short frame, or whose submission failed, stays in step).
     RenderPlan plan;

@@ -32,7 +32,7 @@ struct FrameSlot {
     uint32_t* wfCount = nullptr; size_t wfCap = 0;                  // CRT_KERNEL=wavefront: per primary wave {continuing rays}, {offset within its XCD}, then the 8 per-XCD totals
     uint32_t* ovf = nullptr; size_t ovfWords = 0;   // traversal-stack overflow area of this slot's launches (CrtStack), one block per workgroup
     uint32_t* lists = nullptr; size_t listsCap = 0;   // feedback launch lists: order, costs, sort keys, lengths (prepare_launch_lists)
-    int orderSlots = -1; int orderKey[6] = { 0, 0, 0, 0, 0, 0 };
+    int orderSlots = -1; int orderKey[7] = { 0, 0, 0, 0, 0, 0, 0 };
     bool listsReady = false;                   // the lists for the next frame were already sorted at the end of the last one
     // CRT_RENDER_READBACK: pinned host copy of this slot's frame, queued behind the frame on the slot's stream; packBuf: the
     // frame's RGBA8 bytes, packCap pixels
@@ -186,10 +186,11 @@ int sync_all()
     return CRT_OK;
 }
 
-int owned_tile_rows()
+// ... of a frame `height` rows tall whose bands are `bandRows` rows (an SSAA frame: the virtual frame, k x the output's bands)
+int owned_tile_rows(int height, int bandRows)
 {
-    const int totalTileRows = (g.height + CRT_TILE - 1) / CRT_TILE;
-    const int tpb = g.bandRows / CRT_TILE;
+    const int totalTileRows = (height + CRT_TILE - 1) / CRT_TILE;
+    const int tpb = bandRows / CRT_TILE;
     int n = 0;
     for (int r = 0; r < totalTileRows; ++r) if (((r / tpb) % g.nRanks) == g.rank) ++n;
     return n;
@@ -205,7 +206,8 @@ void set_tile_grid(CrtFrame& F, int tileRows, int tilesX)
     F.listCap = F.slotsPerXcd;
 }
 
-void fill_frame(CrtFrame& F, const CrtTraceArgs* args, const float* invView, const float* invProj)
+// ss: k of k x k supersampling -- F is then the virtual frame kW x kH, an output band of bandRows rows is k x bandRows virtual rows
+void fill_frame(CrtFrame& F, const CrtTraceArgs* args, const float* invView, const float* invProj, int ss = 1)
 {
     memset(&F, 0, sizeof F);
     if (invView) memcpy(F.invView, invView, 64);
@@ -215,9 +217,9 @@ void fill_frame(CrtFrame& F, const CrtTraceArgs* args, const float* invView, con
         F.lightY = (float)sin((double)args->sunAngle);
         F.lightZ = (float)cos((double)args->sunAngle);
     }
-    F.width = g.width; F.height = g.height;
-    set_tile_grid(F, owned_tile_rows(), (g.width + CRT_TILE - 1) / CRT_TILE);
-    F.tileRowsPerBand = g.bandRows / CRT_TILE;
+    F.width = ss * g.width; F.height = ss * g.height; F.ss = ss;
+    set_tile_grid(F, owned_tile_rows(F.height, ss * g.bandRows), (F.width + CRT_TILE - 1) / CRT_TILE);
+    F.tileRowsPerBand = ss * g.bandRows / CRT_TILE;
     F.rank = g.rank; F.nRanks = g.nRanks;
 }
 

@@ -17,6 +17,7 @@ namespace {
     bool deviceReady = false;
     bool postProcess = true;   // upstream always runs PostProcess (Renderer.cpp:360-363)
     bool shadows = false, pipelined = false, unorm8 = false, refraction = false, fxaa = false;
+    int supersampling = 1;     // k of k x k supersampling: 1, 2 or 4 (CRT_RENDER_SSAA2 / SSAA4)
     std::vector<unsigned char> hostFrame8;
     float timeSeconds = 0.0f;
     unsigned frameIndex = 0;
@@ -51,6 +52,11 @@ void Renderer::SetPostProcess(bool enabled) { postProcess = enabled; }
 void Renderer::SetShadows(bool enabled) { shadows = enabled; }
 void Renderer::SetRefraction(bool enabled) { refraction = enabled; }
 void Renderer::SetFXAA(bool enabled) { fxaa = enabled; }
+void Renderer::SetSupersampling(int factor)
+{
+    if (factor != 1 && factor != 2 && factor != 4) { lastError = CRT_E_BAD_ARGUMENT; std::fprintf(stderr, "[Renderer] SetSupersampling(%d): factor must be 1, 2 or 4\n", factor); return; }
+    supersampling = factor;
+}
 void Renderer::SetUnorm8(bool enabled) { unorm8 = enabled; }
 void Renderer::SetPipelined(bool enabled) { pipelined = enabled; }
 void Renderer::SetTime(float seconds) { timeSeconds = seconds; }
@@ -176,7 +182,8 @@ unsigned Renderer::Render(float sunAngle)
     CrtTraceArgs args;
     args.cameraPos[0] = camera.position.x; args.cameraPos[1] = camera.position.y; args.cameraPos[2] = camera.position.z;
     args.time = timeSeconds; args.numMeshes = g_NumMeshInstances; args.sunAngle = sunAngle;
-    const int flags = (postProcess ? CRT_RENDER_POSTPROCESS : 0) | (shadows ? CRT_RENDER_SHADOWS : 0) | (refraction ? CRT_RENDER_REFRACTION : 0) | (fxaa ? CRT_RENDER_FXAA : 0) | (pipelined ? CRT_RENDER_ASYNC : 0) | (unorm8 ? CRT_RENDER_UNORM8 : 0);
+    const int flags = (postProcess ? CRT_RENDER_POSTPROCESS : 0) | (shadows ? CRT_RENDER_SHADOWS : 0) | (refraction ? CRT_RENDER_REFRACTION : 0) | (fxaa ? CRT_RENDER_FXAA : 0) | (pipelined ? CRT_RENDER_ASYNC : 0) | (unorm8 ? CRT_RENDER_UNORM8 : 0)
+                    | (supersampling == 2 ? CRT_RENDER_SSAA2 : supersampling == 4 ? CRT_RENDER_SSAA4 : 0);
     if (!check(crt_render(&args, &camera.inverseView.m[0][0], &camera.inverseProjection.m[0][0], flags), "crt_render")) return 0;
     return ++frameIndex;
 }

@@ -60,7 +60,17 @@ enum {
                                      as the first PostProcess stage (or alone, without CRT_RENDER_POSTPROCESS), reading the unmodified
                                      Trace result; semantics defined by the oracle (orc_fxaa). Whole frames only: refused while
                                      crt_set_row_bands leaves this device a share of the rows (an in-process multi-GPU session
-                                     gathers first and filters on its first device) */
+                                     gathers first and filters on its first device) */,
+    CRT_RENDER_SSAA2       = 2048, /* extension: 2x2 ordered-grid supersampling. The frame is traced as the VIRTUAL frame 2W x 2H (its
+                                     rays exactly those of a plain 2W x 2H frame with the same invView / invProj: subsample (sx, sy) of
+                                     pixel (x, y) is virtual pixel (2x + sx, 2y + sy), so samples sit at x + s/2 like upstream's
+                                     corner-sampled pixel and the image is shifted by 1/4 px against the 1-spp frame) and resolved in
+                                     the Trace kernel: sums of horizontal then vertical pairs, times 1/4. The stages behind Trace
+                                     (UNORM8, PostProcess, FXAA, read-back) see the resolved W x H frame. Counters count every subsample
+                                     ray. With CRT_RENDER_SSAA4: CRT_E_BAD_ARGUMENT. Refused (CRT_E_UNSUPPORTED): with STAMPS, WRITE_RAYS
+                                     or DIAG_MIX3, under a CRT_KERNEL form other than the default, above 7680 x 4320 virtual pixels */
+    CRT_RENDER_SSAA4       = 4096  /* extension: the same with 4x4 subsamples (virtual frame 4W x 4H, shift 3/8 px; the pair sums are
+                                     repeated: sx bit 0, sy bit 0, sx bit 1, sy bit 1, then times 1/16) */
 };
 
 /* Device work counters of the last CRT_RENDER_COUNTERS / crt_query_hits launch. Same meaning as

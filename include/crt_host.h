@@ -57,6 +57,7 @@ void crth_resize(int width, int height);                     /* Renderer::OnWind
 void crth_set_postprocess(int enabled);
 void crth_set_shadows(int enabled);                          /* Renderer::SetShadows (extension) */
 void crth_set_fxaa(int enabled);                             /* Renderer::SetFXAA (extension) */
+void crth_set_supersampling(int factor);                     /* Renderer::SetSupersampling (extension): 1, 2 or 4 */
 void crth_set_refraction(int enabled);                       /* Renderer::SetRefraction (extension) */
 void crth_set_unorm8(int enabled);                           /* Renderer::SetUnorm8 (hazard H8) */
 const unsigned char* crth_map_output_rgba8(void);            /* Renderer::MapOutputRGBA8 */

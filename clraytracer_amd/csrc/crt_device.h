@@ -67,19 +67,24 @@ typedef const crt_f32x4 __attribute__((address_space(3)))* crt_lds_f32x4_ptr;
 #define CRT_MAX_PARK 5
 #define CRT_OVF_SLOTS_MAX (CRT_STACK_DEPTH - (CRT_LDS_SLOTS - CRT_MAX_PARK))
 #define CRT_OVF_WORDS_PER_BLOCK ((size_t)CRT_OVF_SLOTS_MAX * CRT_BLOCK)
-template <int PARK>
+// SLOTS / TOP: CRT_KERNEL=ldstop's four-wave workgroups (crt_ldstop.h) keep fewer slots per wave in LDS, own their overflow block per WAVE
+// (`vblock`, the wave's virtual block number, instead of blockIdx.x) and carry the workgroup's LDS copy of the tree tops (`top`); every
+// other kernel leaves those two members unset and unused.
+template <int PARK, int SLOTS = CRT_LDS_SLOTS, bool TOP = false>
 struct CrtStackT {
-    static constexpr bool kTop = false;      // no LDS-resident tree tops (crt_ldstop.h's stack type says true)
-    static constexpr int kLds = CRT_LDS_SLOTS - PARK;
-    static_assert(PARK >= 0 && PARK <= CRT_MAX_PARK && kLds >= 1 && kLds <= CRT_STACK_DEPTH, "LDS slots");
+    static constexpr bool kTop = TOP;        // LDS-resident tree tops: Traversal::inner's third fetch path
+    static constexpr int kLds = SLOTS - PARK;
+    static_assert(PARK >= 0 && PARK <= CRT_MAX_PARK && kLds >= 1 && kLds <= CRT_STACK_DEPTH && CRT_STACK_DEPTH - kLds <= CRT_OVF_SLOTS_MAX, "LDS slots");
     crt_lds_u32_ptr lds;     // this lane's slot 0
     uint32_t* ovf;           // base of the launch's overflow area (wave-uniform)
+    crt_lds_f32x4_ptr top;   // TOP: the workgroup's copy of the tree-top table
+    uint32_t vblock;         // TOP: the wave's virtual block number (wave-uniform)
     __device__ __forceinline__ uint32_t* overflow_slot(int k) const
     {
         uint32_t lane = threadIdx.x & 63;
         asm volatile("" : "+v"(lane));      // keep the address arithmetic inside this (rarely taken) branch: hoisted out of the
                                             // traversal loop it costs two VGPRs for the whole kernel
-        return ovf + ((size_t)blockIdx.x * CRT_OVF_SLOTS_MAX + (size_t)k) * CRT_BLOCK + lane;
+        return ovf + ((size_t)(TOP ? vblock : blockIdx.x) * CRT_OVF_SLOTS_MAX + (size_t)k) * CRT_BLOCK + lane;
     }
     // The overflow test is made for the WAVE first (one compare + one scalar branch): no scene here passes kLds entries in the
     // common case, and the per-lane form costs every push and pop an exec-mask save / restore pair (the CU's scalar unit is
@@ -98,8 +103,8 @@ struct CrtStackT {
         if (kLds >= CRT_STACK_DEPTH || s < kLds) return lds[s * 64];
         return *overflow_slot(s - kLds);
     }
+    __device__ __forceinline__ crt_lds_f32x4_ptr top_record(uint32_t k) const { return top + k * 4; }
     // parked value k (0 <= k < PARK) of this lane
-    __device__ __forceinline__ crt_lds_f32x4_ptr top_record(uint32_t) const { return nullptr; }   // kTop stacks only (dead code here)
     __device__ __forceinline__ void park(int k, uint32_t v) const { lds[(kLds + k) * 64] = v; }
     __device__ __forceinline__ uint32_t parked(int k) const { return lds[(kLds + k) * 64]; }
 };
@@ -264,6 +269,14 @@ __device__ __forceinline__ v3 mat3mul(const float* __restrict__ m, v3 v)
 }
 
 struct Closest { float distance; int hitInstance; int anyHit; Triout hit; };
+// "no hit yet" (kernel_main.cl:189-190): what a ray without a candidate instance ends with, and shade_bounce's skybox case
+__device__ __forceinline__ Closest no_hit()
+{
+    Closest c;
+    c.distance = 99999.0f; c.hitInstance = 0; c.anyHit = 0;
+    c.hit.t = 0.0f; c.hit.u = 0.0f; c.hit.v = 0.0f; c.hit.tri = 0;
+    return c;
+}
 
 
 // diagnostic (ITERS builds only): true in exactly one active lane, so summing over lanes counts wave-level loop trips
@@ -631,9 +644,7 @@ __device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stac
 template <bool COUNT, bool ITERS = false, bool ANYHIT = false, bool TLAS = false, class STK = CrtStack>
 __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d, const STK& stack, LaneCounters& lc)
 {
-    Closest c;
-    c.distance = 99999.0f; c.hitInstance = 0; c.anyHit = 0;
-    c.hit.t = 0.0f; c.hit.u = 0.0f; c.hit.v = 0.0f; c.hit.tri = 0;
+    Closest c = no_hit();
     Traversal<COUNT> T; T.reset();
 
     if constexpr (TLAS) {
@@ -752,6 +763,16 @@ __device__ __forceinline__ v3 raygen_dir(const CrtFrame& F, int i, int j) { retu
 //   atmosphericLight: (0.255,0.25,0.27)*1 at bounce 0, that * 0.4 at bounce 1 (kernel_main.cl:185,269) -> from `bounce`;
 //   lightDir: the sun at bounce 0, the bounce ray's direction at bounce 1 (kernel_main.cl:181,271) -> from `bounce`.
 struct PathState { v3 o, d, result; float energy; };
+// a path at the camera (kernel_main.cl:179-185), direction `d` (raygen_dir of its pixel)
+__device__ __forceinline__ PathState camera_path(const CrtFrame& F, v3 d)
+{
+    PathState ps;
+    ps.o = mk3(F.camPos[0], F.camPos[1], F.camPos[2]);
+    ps.d = d;
+    ps.result = mk3(0.0f, 0.0f, 0.0f);
+    ps.energy = 1.0f;
+    return ps;
+}
 
 // kernel_main.cl:264: specular = ((1 - roughness) * ndl * shadow) * specularColor * ndl, x component (a splat)
 __device__ __forceinline__ float specular_x(float ndl, float shadow)

@@ -180,7 +180,14 @@ struct FrameCtx {
     bool fused = false, gather8 = false, packInKernel = false;
 };
 
-static int launch_trace_ssaa(FrameCtx& c, float4* out, bool count, bool shadow, bool refract, bool tlas);
+// Run-time bools -> template arguments: with_bools(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...), so a
+// generic lambda can name the kernel instantiation: K<decltype(A)::value, ...>.
+template <class Fn> static void with_bools(Fn&& f) { f(); }
+template <class Fn, class... Rest> static void with_bools(Fn&& f, bool b, Rest... rest)
+{
+    if (b) with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
 
 // The Trace launch(es) of one frame, by kernel form, on c.T and c.gridT. `out`: the frame the launch writes (the slot's frame,
 // or its unfiltered copy when FXAA follows). Sets c.fused: every form but wavefront applies T.epilogue (RGBA8 target /
@@ -205,68 +212,43 @@ static int launch_trace(FrameCtx& c, float4* out)
     }
     // crt_debug_last_kernel: the Trace launch(es) of this frame under the names rocprofv3 prints for them
     switch (g.form) {
-    case Form::Refill:
-    case Form::Block:                    // in-tile lane refill / block compaction (crt_refill.h); T counts blocks, not tiles
-        snprintf(g.lastKernel, sizeof g.lastKernel, "%s<%d,0>", g.form == Form::Block ? "crt_trace_block_kernel" : "crt_trace_refill_kernel", (int)count);
-        if (g.form == Form::Block) {
-            if (count) crt_trace_block_kernel<true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue);
-            else crt_trace_block_kernel<false><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue);
-        } else {
-            if (count) crt_trace_refill_kernel<true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters);
-            else crt_trace_refill_kernel<false><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters);
-        }
+    case Form::Refill:                   // in-tile lane refill / block compaction (crt_refill.h); T counts blocks, not tiles
+        snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_refill_kernel<%d,0>", (int)count);
+        with_bools([&](auto C) { crt_trace_refill_kernel<decltype(C)::value><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters); }, count);
+        break;
+    case Form::Block:
+        snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_block_kernel<%d,0>", (int)count);
+        with_bools([&](auto C) { crt_trace_block_kernel<decltype(C)::value><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue); }, count);
         break;
     case Form::LdsTop:                   // four tiles per workgroup sharing an LDS copy of the tree tops (crt_ldstop.h)
         snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_ldstop_kernel<%d>", (int)count);
-        if (count) crt_trace_ldstop_kernel<true><<<ldstop_grid(T), CRT_BLOCK * CRT_TOP_WAVES, 0, fs.stream>>>(S, T, out, g.counters);
-        else crt_trace_ldstop_kernel<false><<<ldstop_grid(T), CRT_BLOCK * CRT_TOP_WAVES, 0, fs.stream>>>(S, T, out, g.counters);
+        with_bools([&](auto C) { crt_trace_ldstop_kernel<decltype(C)::value><<<ldstop_grid(T), CRT_BLOCK * CRT_TOP_WAVES, 0, fs.stream>>>(S, T, out, g.counters); }, count);
         break;
     case Form::Wavefront: {              // bounce 0, ballot compaction, bounce 1
         c.fused = false;
         snprintf(g.lastKernel, sizeof g.lastKernel, "crt_primary_kernel<%d>+crt_wavefront_scan_kernel+crt_bounce_kernel<%d>", (int)count, (int)count);
         // per-slot state (prepare_lists sized it): queue = one 64-record range per primary wave; counts, offsets, per-XCD totals
         uint32_t* cnt = fs.wfCount; uint32_t* offs = cnt + grid; uint32_t* total = offs + grid;
-        if (count) crt_primary_kernel<true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue, cnt);
-        else crt_primary_kernel<false><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue, cnt);
-        crt_wavefront_scan_kernel<<<8, 1024, 0, fs.stream>>>(cnt, offs, total, T.slotsPerXcd);
-        // an XCD's tiles can all continue: the bounce launch has the primary launch's shape (waves past their XCD's total leave at once)
-        if (count) crt_bounce_kernel<true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue, offs, total);
-        else crt_bounce_kernel<false><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue, offs, total);
+        with_bools([&](auto C) {
+            crt_primary_kernel<decltype(C)::value><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue, cnt);
+            crt_wavefront_scan_kernel<<<8, 1024, 0, fs.stream>>>(cnt, offs, total, T.slotsPerXcd);
+            // an XCD's tiles can all continue: the bounce launch has the primary launch's shape (waves past their XCD's total leave at once)
+            crt_bounce_kernel<decltype(C)::value><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters, fs.blockQueue, offs, total);
+        }, count);
         break;
     }
-    case Form::Mega: {                   // <COUNT, STAMP, SHADOW, TLAS, REFRACT>
+    case Form::Mega: {                   // <COUNT, STAMP, SHADOW, TLAS, REFRACT>; a supersampled frame (CRT_RENDER_SSAA2 / SSAA4; c.T is the virtual frame): <COUNT, SHADOW, TLAS, REFRACT>
         const bool shadow = (c.flags & CRT_RENDER_SHADOWS) != 0, refract = (c.flags & CRT_RENDER_REFRACTION) != 0, tlas = use_tlas(S);
-        if (T.ss > 1) return launch_trace_ssaa(c, out, count, shadow, refract, tlas);   // CRT_RENDER_SSAA2 / SSAA4
-        snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_kernel<%d,0,%d,%d,%d>", (int)count, (int)shadow, (int)tlas, (int)refract);
-#define CRT_LAUNCH_TRACE3(C_, S_, T_, R_) crt_trace_kernel<C_, false, S_, T_, R_><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters)
-#define CRT_LAUNCH_TRACE2(C_, S_, T_) do { if (refract) CRT_LAUNCH_TRACE3(C_, S_, T_, true); else CRT_LAUNCH_TRACE3(C_, S_, T_, false); } while (0)
-#define CRT_LAUNCH_TRACE(C_, S_) do { if (tlas) CRT_LAUNCH_TRACE2(C_, S_, true); else CRT_LAUNCH_TRACE2(C_, S_, false); } while (0)
-        if (count) { if (shadow) CRT_LAUNCH_TRACE(true, true); else CRT_LAUNCH_TRACE(true, false); }
-        else       { if (shadow) CRT_LAUNCH_TRACE(false, true); else CRT_LAUNCH_TRACE(false, false); }
-#undef CRT_LAUNCH_TRACE
-#undef CRT_LAUNCH_TRACE2
-#undef CRT_LAUNCH_TRACE3
+        if (T.ss > 1) snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_ssaa_kernel<%d,%d,%d,%d>", (int)count, (int)shadow, (int)tlas, (int)refract);
+        else snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_kernel<%d,0,%d,%d,%d>", (int)count, (int)shadow, (int)tlas, (int)refract);
+        with_bools([&](auto C, auto Sh, auto Tl, auto R) {
+            constexpr bool kC = decltype(C)::value, kSh = decltype(Sh)::value, kTl = decltype(Tl)::value, kR = decltype(R)::value;
+            if (T.ss > 1) crt_trace_ssaa_kernel<kC, kSh, kTl, kR><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters);
+            else crt_trace_kernel<kC, false, kSh, kTl, kR><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters);
+        }, count, shadow, tlas, refract);
         break;
     }
     }
-    HIPCHK(hipGetLastError());
-    return CRT_OK;
-}
-
-// The Trace launch of a supersampled frame (the default form only; refuse_ssaa): c.T is the virtual frame. (Defined behind
-// launch_trace so that its kernels are emitted behind crt_trace_kernel's: the existing kernels keep their code addresses.)
-static int launch_trace_ssaa(FrameCtx& c, float4* out, bool count, bool shadow, bool refract, bool tlas)
-{
-    const CrtDevScene& S = c.S; const CrtFrame& T = c.T; const unsigned grid = c.gridT; FrameSlot& fs = *c.fs;
-    snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_ssaa_kernel<%d,%d,%d,%d>", (int)count, (int)shadow, (int)tlas, (int)refract);
-#define CRT_LAUNCH_SSAA3(C_, S_, T_, R_) crt_trace_ssaa_kernel<C_, S_, T_, R_><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.counters)
-#define CRT_LAUNCH_SSAA2(C_, S_, T_) do { if (refract) CRT_LAUNCH_SSAA3(C_, S_, T_, true); else CRT_LAUNCH_SSAA3(C_, S_, T_, false); } while (0)
-#define CRT_LAUNCH_SSAA(C_, S_) do { if (tlas) CRT_LAUNCH_SSAA2(C_, S_, true); else CRT_LAUNCH_SSAA2(C_, S_, false); } while (0)
-    if (count) { if (shadow) CRT_LAUNCH_SSAA(true, true); else CRT_LAUNCH_SSAA(true, false); }
-    else       { if (shadow) CRT_LAUNCH_SSAA(false, true); else CRT_LAUNCH_SSAA(false, false); }
-#undef CRT_LAUNCH_SSAA
-#undef CRT_LAUNCH_SSAA2
-#undef CRT_LAUNCH_SSAA3
     HIPCHK(hipGetLastError());
     return CRT_OK;
 }
@@ -651,8 +633,7 @@ int crt1_query_hits(const float* origins, const float* dirs, int n, uint32_t num
         if (!(d2 <= farthest2)) farthest2 = d2;      // (NaN sticks)
     }
     CrtDevScene S; fill_scene(S, numInstances, fs, beyond_cull_range(sqrt(farthest2)));
-    if (use_tlas(S)) crt_query_kernel<true><<<(unsigned)((n + CRT_BLOCK - 1) / CRT_BLOCK), CRT_BLOCK, 0, g.stream>>>(S, dO, dD, n, dH, g.counters);
-    else crt_query_kernel<false><<<(unsigned)((n + CRT_BLOCK - 1) / CRT_BLOCK), CRT_BLOCK, 0, g.stream>>>(S, dO, dD, n, dH, g.counters);
+    with_bools([&](auto Tl) { crt_query_kernel<decltype(Tl)::value><<<(unsigned)((n + CRT_BLOCK - 1) / CRT_BLOCK), CRT_BLOCK, 0, g.stream>>>(S, dO, dD, n, dH, g.counters); }, use_tlas(S));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dH, sizeof(CrtRayHit) * (size_t)n, hipMemcpyDeviceToHost, g.stream));
     unsigned long long c[CRT_NUM_COUNTERS];

@@ -1,7 +1,7 @@
 // crt_kernels.h -- the per-frame kernels of the MI355X ray-trace path (gfx950).
 //
 //   crt_trace_kernel        RayGen + Trace megakernel (kernel_main.cl:164-287), the default and dominant launch
-//   crt_trace_ssaa_kernel   the same over a k x k supersampled frame, resolved in registers (CRT_RENDER_SSAA2 / SSAA4)
+//   crt_trace_ssaa_kernel   the same body (trace_body) over a k x k supersampled frame, resolved in registers (CRT_RENDER_SSAA2 / SSAA4)
 //   crt_primary_kernel /    wavefront form: one launch per bounce with ballot compaction (CRT_KERNEL=wavefront)
 //   crt_bounce_kernel
 //   crt_raygen_kernel       RayGen alone (kernel_main.cl:277-287), only for CRT_RENDER_WRITE_RAYS
@@ -53,13 +53,14 @@ __device__ __forceinline__ void zero_counters(LaneCounters& lc)
 // tile rows left to right -- neighbouring tiles share BVH subtrees in its L2 -- while the eight XCDs
 // interleave row by row, which keeps them equally loaded when geometry is concentrated in one part
 // of the frame (a contiguous slab per XCD left most XCDs idle: ~1.2 resident waves/SIMD measured).
-// `slotOut` receives this workgroup's index into the per-tile cost array (or -1).
-__device__ __forceinline__ bool lane_pixel(const CrtFrame& F, int& px, int& py, int* slotOut = nullptr, bool* quadrantOut = nullptr, int b = blockIdx.x,
-                                           int lane = (int)(threadIdx.x & 63))
+// deal_tile is the wave-uniform part: workgroup b's list entry -- `slotOut` receives its index into the per-tile cost array (or -1),
+// `quadrant` the quadrant a quadrant wave traces (or -1) -- and its tile (column tx, tile row of the rank's band); false when the
+// workgroup has no tile.
+__device__ __forceinline__ bool deal_tile(const CrtFrame& F, int b, int& tx, int& tileRow, int& quadrant, int* slotOut)
 {
     const int xcd = b & 7;
     int slot = b >> 3;
-    int quadrant = -1;
+    quadrant = -1;
     // Feedback scheduling (crt_order_kernel): each XCD's tiles are launched heaviest-first, by the cycles the same
     // tile cost in the previous frame, and the very heaviest are traced by four waves of one 4x4 quadrant each, so
     // that no single wave's serial chain outlasts the rest of the frame. Nothing is cached or skipped -- only the
@@ -69,20 +70,31 @@ __device__ __forceinline__ bool lane_pixel(const CrtFrame& F, int& px, int& py, 
         const uint32_t e = __builtin_amdgcn_readfirstlane(F.order[xcd * F.listCap + slot]);   // wave-uniform: keep it (and what follows from it) in SGPRs
         slot = (int)(e & 0x0FFFFFFFu);
         if (e & 0x80000000u) quadrant = (int)((e >> 28) & 3u);
-        if (quadrantOut) *quadrantOut = (e & 0x80000000u) != 0;
     } else if (slot >= F.slotsPerXcd) { if (slotOut) *slotOut = -1; return false; }
     if (slotOut) *slotOut = xcd * F.slotsPerXcd + slot;
     const int round = slot / F.tilesX;
-    const int tx = slot - round * F.tilesX;
+    tx = slot - round * F.tilesX;
     const int k = round * 8 + xcd;                     // index among the tile rows this rank owns
     if (k >= F.ownedTileRows) return false;
     const int bandK = k / F.tileRowsPerBand;
-    const int tileRow = (F.rank + bandK * F.nRanks) * F.tileRowsPerBand + (k - bandK * F.tileRowsPerBand);
+    tileRow = (F.rank + bandK * F.nRanks) * F.tileRowsPerBand + (k - bandK * F.tileRowsPerBand);
+    return true;
+}
+// pixel (tx * 8 + lx, tileRow * 8 + ly) of Morton position m (0..63) in tile (tx, tileRow)
+__device__ __forceinline__ void tile_pixel(int tx, int tileRow, int m, int& px, int& py)
+{
+    px = tx * CRT_TILE + ((m & 1) | ((m >> 1) & 2) | ((m >> 2) & 4));
+    py = tileRow * CRT_TILE + (((m >> 1) & 1) | ((m >> 2) & 2) | ((m >> 3) & 4));
+}
+__device__ __forceinline__ bool lane_pixel(const CrtFrame& F, int& px, int& py, int* slotOut = nullptr, bool* quadrantOut = nullptr, int b = blockIdx.x,
+                                           int lane = (int)(threadIdx.x & 63))
+{
+    int tx, tileRow, quadrant;
+    const bool dealt = deal_tile(F, b, tx, tileRow, quadrant, slotOut);
+    if (quadrantOut) *quadrantOut = quadrant >= 0;
+    if (!dealt) return false;
     if (quadrant >= 0 && (lane >> 4) != quadrant) return false;   // Morton order: lanes 16q..16q+15 are one 4x4 quadrant
-    const int lx = (lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4);
-    const int ly = ((lane >> 1) & 1) | ((lane >> 2) & 2) | ((lane >> 3) & 4);
-    px = tx * CRT_TILE + lx;
-    py = tileRow * CRT_TILE + ly;
+    tile_pixel(tx, tileRow, lane, px, py);
     return px < F.width && py < F.height;
 }
 
@@ -222,39 +234,121 @@ __device__ __forceinline__ float quantize1(float x) { return (float)unorm8(x) / 
 #define CRT_EPILOGUE_QUANTIZE 1   // CrtFrame::epilogue bits
 #define CRT_EPILOGUE_POST 2
 
+__device__ __forceinline__ v3 quantize3(v3 c) { return mk3(quantize1(c.x), quantize1(c.y), quantize1(c.z)); }
+// the bytes of upstream's RGBA8 texture: an opaque pixel, or all four channels of a stored one
+__device__ __forceinline__ uint32_t pack_rgba8(float4 p) { return unorm8(p.x) | (unorm8(p.y) << 8) | (unorm8(p.z) << 16) | (unorm8(p.w) << 24); }
+__device__ __forceinline__ uint32_t pack_rgba8(v3 c) { return unorm8(c.x) | (unorm8(c.y) << 8) | (unorm8(c.z) << 16) | 0xFF000000u; }
+
+// The per-pixel stages that follow Trace upstream (its RGBA8 render target, PostProcess) applied to a value in registers, and the
+// store of pixel (x, y) of a width x height frame: no second and third pass over the frame (wave-uniform branches). With
+// F.packOut also the bytes of upstream's RGBA8 texture, for a read-back (what crt_pack_unorm8_kernel would make of the value
+// just stored). `always` = false: the float frame already holds the plain value (the post-pass of the refill / block forms).
+__device__ __forceinline__ void finish_pixel(const CrtFrame& F, v3 rgb, int x, int y, int width, int height, float4* __restrict__ out, bool always = true)
+{
+    if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = quantize3(rgb);
+    if (F.epilogue & CRT_EPILOGUE_POST) {
+        rgb = post_pixel(rgb, x, y, width, height);
+        if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = quantize3(rgb);
+    }
+    const size_t idx = (size_t)y * (size_t)width + (size_t)x;
+    if (always || F.epilogue != 0) out[idx] = make_float4(rgb.x, rgb.y, rgb.z, 1.0f);
+    if (F.packOut) F.packOut[idx] = pack_rgba8(rgb);
+}
+// ... as one pass over the `pixels` pixels of a block of tiles starting at tile (tx0, tileRow), at full lane occupancy, on the
+// plain values this wave stored before (workgroup-scope release / acquire: the wave reads its own stores). The refill and block
+// forms keep the stages out of their loops: seven powf per pixel inside cost the traversal its registers.
+__device__ __forceinline__ void finish_block_pixels(const CrtFrame& F, int tx0, int tileRow, uint32_t pixels, float4* __restrict__ out)
+{
+    if (F.epilogue == 0 && F.packOut == nullptr) return;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    for (uint32_t p = threadIdx.x & 63u; p < pixels; p += 64u) {
+        int qx, qy;
+        tile_pixel(tx0 + (int)(p >> 6), tileRow, (int)(p & 63u), qx, qy);
+        if (qx >= F.width || qy >= F.height) continue;
+        const float4 v = out[(size_t)qy * (size_t)F.width + (size_t)qx];
+        finish_pixel(F, mk3(v.x, v.y, v.z), qx, qy, F.width, F.height, out, false);
+    }
+}
+
+// Per-tile cost of this frame (wave-uniform value, one atomic): the cycles since `tc0` = tile_cost_start(F).
+// `halve`: the four quadrant waves of a split tile each add half their cycles: about what the tile would take as one wave
+// (a quadrant wave runs ~0.6x as long as the whole tile's), so a split tile neither sticks nor flips every frame
+__device__ __forceinline__ unsigned long long tile_cost_start(const CrtFrame& F) { return F.cost ? __builtin_amdgcn_s_memtime() : 0ull; }
+__device__ __forceinline__ void add_tile_cost(const CrtFrame& F, int costSlot, unsigned long long tc0, bool halve = false)
+{
+    if (F.cost && costSlot >= 0) {
+        unsigned long long dt = __builtin_amdgcn_s_memtime() - tc0;
+        if (halve) dt >>= 1;
+        if ((threadIdx.x & 63) == 0) atomicAdd(&F.cost[costSlot], dt > 0x0FFFFFFFull ? 0x0FFFFFFFu : (uint32_t)dt);
+    }
+}
+
+// STAMP (diagnostic build only, CRT_RENDER_STAMPS): every wave records start/end s_memrealtime (100 MHz), its s_memtime cycle
+// count, XCC/HW ids and its wave-level step counts (closest_hit's ITERS) into 8 words of a buffer nothing else reads
+// (tools/wave_timeline.py). Every lane of the wave must call write_wave_stamp.
+struct WaveStampStart { unsigned long long rt, c; };
+__device__ __forceinline__ WaveStampStart wave_stamp_start() { return { __builtin_amdgcn_s_memrealtime(), __builtin_amdgcn_s_memtime() }; }
+__device__ __forceinline__ void write_wave_stamp(unsigned long long* __restrict__ counters, const LaneCounters& lc, WaveStampStart t0, uint32_t wService = 0)
+{
+    const unsigned long long t1c = __builtin_amdgcn_s_memtime(), t1rt = __builtin_amdgcn_s_memrealtime();
+    const uint32_t wOuter = wave_sum(lc.pops), wEnter = wave_sum(lc.traversals), wDescent = wave_sum(lc.innerVisits),
+                   wLeaf = wave_sum(lc.triTests), laneVisits = wave_sum(lc.rays), wInner2 = wave_sum(lc.hits), wLeafIters = wave_sum(lc.misses);
+    if ((threadIdx.x & 63) == 0) {
+        unsigned long long* st = counters + 16 + (size_t)blockIdx.x * 8;
+        st[4] = wOuter | ((unsigned long long)wInner2 << 32); st[5] = wEnter | ((unsigned long long)wLeafIters << 32);
+        st[6] = wDescent | ((unsigned long long)wService << 32); st[7] = ((unsigned long long)wLeaf << 32) | laneVisits;
+        st[0] = t0.rt; st[1] = t1rt; st[2] = t1c - t0.c;
+        st[3] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 32);
+    }
+}
+
+// (v + v of lane ^ M) per channel, for the SSAA resolve: ds_swizzle in bit mode, and_mask 0x1F, or_mask 0, xor_mask M (M < 32)
+template <int M> __device__ __forceinline__ float xor_add(float v) { return v + __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x1F | (M << 10))); }
+template <int M> __device__ __forceinline__ v3 xor_add3(v3 v) { return mk3(xor_add<M>(v.x), xor_add<M>(v.y), xor_add<M>(v.z)); }
+
+// The pixel of lane `lane` of workgroup `b` once more, behind the traversals: the pixel coordinates are recomputed rather than
+// kept alive through both traversals (4 VGPRs that were spilled to scratch at 8 waves/SIMD): the block index goes through an
+// opaque asm so the two computations are not merged
+__device__ __forceinline__ void lane_pixel_again(const CrtFrame& F, int b, int lane, int& qx, int& qy)
+{
+    asm volatile("" : "+s"(b), "+v"(lane));
+    (void)lane_pixel(F, qx, qy, nullptr, nullptr, b, lane);
+}
+
 // kernel Trace (kernel_main.cl:164-275) with RayGen (kernel_main.cl:277-287) fused: the ray
 // direction is computed with the same arithmetic RayGen stores, so the 24.9 MB ray buffer
-// round-trip disappears. One thread per pixel, both bounces.
-// STAMP (diagnostic build only, CRT_RENDER_STAMPS): every wave records start/end s_memrealtime (100 MHz),
-// its s_memtime cycle count and XCC/HW ids into a buffer nothing else reads.
+// round-trip disappears. One thread per pixel, both bounces. The body of crt_trace_kernel, crt_trace_ssaa_kernel and
+// crt_trace_ldstop_kernel: `stack` is the wave's stack (parked slots: the instance tree's candidate list [0, 4) and the shadow
+// ray's n.l behind it), `b` its (virtual) block number, `lane` the lane.
+// STAMP: see write_wave_stamp.
 // SHADOW (CRT_RENDER_SHADOWS, an extension: upstream only threads the factor through, kernel_main.cl:256-258,264):
 // after the first hit a shadow ray (new ray origin, -lightDir) decides `shadow` in `energy *= specular`. Traced only
 // where it is observable: at bounce 0 (the energy after bounce 1 is never read) and when n.l > 0 (otherwise the
 // product is 0 whatever the shadow factor).
 // TLAS: candidates come from the instance tree instead of the linear sphere loop (scenes with many instances).
 // REFRACT (CRT_RENDER_REFRACTION, the other README TODO of upstream, oracle-defined): translucent materials transmit.
-template <bool COUNT, bool STAMP = false, bool SHADOW = false, bool TLAS = false, bool REFRACT = false>
-__global__ __launch_bounds__(CRT_BLOCK, (COUNT || STAMP) ? CRT_WAVES_PER_SIMD_COUNT : CRT_WAVES_PER_SIMD)
-void crt_trace_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out, unsigned long long* __restrict__ counters)
+// SSAA (CRT_RENDER_SSAA2 / SSAA4, k = F.ss): F describes the VIRTUAL frame kW x kH -- its tile grid, raygen_dir's width and
+// height -- and every lane traces virtual pixel (k x + sx, k y + sy) exactly as a pixel of a kW x kH frame. The k x k subsamples
+// of output pixel (x, y) are Morton lanes 4p..4p+3 (k = 2) or 16q..16q+15 (k = 4) of one wave, all active or all inactive (kW, kH
+// are multiples of k, k divides the 8x8 tile). The epilogue resolves them in registers in a fixed order -- lane ^ 1 (sx bit 0),
+// ^ 2 (sy bit 0), ^ 4 (sx bit 1), ^ 8 (sy bit 1), then x 1/k^2 (exact) -- and the lane of sub-index 0 applies the stages behind
+// Trace at OUTPUT coordinates and stores the W x H pixel.
+template <bool SHADOW, bool TLAS> using CrtTraceStack = CrtStackT<(TLAS ? CRT_TLAS_PARK : 0) + (SHADOW ? 1 : 0)>;
+template <bool COUNT, bool STAMP, bool SHADOW, bool TLAS, bool REFRACT, bool SSAA, class STK>
+__device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame& F, float4* __restrict__ out, unsigned long long* __restrict__ counters,
+                                           const STK& stack, int b, int lane)
 {
-    __shared__ uint32_t s_stack[CRT_LDS_SLOTS * CRT_BLOCK];
-    // parked LDS slots (CrtStackT): the instance tree's candidate list [0, 4) and the shadow ray's n.l behind it
     constexpr int kParkNdl = TLAS ? CRT_TLAS_PARK : 0;
-    typedef CrtStackT<kParkNdl + (SHADOW ? 1 : 0)> Stack;
-    const Stack stack = { (crt_lds_u32_ptr)s_stack + threadIdx.x, S.stackOverflow };
     LaneCounters lc; zero_counters(lc);
-    unsigned long long t0rt = 0, t0c = 0;
-    if (STAMP) { t0rt = __builtin_amdgcn_s_memrealtime(); t0c = __builtin_amdgcn_s_memtime(); }
+    WaveStampStart t0 = { 0, 0 };
+    if (STAMP) t0 = wave_stamp_start();
     int px, py, costSlot = -1;
     bool isQuadrant = false;
-    const unsigned long long tc0 = F.cost ? __builtin_amdgcn_s_memtime() : 0ull;
-    const bool active = lane_pixel(F, px, py, &costSlot, &isQuadrant);
+    const unsigned long long tc0 = tile_cost_start(F);
+    const bool active = lane_pixel(F, px, py, &costSlot, &isQuadrant, b, lane);
     if (active) {
-        PathState ps;
-        ps.o = mk3(F.camPos[0], F.camPos[1], F.camPos[2]);
-        ps.d = raygen_dir(F, px, py);
-        ps.result = mk3(0.0f, 0.0f, 0.0f);
-        ps.energy = 1.0f;
+        PathState ps = camera_path(F, raygen_dir(F, px, py));
         for (int bounce = 0; bounce < 2; ++bounce) {
             if (COUNT) { lc.rays++; if (bounce == 0) lc.primary++; else lc.secondary++; }
             // SHADOW: the path's energy waits in the parked LDS slot while the ray is traced (the one value these instantiations
@@ -283,61 +377,43 @@ void crt_trace_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out, unsig
                 } else ps.energy = ps.energy * specular_x(ndl, 1.0f);
             }
         }
-        // the pixel coordinates are recomputed here rather than kept alive through both traversals (4 VGPRs that were
-        // spilled to scratch at 8 waves/SIMD): the block index goes through an opaque asm so the two computations are
-        // not merged
-        int b2 = blockIdx.x, lane2 = (int)(threadIdx.x & 63);
-        asm volatile("" : "+s"(b2), "+v"(lane2));
         int qx, qy;
-        (void)lane_pixel(F, qx, qy, nullptr, nullptr, b2, lane2);
-        // the per-pixel stages that follow Trace upstream (its RGBA8 render target, PostProcess) applied to the value in
-        // registers: no second and third pass over the frame (wave-uniform branches)
-        v3 rgb = ps.result;
-        if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = mk3(quantize1(rgb.x), quantize1(rgb.y), quantize1(rgb.z));
-        if (F.epilogue & CRT_EPILOGUE_POST) {
+        if constexpr (SSAA) {
+            // resolve: every lane of the k x k group is active here (see above), so each swizzle reads a partner of the same pixel
+            const int k = F.ss;                                   // wave-uniform: 2 or 4
+            v3 rgb = xor_add3<2>(xor_add3<1>(ps.result));
+            if (k == 4) rgb = xor_add3<8>(xor_add3<4>(rgb));
+            rgb = scale3(rgb, k == 4 ? 1.0f / 16.0f : 0.25f);
+            lane_pixel_again(F, b, lane, qx, qy);
+            if ((lane & (k * k - 1)) == 0) {                      // Morton sub-index 0: virtual pixel (k x, k y)
+                const int sh = k == 4 ? 2 : 1;
+                int w2 = F.width >> sh, h2 = F.height >> sh;       // the output frame W x H
+                asm volatile("" : "+s"(w2), "+s"(h2));
+                finish_pixel(F, rgb, qx >> sh, qy >> sh, w2, h2, out);
+            }
+        } else {
+            lane_pixel_again(F, b, lane, qx, qy);
             // opaque copies: otherwise (float)width / (float)height of RayGen are kept alive (spilled) through both traversals
             int w2 = F.width, h2 = F.height;
             asm volatile("" : "+s"(w2), "+s"(h2));
-            rgb = post_pixel(rgb, qx, qy, w2, h2);
-            if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = mk3(quantize1(rgb.x), quantize1(rgb.y), quantize1(rgb.z));
+            finish_pixel(F, ps.result, qx, qy, w2, h2, out);
         }
-        out[(size_t)qy * (size_t)F.width + (size_t)qx] = make_float4(rgb.x, rgb.y, rgb.z, 1.0f);
-        // the bytes of upstream's RGBA8 texture, for a read-back (what crt_pack_unorm8_kernel would make of the value just stored)
-        if (F.packOut) F.packOut[(size_t)qy * (size_t)F.width + (size_t)qx] = unorm8(rgb.x) | (unorm8(rgb.y) << 8) | (unorm8(rgb.z) << 16) | 0xFF000000u;
     }
-    if (F.cost && costSlot >= 0) {      // per-tile cost of this frame (wave-uniform value, one store)
-        // the four quadrant waves of a split tile each add half their cycles: about what the tile would take as one wave
-        // (a quadrant wave runs ~0.6x as long as the whole tile's), so a split tile neither sticks nor flips every frame
-        unsigned long long dt = __builtin_amdgcn_s_memtime() - tc0;
-        if (isQuadrant) dt >>= 1;
-        if ((threadIdx.x & 63) == 0) atomicAdd(&F.cost[costSlot], dt > 0x0FFFFFFFull ? 0x0FFFFFFFu : (uint32_t)dt);
-    }
+    add_tile_cost(F, costSlot, tc0, isQuadrant);
     if (COUNT) flush_counters(lc, counters);
-    if (STAMP) {
-        const unsigned long long t1c = __builtin_amdgcn_s_memtime(), t1rt = __builtin_amdgcn_s_memrealtime();
-        const uint32_t wOuter = wave_sum(lc.pops), wEnter = wave_sum(lc.traversals), wDescent = wave_sum(lc.innerVisits),
-                       wLeaf = wave_sum(lc.triTests), laneVisits = wave_sum(lc.rays), wInner2 = wave_sum(lc.hits), wLeafIters = wave_sum(lc.misses);
-        if ((threadIdx.x & 63) == 0) {
-            unsigned long long* st = counters + 16 + (size_t)blockIdx.x * 8;
-            st[4] = wOuter | ((unsigned long long)wInner2 << 32); st[5] = wEnter | ((unsigned long long)wLeafIters << 32);
-            st[6] = wDescent; st[7] = ((unsigned long long)wLeaf << 32) | laneVisits;
-            st[0] = t0rt; st[1] = t1rt; st[2] = t1c - t0c;
-            st[3] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 32);
-        }
-    }
+    if (STAMP) write_wave_stamp(counters, lc, t0);
 }
 
-// (v + v of lane ^ M) per channel, for the SSAA resolve: ds_swizzle in bit mode, and_mask 0x1F, or_mask 0, xor_mask M (M < 32)
-template <int M> __device__ __forceinline__ float xor_add(float v) { return v + __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x1F | (M << 10))); }
-template <int M> __device__ __forceinline__ v3 xor_add3(v3 v) { return mk3(xor_add<M>(v.x), xor_add<M>(v.y), xor_add<M>(v.z)); }
+template <bool COUNT, bool STAMP = false, bool SHADOW = false, bool TLAS = false, bool REFRACT = false>
+__global__ __launch_bounds__(CRT_BLOCK, (COUNT || STAMP) ? CRT_WAVES_PER_SIMD_COUNT : CRT_WAVES_PER_SIMD)
+void crt_trace_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out, unsigned long long* __restrict__ counters)
+{
+    __shared__ uint32_t s_stack[CRT_LDS_SLOTS * CRT_BLOCK];
+    const CrtTraceStack<SHADOW, TLAS> stack = { (crt_lds_u32_ptr)s_stack + threadIdx.x, S.stackOverflow };
+    trace_body<COUNT, STAMP, SHADOW, TLAS, REFRACT, false>(S, F, out, counters, stack, blockIdx.x, (int)(threadIdx.x & 63));
+}
 
-// Supersampled Trace (CRT_RENDER_SSAA2 / SSAA4, k = F.ss): F describes the VIRTUAL frame kW x kH -- its tile grid, raygen_dir's
-// width and height -- and every lane traces virtual pixel (k x + sx, k y + sy) exactly as crt_trace_kernel traces a pixel of a
-// kW x kH frame. The k x k subsamples of output pixel (x, y) are Morton lanes 4p..4p+3 (k = 2) or 16q..16q+15 (k = 4) of one wave,
-// all active or all inactive (kW, kH are multiples of k, k divides the 8x8 tile). The epilogue resolves them in registers in a
-// fixed order -- lane ^ 1 (sx bit 0), ^ 2 (sy bit 0), ^ 4 (sx bit 1), ^ 8 (sy bit 1), then x 1/k^2 (exact) -- and the lane of
-// sub-index 0 applies the stages behind Trace at OUTPUT coordinates and stores the W x H pixel. No stamps (refused).
-// The bounce loop is crt_trace_kernel's, kept as a copy: sharing it through a function reorders that kernel's code.
+// Supersampled Trace: trace_body's SSAA case. No stamps (refused).
 // Counted instantiations are bounded at 5 waves/SIMD (96 VGPRs), not 6: at 80 VGPRs the counted instance-tree traversal spills
 // 32-48 B per lane (as crt_trace_kernel's counted TLAS instantiations do); the others still fit 80 and run at 6.
 template <bool COUNT, bool SHADOW, bool TLAS, bool REFRACT>
@@ -345,74 +421,8 @@ __global__ __launch_bounds__(CRT_BLOCK, COUNT ? CRT_WAVES_PER_SIMD_COUNT - 1 : C
 void crt_trace_ssaa_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out, unsigned long long* __restrict__ counters)
 {
     __shared__ uint32_t s_stack[CRT_LDS_SLOTS * CRT_BLOCK];
-    constexpr int kParkNdl = TLAS ? CRT_TLAS_PARK : 0;
-    typedef CrtStackT<kParkNdl + (SHADOW ? 1 : 0)> Stack;
-    const Stack stack = { (crt_lds_u32_ptr)s_stack + threadIdx.x, S.stackOverflow };
-    LaneCounters lc; zero_counters(lc);
-    int px, py, costSlot = -1;
-    bool isQuadrant = false;
-    const unsigned long long tc0 = F.cost ? __builtin_amdgcn_s_memtime() : 0ull;
-    const bool active = lane_pixel(F, px, py, &costSlot, &isQuadrant);
-    if (active) {
-        PathState ps;
-        ps.o = mk3(F.camPos[0], F.camPos[1], F.camPos[2]);
-        ps.d = raygen_dir(F, px, py);
-        ps.result = mk3(0.0f, 0.0f, 0.0f);
-        ps.energy = 1.0f;
-        for (int bounce = 0; bounce < 2; ++bounce) {
-            if (COUNT) { lc.rays++; if (bounce == 0) lc.primary++; else lc.secondary++; }
-            if (SHADOW) stack.park(kParkNdl, __float_as_uint(ps.energy));
-            Closest c = closest_hit<COUNT, false, false, TLAS>(S, ps.o, ps.d, stack, lc);
-            if (SHADOW) ps.energy = __uint_as_float(stack.parked(kParkNdl));
-            float ndl = 0.0f;
-            const int cont = shade_bounce<SHADOW, REFRACT>(S, c, ps, bounce, F.lightY, F.lightZ, &ndl);
-            if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
-            if (!cont) break;
-            if (SHADOW && cont == 1) {
-                if (bounce == 0) {
-                    float shadow = 1.0f;
-                    if (ndl > 0.0f) {
-                        if (COUNT) { lc.rays++; lc.shadowRays++; }
-                        stack.park(kParkNdl, __float_as_uint(ndl));
-                        const Closest sc = closest_hit<COUNT, false, true, TLAS>(S, ps.o, neg3(mk3(0.0f, F.lightY, F.lightZ)), stack, lc);
-                        if (sc.anyHit) { shadow = 0.0f; if (COUNT) lc.shadowHits++; }
-                        ndl = __uint_as_float(stack.parked(kParkNdl));
-                    }
-                    ps.energy = specular_x(ndl, shadow);
-                } else ps.energy = ps.energy * specular_x(ndl, 1.0f);
-            }
-        }
-        // resolve: every lane of the k x k group is active here (see above), so each swizzle reads a partner of the same pixel
-        const int k = F.ss;                                   // wave-uniform: 2 or 4
-        v3 rgb = xor_add3<2>(xor_add3<1>(ps.result));
-        if (k == 4) rgb = xor_add3<8>(xor_add3<4>(rgb));
-        rgb = scale3(rgb, k == 4 ? 1.0f / 16.0f : 0.25f);
-        // the virtual pixel recomputed behind an opaque copy of the block index and lane (as in crt_trace_kernel)
-        int b2 = blockIdx.x, lane2 = (int)(threadIdx.x & 63);
-        asm volatile("" : "+s"(b2), "+v"(lane2));
-        int qx, qy;
-        (void)lane_pixel(F, qx, qy, nullptr, nullptr, b2, lane2);
-        if ((lane2 & (k * k - 1)) == 0) {                     // Morton sub-index 0: virtual pixel (k x, k y)
-            const int sh = k == 4 ? 2 : 1;
-            int w2 = F.width >> sh, h2 = F.height >> sh;       // the output frame W x H
-            asm volatile("" : "+s"(w2), "+s"(h2));
-            const int ox = qx >> sh, oy = qy >> sh;
-            if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = mk3(quantize1(rgb.x), quantize1(rgb.y), quantize1(rgb.z));
-            if (F.epilogue & CRT_EPILOGUE_POST) {
-                rgb = post_pixel(rgb, ox, oy, w2, h2);
-                if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = mk3(quantize1(rgb.x), quantize1(rgb.y), quantize1(rgb.z));
-            }
-            const size_t idx = (size_t)oy * (size_t)w2 + (size_t)ox;
-            out[idx] = make_float4(rgb.x, rgb.y, rgb.z, 1.0f);
-            if (F.packOut) F.packOut[idx] = unorm8(rgb.x) | (unorm8(rgb.y) << 8) | (unorm8(rgb.z) << 16) | 0xFF000000u;
-        }
-    }
-    if (F.cost && costSlot >= 0) {      // per-tile cost, as in crt_trace_kernel
-        unsigned long long dt = __builtin_amdgcn_s_memtime() - tc0;
-        if (isQuadrant) dt >>= 1;
-        if ((threadIdx.x & 63) == 0) atomicAdd(&F.cost[costSlot], dt > 0x0FFFFFFFull ? 0x0FFFFFFFu : (uint32_t)dt);
-    }
-    if (COUNT) flush_counters(lc, counters);
+    const CrtTraceStack<SHADOW, TLAS> stack = { (crt_lds_u32_ptr)s_stack + threadIdx.x, S.stackOverflow };
+    trace_body<COUNT, false, SHADOW, TLAS, REFRACT, true>(S, F, out, counters, stack, blockIdx.x, (int)(threadIdx.x & 63));
 }
 
 // ---- wavefront form of Trace: one launch per bounce with ballot compaction in between ----------------
@@ -431,6 +441,20 @@ void crt_trace_ssaa_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out, 
 // tiles' bounce rays share a packet and an L2 -- and nothing is shared between frames: queue, counts and
 // offsets belong to the frame slot, so the wavefront form may keep frames in flight like the default kernel.)
 struct CrtBounceRay { float ox, oy, oz, energy, dx, dy, dz; uint32_t pixel; };   // 32 B
+__device__ __forceinline__ CrtBounceRay pack_bounce(const PathState& ps, uint32_t pixel)
+{
+    CrtBounceRay r;
+    r.ox = ps.o.x; r.oy = ps.o.y; r.oz = ps.o.z; r.energy = ps.energy;
+    r.dx = ps.d.x; r.dy = ps.d.y; r.dz = ps.d.z; r.pixel = pixel;
+    return r;
+}
+// the path a queued record continues; `result`: the pixel's partial radiance (whoever reads it first stores it in ps.result)
+__device__ __forceinline__ PathState unpack_bounce(const CrtBounceRay& r, v3 result = mk3(0.0f, 0.0f, 0.0f))
+{
+    PathState ps;
+    ps.o = mk3(r.ox, r.oy, r.oz); ps.d = mk3(r.dx, r.dy, r.dz); ps.result = result; ps.energy = r.energy;
+    return ps;
+}
 
 template <bool COUNT>
 __global__ __launch_bounds__(CRT_BLOCK, COUNT ? CRT_WAVES_PER_SIMD_COUNT : CRT_WAVES_PER_SIMD) void crt_primary_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
@@ -443,10 +467,8 @@ __global__ __launch_bounds__(CRT_BLOCK, COUNT ? CRT_WAVES_PER_SIMD_COUNT : CRT_W
     int px, py;
     const bool active = lane_pixel(F, px, py);
     bool cont = false;
-    PathState ps;
-    ps.o = mk3(0.f, 0.f, 0.f); ps.d = ps.o; ps.result = ps.o; ps.energy = 1.0f;
+    PathState ps = camera_path(F, mk3(0.f, 0.f, 0.f));
     if (active) {
-        ps.o = mk3(F.camPos[0], F.camPos[1], F.camPos[2]);
         ps.d = raygen_dir(F, px, py);
         if (COUNT) { lc.rays++; lc.primary++; }
         Closest c = closest_hit<COUNT>(S, ps.o, ps.d, stack, lc);
@@ -459,10 +481,7 @@ __global__ __launch_bounds__(CRT_BLOCK, COUNT ? CRT_WAVES_PER_SIMD_COUNT : CRT_W
     const unsigned long long m = __ballot(cont);
     if (cont) {
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        CrtBounceRay r;
-        r.ox = ps.o.x; r.oy = ps.o.y; r.oz = ps.o.z; r.energy = ps.energy;
-        r.dx = ps.d.x; r.dy = ps.d.y; r.dz = ps.d.z; r.pixel = (uint32_t)py * (uint32_t)F.width + (uint32_t)px;
-        queue[(size_t)entry * 64 + rank] = r;
+        queue[(size_t)entry * 64 + rank] = pack_bounce(ps, (uint32_t)py * (uint32_t)F.width + (uint32_t)px);
     }
     if ((threadIdx.x & 63) == 0) waveCount[entry] = (uint32_t)__popcll(m);
     if (COUNT) flush_counters(lc, counters);
@@ -507,10 +526,8 @@ __global__ __launch_bounds__(CRT_BLOCK, COUNT ? CRT_WAVES_PER_SIMD_COUNT : CRT_W
         uint32_t lo = 0, hi = (uint32_t)F.slotsPerXcd;
         while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (o[mid] <= k) lo = mid; else hi = mid; }
         const CrtBounceRay r = queue[((size_t)xcd * (uint32_t)F.slotsPerXcd + lo) * 64 + (k - o[lo])];
-        PathState ps;
-        ps.o = mk3(r.ox, r.oy, r.oz); ps.d = mk3(r.dx, r.dy, r.dz); ps.energy = r.energy;
         const float4 partial = out[r.pixel];
-        ps.result = mk3(partial.x, partial.y, partial.z);
+        PathState ps = unpack_bounce(r, mk3(partial.x, partial.y, partial.z));
         if (COUNT) { lc.rays++; lc.secondary++; }
         Closest c = closest_hit<COUNT>(S, ps.o, ps.d, stack, lc);
         const bool cont = shade_bounce(S, c, ps, 1, F.lightY, F.lightZ) != 0;
@@ -597,9 +614,9 @@ __global__ __launch_bounds__(CRT_BLOCK) void crt_fxaa_kernel(CrtFrame F, const f
     v3 o = ((lumaB < lumaMin) || (lumaB > lumaMax)) ? rgbA : rgbB;
     // the stages behind the filter, on the value in registers: PostProcess, then the store into upstream's RGBA8 target
     if (F.epilogue & CRT_EPILOGUE_POST) o = post_pixel(o, px, py, W, H);
-    if (F.epilogue & CRT_EPILOGUE_QUANTIZE) o = mk3(quantize1(o.x), quantize1(o.y), quantize1(o.z));
+    if (F.epilogue & CRT_EPILOGUE_QUANTIZE) o = quantize3(o);
     dst[(size_t)py * (size_t)W + (size_t)px] = make_float4(o.x, o.y, o.z, 1.0f);
-    if (F.packOut) F.packOut[(size_t)py * (size_t)W + (size_t)px] = unorm8(o.x) | (unorm8(o.y) << 8) | (unorm8(o.z) << 16) | 0xFF000000u;
+    if (F.packOut) F.packOut[(size_t)py * (size_t)W + (size_t)px] = pack_rgba8(o);
 }
 
 // Hazard H8: the store + load through upstream's RGBA8-UNORM render target (write_imagef / read_imagef):
@@ -616,8 +633,7 @@ __global__ void crt_pack_unorm8_kernel(const float4* __restrict__ img, uint32_t*
 {
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= pixels) return;
-    const float4 p = img[k];
-    out[k] = unorm8(p.x) | (unorm8(p.y) << 8) | (unorm8(p.z) << 16) | (unorm8(p.w) << 24);
+    out[k] = pack_rgba8(img[k]);
 }
 
 // ... of the pixels this launch owns only (a device's share of a banded frame: the other rows of `out` belong to other devices' copies)
@@ -626,8 +642,7 @@ __global__ __launch_bounds__(CRT_BLOCK) void crt_pack_owned_kernel(CrtFrame F, c
     int px, py;
     if (!lane_pixel(F, px, py)) return;
     const size_t k = (size_t)py * (size_t)F.width + (size_t)px;
-    const float4 p = img[k];
-    out[k] = unorm8(p.x) | (unorm8(p.y) << 8) | (unorm8(p.z) << 16) | (unorm8(p.w) << 24);
+    out[k] = pack_rgba8(img[k]);
 }
 // the float frame back from the bytes of the RGBA8 target: x = byte / 255 -- bit for bit what quantize1 stored (multi-device RGBA8 gather)
 __global__ void crt_unpack_unorm8_kernel(const uint32_t* __restrict__ in, float4* __restrict__ img, size_t pixels)

@@ -23,7 +23,6 @@
 #define CRT_TOP_WAVES 4                      // waves (tiles) per workgroup
 #endif
 #define CRT_TOP_LDS_SLOTS 15                 // stack slots per wave in LDS; the other 17 of upstream's 32 in the overflow area (CRT_OVF_SLOTS_MAX)
-static_assert(CRT_STACK_DEPTH - CRT_TOP_LDS_SLOTS <= CRT_OVF_SLOTS_MAX, "the overflow area is sized for 17 slots per wave");
 static_assert(CRT_TOP_PAIRS <= 0xFFFF, "table references keep the record in 16 bits");
 
 // One thread per mesh: breadth-first copy of the tree's top `perMesh` pair records into the mesh's range of the table, children that land in
@@ -53,40 +52,12 @@ __global__ void crt_build_top_kernel(const float4* __restrict__ pairs, const uin
     }
 }
 
-// The stack of one wave of a four-wave workgroup: CrtStackT's layout (slot s of lane l at lds[s * 64 + l], overflow block per WAVE, indexed by
-// the wave's virtual block number) plus the workgroup's LDS copy of the tree tops.
-struct CrtStackTop {
-    static constexpr bool kTop = true;
-    static constexpr int kLds = CRT_TOP_LDS_SLOTS;
-    crt_lds_u32_ptr lds;          // this lane's slot 0 in its wave's block
-    uint32_t* ovf;                // base of the launch's overflow area
-    crt_lds_f32x4_ptr top;        // the workgroup's copy of the table
-    uint32_t vblock;              // the wave's virtual block number (wave-uniform)
-    __device__ __forceinline__ uint32_t* overflow_slot(int k) const
-    {
-        uint32_t lane = threadIdx.x & 63;
-        asm volatile("" : "+v"(lane));
-        return ovf + ((size_t)vblock * CRT_OVF_SLOTS_MAX + (size_t)k) * CRT_BLOCK + lane;
-    }
-    __device__ __forceinline__ void write(int slot, uint32_t v) const
-    {
-        const int s = slot & (CRT_STACK_DEPTH - 1);
-        if (__ballot(s >= kLds) == 0) { lds[s * 64] = v; return; }
-        if (s < kLds) lds[s * 64] = v;
-        else *overflow_slot(s - kLds) = v;
-    }
-    __device__ __forceinline__ uint32_t read(int slot) const
-    {
-        const int s = slot & (CRT_STACK_DEPTH - 1);
-        if (__ballot(s >= kLds) == 0) return lds[s * 64];
-        if (s < kLds) return lds[s * 64];
-        return *overflow_slot(s - kLds);
-    }
-    __device__ __forceinline__ crt_lds_f32x4_ptr top_record(uint32_t k) const { return top + k * 4; }
-};
+// The stack of one wave of a four-wave workgroup: CrtStackT's layout (slot s of lane l at lds[s * 64 + l]) with 15 slots in LDS, the
+// overflow block per WAVE, indexed by the wave's virtual block number, and the workgroup's LDS copy of the tree tops.
+typedef CrtStackT<0, CRT_TOP_LDS_SLOTS, true> CrtStackTop;
 
-// RayGen + Trace, both bounces, as crt_trace_kernel<COUNT> (plain instantiation: no shadow rays / refraction / instance tree / stamps / feedback
-// lists), four tiles per workgroup. Workgroup g runs on XCD g % 8 and holds the tiles at positions (g / 8) * 4 + w of that XCD's plain list, so the
+// RayGen + Trace, both bounces: trace_body as in crt_trace_kernel<COUNT> (plain instantiation: no shadow rays / refraction / instance tree /
+// stamps / feedback lists), four tiles per workgroup. Workgroup g runs on XCD g % 8 and holds the tiles at positions (g / 8) * 4 + w of that XCD's plain list, so the
 // tile-to-XCD mapping is the default kernel's (lane_pixel with the wave's virtual block number).
 template <bool COUNT>
 __global__ __launch_bounds__(CRT_BLOCK * CRT_TOP_WAVES) void crt_trace_ldstop_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out, unsigned long long* __restrict__ counters)
@@ -99,34 +70,8 @@ __global__ __launch_bounds__(CRT_BLOCK * CRT_TOP_WAVES) void crt_trace_ldstop_ke
         for (int k = (int)threadIdx.x; k < CRT_TOP_PAIRS * 4; k += CRT_BLOCK * CRT_TOP_WAVES) s_top[k] = src[k];
     }
     __syncthreads();
-    const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);   // wave-uniform: the block number stays in SGPRs
     const int vb = (int)(((blockIdx.x >> 3) * CRT_TOP_WAVES + (uint32_t)wave) * 8u + (blockIdx.x & 7u));
     const CrtStackTop stack = { (crt_lds_u32_ptr)s_stack + wave * (CRT_TOP_LDS_SLOTS * CRT_BLOCK) + lane, S.stackOverflow, (crt_lds_f32x4_ptr)s_top, (uint32_t)vb };
-    LaneCounters lc; zero_counters(lc);
-    int px, py;
-    const bool active = lane_pixel(F, px, py, nullptr, nullptr, vb, lane);
-    if (active) {
-        PathState ps;
-        ps.o = mk3(F.camPos[0], F.camPos[1], F.camPos[2]);
-        ps.d = raygen_dir(F, px, py);
-        ps.result = mk3(0.0f, 0.0f, 0.0f);
-        ps.energy = 1.0f;
-        for (int bounce = 0; bounce < 2; ++bounce) {
-            if (COUNT) { lc.rays++; if (bounce == 0) lc.primary++; else lc.secondary++; }
-            Closest c = closest_hit<COUNT, false, false, false>(S, ps.o, ps.d, stack, lc);
-            const int cont = shade_bounce(S, c, ps, bounce, F.lightY, F.lightZ);
-            if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
-            if (!cont) break;
-        }
-        // the per-pixel stages that follow Trace upstream, on the value in registers (as crt_trace_kernel's epilogue)
-        v3 rgb = ps.result;
-        if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = mk3(quantize1(rgb.x), quantize1(rgb.y), quantize1(rgb.z));
-        if (F.epilogue & CRT_EPILOGUE_POST) {
-            rgb = post_pixel(rgb, px, py, F.width, F.height);
-            if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = mk3(quantize1(rgb.x), quantize1(rgb.y), quantize1(rgb.z));
-        }
-        out[(size_t)py * (size_t)F.width + (size_t)px] = make_float4(rgb.x, rgb.y, rgb.z, 1.0f);
-        if (F.packOut) F.packOut[(size_t)py * (size_t)F.width + (size_t)px] = unorm8(rgb.x) | (unorm8(rgb.y) << 8) | (unorm8(rgb.z) << 16) | 0xFF000000u;
-    }
-    if (COUNT) flush_counters(lc, counters);
+    trace_body<COUNT, false, false, false, false, false>(S, F, out, counters, stack, vb, lane);
 }

@@ -33,38 +33,18 @@
 #define CRT_REFILL_PIXELS (64 * CRT_REFILL_TILES)
 
 // Block of workgroup `b`: the launch's CrtFrame counts BLOCKS where the megakernel's counts tiles (tilesX = blocks per tile row,
-// slotsPerXcd, gridBlocks, the launch lists and the per-slot costs), so lane_pixel's dealing -- block b on XCD b % 8, XCD x owning
+// slotsPerXcd, gridBlocks, the launch lists and the per-slot costs), so deal_tile -- block b on XCD b % 8, XCD x owning
 // the tile rows k with k % 8 == x, heaviest first when a feedback list exists -- carries over unchanged. Wave-uniform.
 __device__ __forceinline__ bool refill_block(const CrtFrame& F, int b, int& tx0, int& tileRow, int& costSlot, int tiles = CRT_REFILL_TILES)
 {
-    const int xcd = b & 7;
-    int slot = b >> 3;
-    costSlot = -1;
-    if (F.order) {
-        if ((uint32_t)slot >= F.listLen[xcd]) return false;
-        const uint32_t e = __builtin_amdgcn_readfirstlane(F.order[xcd * F.listCap + slot]);
-        slot = (int)(e & 0x0FFFFFFFu);
-    } else if (slot >= F.slotsPerXcd) return false;
-    costSlot = xcd * F.slotsPerXcd + slot;
-    const int round = slot / F.tilesX;
-    const int bx = slot - round * F.tilesX;
-    const int k = round * 8 + xcd;
-    if (k >= F.ownedTileRows) return false;
-    const int bandK = k / F.tileRowsPerBand;
-    tileRow = (F.rank + bandK * F.nRanks) * F.tileRowsPerBand + (k - bandK * F.tileRowsPerBand);
+    int bx = 0, quadrant;
+    const bool dealt = deal_tile(F, b, bx, tileRow, quadrant, &costSlot);
     tx0 = bx * tiles;
-    return true;
+    return dealt;
 }
 
 // pixel p of the block: tile p / 64, Morton position p % 64 inside it
-__device__ __forceinline__ void refill_pixel(int tx0, int tileRow, uint32_t p, int& px, int& py)
-{
-    const int m = (int)(p & 63u);
-    const int lx = (m & 1) | ((m >> 1) & 2) | ((m >> 2) & 4);
-    const int ly = ((m >> 1) & 1) | ((m >> 2) & 2) | ((m >> 3) & 4);
-    px = (tx0 + (int)(p >> 6)) * CRT_TILE + lx;
-    py = tileRow * CRT_TILE + ly;
-}
+__device__ __forceinline__ void refill_pixel(int tx0, int tileRow, uint32_t p, int& px, int& py) { tile_pixel(tx0 + (int)(p >> 6), tileRow, (int)(p & 63u), px, py); }
 
 // STAMP (diagnostic, CRT_RENDER_STAMPS): per-wave time stamps and wave-level step counts in the megakernel's record layout
 // (tools/wave_timeline.py), plus the number of service steps in the upper half of word 6.
@@ -76,18 +56,15 @@ void crt_trace_refill_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out
     typedef CrtStackT<2> Stack;                              // parked slots: [0] pixel index within the block | bounce << 31, [1] the path's energy
     const Stack stack = { (crt_lds_u32_ptr)s_stack + threadIdx.x, S.stackOverflow };
     LaneCounters lc; zero_counters(lc);
-    unsigned long long t0rt = 0, t0c = 0;
-    if (STAMP) { t0rt = __builtin_amdgcn_s_memrealtime(); t0c = __builtin_amdgcn_s_memtime(); }
-    const unsigned long long tc0 = F.cost ? __builtin_amdgcn_s_memtime() : 0ull;
+    WaveStampStart t0 = { 0, 0 };
+    if (STAMP) t0 = wave_stamp_start();
+    const unsigned long long tc0 = tile_cost_start(F);
     int tx0 = 0, tileRow = 0, costSlot = -1;
     const bool valid = refill_block(F, blockIdx.x, tx0, tileRow, costSlot);
     if (valid) {
         uint32_t cursor = 0;                                 // next pixel of the block nobody has taken yet (wave-uniform)
-        PathState ps;
-        ps.o = mk3(0.f, 0.f, 0.f); ps.d = ps.o; ps.result = ps.o; ps.energy = 1.0f;
-        Closest c;
-        c.distance = 99999.0f; c.hitInstance = 0; c.anyHit = 0;
-        c.hit.t = 0.0f; c.hit.u = 0.0f; c.hit.v = 0.0f; c.hit.tri = 0;
+        PathState ps = camera_path(F, mk3(0.f, 0.f, 0.f));
+        Closest c = no_hit();
         Traversal<COUNT> T; T.reset();
         unsigned long long cand = 0;
         bool havePath = false;
@@ -112,8 +89,7 @@ void crt_trace_refill_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out
                     const int bounce = (int)(st >> 31);
                     ps.energy = __uint_as_float(stack.parked(1));      // (waits in LDS through the traversals, as in the megakernel's SHADOW instantiations)
                     const int cont = shade_bounce(S, c, ps, bounce, F.lightY, F.lightZ);
-                    c.distance = 99999.0f; c.hitInstance = 0; c.anyHit = 0;
-                    c.hit.t = 0.0f; c.hit.u = 0.0f; c.hit.v = 0.0f; c.hit.tri = 0;
+                    c = no_hit();
                     if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
                     if (cont != 0 && bounce == 0) {           // kernel_main.cl:187: the second iteration of the bounce loop
                         stack.park(0, st | 0x80000000u);
@@ -140,13 +116,11 @@ void crt_trace_refill_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out
                         if (px < F.width && py < F.height) {
                             havePath = true;
                             stack.park(0, p);
-                            ps.o = mk3(F.camPos[0], F.camPos[1], F.camPos[2]);
                             // opaque copies: otherwise (float)width / (float)height are hoisted out of the loop and kept alive (spilled) through it
                             int w2 = F.width, h2 = F.height;
                             asm volatile("" : "+s"(w2), "+s"(h2));
-                            ps.d = raygen_dir(F, px, py, w2, h2);
-                            ps.result = mk3(0.0f, 0.0f, 0.0f);
-                            stack.park(1, __float_as_uint(1.0f));
+                            ps = camera_path(F, raygen_dir(F, px, py, w2, h2));
+                            stack.park(1, __float_as_uint(ps.energy));
                             newRay = true;
                             if (COUNT) { lc.rays++; lc.primary++; }
                         }
@@ -164,45 +138,10 @@ void crt_trace_refill_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out
             trip_steps<COUNT, STAMP, false>(S, stack, T, c, lc, false);
         }
     }
-    // The per-pixel stages that follow Trace upstream (its RGBA8 render target, PostProcess; the megakernel's epilogue): one pass over
-    // the block's pixels at full lane occupancy, on the values this wave stored above (workgroup-scope release / acquire: the wave
-    // reads its own stores). Kept out of the loop: seven powf per pixel inside the service step cost the traversal its registers.
-    if (valid && (F.epilogue != 0 || F.packOut != nullptr)) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        for (uint32_t p = threadIdx.x & 63u; p < (uint32_t)CRT_REFILL_PIXELS; p += 64u) {
-            int qx, qy;
-            refill_pixel(tx0, tileRow, p, qx, qy);
-            if (qx >= F.width || qy >= F.height) continue;
-            const size_t idx = (size_t)qy * (size_t)F.width + (size_t)qx;
-            const float4 v = out[idx];
-            v3 rgb = mk3(v.x, v.y, v.z);
-            if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = mk3(quantize1(rgb.x), quantize1(rgb.y), quantize1(rgb.z));
-            if (F.epilogue & CRT_EPILOGUE_POST) {
-                rgb = post_pixel(rgb, qx, qy, F.width, F.height);
-                if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = mk3(quantize1(rgb.x), quantize1(rgb.y), quantize1(rgb.z));
-            }
-            if (F.epilogue != 0) out[idx] = make_float4(rgb.x, rgb.y, rgb.z, 1.0f);
-            if (F.packOut) F.packOut[idx] = unorm8(rgb.x) | (unorm8(rgb.y) << 8) | (unorm8(rgb.z) << 16) | 0xFF000000u;
-        }
-    }
-    if (F.cost && costSlot >= 0) {
-        const unsigned long long dt = __builtin_amdgcn_s_memtime() - tc0;
-        if ((threadIdx.x & 63) == 0) atomicAdd(&F.cost[costSlot], dt > 0x0FFFFFFFull ? 0x0FFFFFFFu : (uint32_t)dt);
-    }
+    if (valid) finish_block_pixels(F, tx0, tileRow, CRT_REFILL_PIXELS, out);   // upstream's per-pixel stages behind Trace
+    add_tile_cost(F, costSlot, tc0);
     if (COUNT) flush_counters(lc, counters);
-    if (STAMP) {
-        const unsigned long long t1c = __builtin_amdgcn_s_memtime(), t1rt = __builtin_amdgcn_s_memrealtime();
-        const uint32_t wOuter = wave_sum(lc.pops), wEnter = wave_sum(lc.traversals), wDescent = wave_sum(lc.innerVisits), wService = wave_sum(lc.capHits),
-                       wLeaf = wave_sum(lc.triTests), laneVisits = wave_sum(lc.rays), wInner2 = wave_sum(lc.hits), wLeafIters = wave_sum(lc.misses);
-        if ((threadIdx.x & 63) == 0) {
-            unsigned long long* st = counters + 16 + (size_t)blockIdx.x * 8;
-            st[4] = wOuter | ((unsigned long long)wInner2 << 32); st[5] = wEnter | ((unsigned long long)wLeafIters << 32);
-            st[6] = wDescent | ((unsigned long long)wService << 32); st[7] = ((unsigned long long)wLeaf << 32) | laneVisits;
-            st[0] = t0rt; st[1] = t1rt; st[2] = t1c - t0c;
-            st[3] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 32);
-        }
-    }
+    if (STAMP) write_wave_stamp(counters, lc, t0, wave_sum(lc.capHits));      // + the service steps
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -238,9 +177,9 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
     const crt_lds_u32_ptr list = (crt_lds_u32_ptr)s_stack + Stack::kLds * 64;
     const uint32_t lane = threadIdx.x & 63u;
     LaneCounters lc; zero_counters(lc);
-    unsigned long long t0rt = 0, t0c = 0;
-    if (STAMP) { t0rt = __builtin_amdgcn_s_memrealtime(); t0c = __builtin_amdgcn_s_memtime(); }
-    const unsigned long long tc0 = F.cost ? __builtin_amdgcn_s_memtime() : 0ull;
+    WaveStampStart t0 = { 0, 0 };
+    if (STAMP) t0 = wave_stamp_start();
+    const unsigned long long tc0 = tile_cost_start(F);
     int tx0 = 0, tileRow = 0, costSlot = -1;
     const bool valid = refill_block(F, blockIdx.x, tx0, tileRow, costSlot, CRT_BLOCK_TILES);
     if (valid) {
@@ -255,16 +194,13 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
             const bool inFrame = px < F.width && py < F.height;
             bool listed = false;
             if (inFrame) {
-                PathState ps;
-                ps.o = mk3(F.camPos[0], F.camPos[1], F.camPos[2]); ps.d = raygen_dir(F, px, py); ps.result = mk3(0.0f, 0.0f, 0.0f); ps.energy = 1.0f;
+                PathState ps = camera_path(F, raygen_dir(F, px, py));
                 LaneCounters none;
                 const unsigned long long cand = candidate_mask<false>(S, ps.o, ps.d, 0u, cnt, none);
                 if (cand == 0 && S.numInstances <= 64u) {
                     // no instance can be hit: closest_hit would return the initial miss (kernel_main.cl:219-224: skybox, break)
                     if (COUNT) { lc.rays++; lc.primary++; lc.misses++; lc.traversals += cnt; lc.pops += cnt; lc.innerVisits += cnt; lc.culled += cnt; }
-                    Closest c;
-                    c.distance = 99999.0f; c.hitInstance = 0; c.anyHit = 0; c.hit.t = 0.0f; c.hit.u = 0.0f; c.hit.v = 0.0f; c.hit.tri = 0;
-                    (void)shade_bounce(S, c, ps, 0, F.lightY, F.lightZ);
+                    (void)shade_bounce(S, no_hit(), ps, 0, F.lightY, F.lightZ);
                     out[(size_t)py * (size_t)F.width + (size_t)px] = make_float4(ps.result.x, ps.result.y, ps.result.z, 1.0f);
                 } else listed = true;
             }
@@ -277,8 +213,7 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
         // the megakernel; the opaque asm keeps the two computations apart)
         for (uint32_t base = 0; base < nList; base += 64u) {
             bool cont = false;
-            PathState ps;
-            ps.o = mk3(F.camPos[0], F.camPos[1], F.camPos[2]); ps.d = ps.o; ps.result = mk3(0.0f, 0.0f, 0.0f); ps.energy = 1.0f;
+            PathState ps = camera_path(F, mk3(0.f, 0.f, 0.f));
             if (base + lane < nList) {
                 {
                     int px, py;
@@ -301,10 +236,7 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
             }
             const unsigned long long m = __ballot(cont);
             if (cont) {
-                CrtBounceRay r;
-                r.ox = ps.o.x; r.oy = ps.o.y; r.oz = ps.o.z; r.energy = ps.energy;
-                r.dx = ps.d.x; r.dy = ps.d.y; r.dz = ps.d.z; r.pixel = pixel;
-                q[nQueue + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = r;
+                q[nQueue + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = pack_bounce(ps, pixel);
             }
             nQueue += (uint32_t)__popcll(m);
         }
@@ -315,11 +247,7 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
         }
         for (uint32_t base = 0; base < nQueue; base += 64u) {
             if (base + lane < nQueue) {
-                PathState ps;
-                {
-                    const CrtBounceRay r = q[base + lane];
-                    ps.o = mk3(r.ox, r.oy, r.oz); ps.d = mk3(r.dx, r.dy, r.dz); ps.energy = r.energy;
-                }
+                PathState ps = unpack_bounce(q[base + lane]);
                 if (COUNT) { lc.rays++; lc.secondary++; }
                 const Closest c = closest_hit<COUNT, STAMP>(S, ps.o, ps.d, stack, lc);
                 // the partial radiance and the pixel index are fetched behind the traversal (nothing kept alive through it)
@@ -334,41 +262,8 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
             }
         }
     }
-    // upstream's per-pixel stages behind Trace (see crt_trace_refill_kernel)
-    if (valid && (F.epilogue != 0 || F.packOut != nullptr)) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        for (uint32_t p = lane; p < (uint32_t)CRT_BLOCK_PIXELS; p += 64u) {
-            int qx, qy;
-            refill_pixel(tx0, tileRow, p, qx, qy);
-            if (qx >= F.width || qy >= F.height) continue;
-            const size_t idx = (size_t)qy * (size_t)F.width + (size_t)qx;
-            const float4 v = out[idx];
-            v3 rgb = mk3(v.x, v.y, v.z);
-            if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = mk3(quantize1(rgb.x), quantize1(rgb.y), quantize1(rgb.z));
-            if (F.epilogue & CRT_EPILOGUE_POST) {
-                rgb = post_pixel(rgb, qx, qy, F.width, F.height);
-                if (F.epilogue & CRT_EPILOGUE_QUANTIZE) rgb = mk3(quantize1(rgb.x), quantize1(rgb.y), quantize1(rgb.z));
-            }
-            if (F.epilogue != 0) out[idx] = make_float4(rgb.x, rgb.y, rgb.z, 1.0f);
-            if (F.packOut) F.packOut[idx] = unorm8(rgb.x) | (unorm8(rgb.y) << 8) | (unorm8(rgb.z) << 16) | 0xFF000000u;
-        }
-    }
-    if (F.cost && costSlot >= 0) {
-        const unsigned long long dt = __builtin_amdgcn_s_memtime() - tc0;
-        if ((threadIdx.x & 63) == 0) atomicAdd(&F.cost[costSlot], dt > 0x0FFFFFFFull ? 0x0FFFFFFFu : (uint32_t)dt);
-    }
+    if (valid) finish_block_pixels(F, tx0, tileRow, CRT_BLOCK_PIXELS, out);   // upstream's per-pixel stages behind Trace
+    add_tile_cost(F, costSlot, tc0);
     if (COUNT) flush_counters(lc, counters);
-    if (STAMP) {
-        const unsigned long long t1c = __builtin_amdgcn_s_memtime(), t1rt = __builtin_amdgcn_s_memrealtime();
-        const uint32_t wOuter = wave_sum(lc.pops), wEnter = wave_sum(lc.traversals), wDescent = wave_sum(lc.innerVisits),
-                       wLeaf = wave_sum(lc.triTests), laneVisits = wave_sum(lc.rays), wInner2 = wave_sum(lc.hits), wLeafIters = wave_sum(lc.misses);
-        if ((threadIdx.x & 63) == 0) {
-            unsigned long long* st = counters + 16 + (size_t)blockIdx.x * 8;
-            st[4] = wOuter | ((unsigned long long)wInner2 << 32); st[5] = wEnter | ((unsigned long long)wLeafIters << 32);
-            st[6] = wDescent; st[7] = ((unsigned long long)wLeaf << 32) | laneVisits;
-            st[0] = t0rt; st[1] = t1rt; st[2] = t1c - t0c;
-            st[3] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 32);
-        }
-    }
+    if (STAMP) write_wave_stamp(counters, lc, t0);
 }

@@ -54,6 +54,17 @@ HITRECORD_DTYPE = np.dtype([("normal", "<f4", 3), ("uv", "<f4", 2), ("distance",
 assert TRI_DTYPE.itemsize == 80 and NODE_DTYPE.itemsize == 32 and MATERIAL_DTYPE.itemsize == 16
 assert TEXTURE_DTYPE.itemsize == 16 and INSTANCE_DTYPE.itemsize == 80 and RAYHIT_DTYPE.itemsize == 20
 assert HITRECORD_DTYPE.itemsize == 32
+# the first-hit planes of a CRT_RENDER_GBUFFER frame (include/crt_api.h) and one pixel of all three (CrtGBufferPixel, crt_pick_pixel)
+CRT_RENDER_GBUFFER = 8192        # the crt_render flag
+CRT_GBUFFER_GEOMETRY, CRT_GBUFFER_IDS, CRT_GBUFFER_ALBEDO = 0, 1, 2
+GBUFFER_GEOMETRY_DTYPE = np.dtype([("normal", "<f4", 3), ("t", "<f4")])
+GBUFFER_IDS_DTYPE = np.dtype([("instance", "<i4"), ("tri", "<u4"), ("u", "<f4"), ("v", "<f4")])
+GBUFFER_ALBEDO_DTYPE = np.dtype("<u4")
+GBUFFER_PLANE_DTYPES = {"geometry": (CRT_GBUFFER_GEOMETRY, GBUFFER_GEOMETRY_DTYPE), "ids": (CRT_GBUFFER_IDS, GBUFFER_IDS_DTYPE),
+                        "albedo": (CRT_GBUFFER_ALBEDO, GBUFFER_ALBEDO_DTYPE)}
+GBUFFER_PIXEL_DTYPE = np.dtype([("normal", "<f4", 3), ("t", "<f4"), ("instance", "<i4"), ("tri", "<u4"), ("u", "<f4"), ("v", "<f4"),
+                                ("albedo", "<u4")])
+assert GBUFFER_GEOMETRY_DTYPE.itemsize == 16 and GBUFFER_IDS_DTYPE.itemsize == 16 and GBUFFER_PIXEL_DTYPE.itemsize == 36
 
 _f = C.c_float
 _fp = C.POINTER(C.c_float)
@@ -102,6 +113,9 @@ HIP_API = {
     "crt_map_host_frame_back": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "crt_read_rays": (C.c_int, [_vp, _sz]),
     "crt_output_device_ptr": (_vp, []),
+    "crt_read_gbuffer": (C.c_int, [C.c_int, _vp, _sz]),
+    "crt_gbuffer_device_ptr": (_vp, [C.c_int]),
+    "crt_pick_pixel": (C.c_int, [C.c_int, C.c_int, _vp]),
     "crt_owned_rows": (C.c_int, []),
     "crt_last_kernel_ms": (C.c_float, [C.c_int]),
     "crt_frame_time_stats": (C.c_int, [C.POINTER(CrtFrameStats), C.c_int]),
@@ -151,6 +165,9 @@ HOST_API = {
     "crth_set_refraction": (None, [C.c_int]),
     "crth_set_fxaa": (None, [C.c_int]),
     "crth_set_supersampling": (None, [C.c_int]),
+    "crth_set_gbuffer": (None, [C.c_int]),
+    "crth_map_gbuffer": (_vp, [C.c_int]),
+    "crth_pick_pixel": (C.c_int, [C.c_int, C.c_int, _vp]),
     "crth_set_unorm8": (None, [C.c_int]),
     "crth_map_output_rgba8": (_vp, []),
     "crth_set_pipelined": (None, [C.c_int]),

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/crt_types.h"
 
 #define CRT_LEAF_BIT 0x80000000u
@@ -170,6 +171,20 @@ struct CrtFrame {
     int ss;                   // crt_trace_ssaa_kernel: k of k x k supersampling (CRT_RENDER_SSAA2/4), 1 otherwise. It sits in the padding before
                               // packOut, so the struct's size -- and with it the offsets of every kernel argument behind F -- is unchanged
     uint32_t* packOut;        // with CRT_EPILOGUE_QUANTIZE: also store the pixel's RGBA8 bytes here (the frame a read-back delivers); or null
+};
+
+// The first-hit planes of a CRT_RENDER_GBUFFER frame (crt_trace_gbuffer_kernel's own argument: CrtFrame keeps its size, see `ss`),
+// W x H each, row-major like the frame, back to back in one allocation (layouts in include/crt_api.h):
+//   geometry  float4 {normal.xyz, t}                          at planes
+//   ids       uint4 {instance, triIndex, u bits, v bits}      at planes + 16 W H
+//   albedo    uint32 0xFF000000 | b << 16 | g << 8 | r        at planes + 32 W H
+// One pointer, not three: the Trace kernels keep their arguments alive through both traversals and already spill SGPRs into the
+// lanes of a VGPR; every further argument is two more lanes.
+struct CrtGBuffer {
+    char* __restrict__ planes;
+    __host__ __device__ char* geometry() const { return planes; }
+    __host__ __device__ char* ids(size_t pixels) const { return planes + 16 * pixels; }
+    __host__ __device__ char* albedo(size_t pixels) const { return planes + 32 * pixels; }
 };
 
 struct v3 { float x, y, z; };
@@ -788,12 +803,18 @@ __device__ __forceinline__ float specular_x(float ndl, float shadow)
 // 1.5; total internal reflection keeps the reflection), 0.01 behind the surface, with (1 - opacity) of the energy.
 // Returns 0: path ended (miss -> skybox); 1: continues with the reflected ray; 2: continues with the transmitted ray
 // (energy already applied, no shadow ray wanted).
-template <bool DEFER_ENERGY = false, bool REFRACT = false>
+// SINK (CRT_RENDER_GBUFFER: GBufferSink, crt_kernels.h; NoSink: nothing): at bounce 0 `sink` is handed what the primary ray found
+// where it is in registers anyway -- sink->miss(c) before the skybox lookup, sink->hit(c, record.normal, the bytes of record.color)
+// (kernel_main.cl:236,245) behind the texture fetch -- so that nothing of it has to stay alive through the second traversal.
+struct NoSink { };
+template <bool DEFER_ENERGY = false, bool REFRACT = false, class SINK = NoSink>
 __device__ __forceinline__ int shade_bounce(const CrtDevScene& S, const Closest& c, PathState& ps, int bounce, float lightY, float lightZ,
-                                            float* ndlOut = nullptr)
+                                            float* ndlOut = nullptr, const SINK* sink = nullptr)
 {
+    constexpr bool kSink = !std::is_same<SINK, NoSink>::value;
     const float UcharToFloat01 = 1.0f / 255.0f;
     if (c.distance > 99998.0f) {
+        if constexpr (kSink) { if (bounce == 0) sink->miss(c); }
         // textures[2] for every lane: a scalar load (constant address space, see crt_const_f32x4_ptr)
         const crt_f32x4 skyHdr = ((crt_const_f32x4_ptr)S.textures)[2];
         int idx = clamp_texel(sample_skybox(ps.d, __float_as_int(skyHdr.x), __float_as_int(skyHdr.y)), S.numTexels);
@@ -836,6 +857,7 @@ __device__ __forceinline__ int shade_bounce(const CrtDevScene& S, const Closest&
     const uint32_t cg = ((((a >> 8) & 0xffu) * ((px >> 8) & 0xffu)) >> 8) & 0xffu;
     const uint32_t cb = ((((a >> 16) & 0xffu) * ((px >> 16) & 0xffu)) >> 8) & 0xffu;
     const v3 color = scale3(mk3((float)cr, (float)cg, (float)cb), UcharToFloat01);
+    if constexpr (kSink) { if (bounce == 0) sink->hit(c, normal, 0xFF000000u | (cb << 16) | (cg << 8) | cr); }
     const v3 point = add3(mo, scale3(md, c.hit.t));
 
 

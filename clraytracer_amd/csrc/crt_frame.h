@@ -180,6 +180,11 @@ struct FrameCtx {
     bool fused = false, gather8 = false, packInKernel = false;
 };
 
+// CRT_RENDER_GBUFFER: bytes per pixel of plane `plane` (CRT_GBUFFER_*; 0: no such plane), and the planes of a slot that holds them
+#define CRT_GBUFFER_PIXEL_BYTES 36
+static size_t gbuffer_plane_pixel_bytes(int plane) { return plane == CRT_GBUFFER_GEOMETRY || plane == CRT_GBUFFER_IDS ? 16 : plane == CRT_GBUFFER_ALBEDO ? 4 : 0; }
+static CrtGBuffer slot_gbuffer(const FrameSlot& fs) { CrtGBuffer gb; gb.planes = fs.gbuf; return gb; }
+
 // Run-time bools -> template arguments: with_bools(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...), so a
 // generic lambda can name the kernel instantiation: K<decltype(A)::value, ...>.
 template <class Fn> static void with_bools(Fn&& f) { f(); }
@@ -239,6 +244,14 @@ static int launch_trace(FrameCtx& c, float4* out)
     }
     case Form::Mega: {                   // <COUNT, STAMP, SHADOW, TLAS, REFRACT>; a supersampled frame (CRT_RENDER_SSAA2 / SSAA4; c.T is the virtual frame): <COUNT, SHADOW, TLAS, REFRACT>
         const bool shadow = (c.flags & CRT_RENDER_SHADOWS) != 0, refract = (c.flags & CRT_RENDER_REFRACTION) != 0, tlas = use_tlas(S);
+        if (c.flags & CRT_RENDER_GBUFFER) {   // <SHADOW, TLAS, REFRACT> (never counted or supersampled: refuse_gbuffer), the slot's planes as its own argument
+            const CrtGBuffer gb = slot_gbuffer(fs);
+            snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_gbuffer_kernel<%d,%d,%d>", (int)shadow, (int)tlas, (int)refract);
+            with_bools([&](auto Sh, auto Tl, auto R) {
+                crt_trace_gbuffer_kernel<decltype(Sh)::value, decltype(Tl)::value, decltype(R)::value><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, gb);
+            }, shadow, tlas, refract);
+            break;
+        }
         if (T.ss > 1) snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_ssaa_kernel<%d,%d,%d,%d>", (int)count, (int)shadow, (int)tlas, (int)refract);
         else snprintf(g.lastKernel, sizeof g.lastKernel, "crt_trace_kernel<%d,0,%d,%d,%d>", (int)count, (int)shadow, (int)tlas, (int)refract);
         with_bools([&](auto C, auto Sh, auto Tl, auto R) {
@@ -347,6 +360,18 @@ static int refuse_ssaa(int flags)
     return CRT_OK;
 }
 
+// The rules of a frame with the first-hit planes (CRT_RENDER_GBUFFER, CRT_E_UNSUPPORTED): the default kernel form on one device; no
+// supersampling (the planes hold one primary ray per pixel), no per-wave stamps, no three-frame mix, no counters (which keeps the
+// kernel at 8 instantiations instead of 16); fewer than 2^28 pixels (GBufferSink addresses a plane with 32-bit byte offsets).
+static int refuse_gbuffer(int flags)
+{
+    if (!(flags & CRT_RENDER_GBUFFER)) return CRT_OK;
+    if ((unsigned long long)g.width * (unsigned long long)g.height >= (1ull << 28)) return CRT_E_UNSUPPORTED;
+    if (g.form != Form::Mega || g.groupSize > 1) return CRT_E_UNSUPPORTED;
+    if (flags & (CRT_RENDER_SSAA2 | CRT_RENDER_SSAA4 | CRT_RENDER_STAMPS | CRT_RENDER_DIAG_MIX3 | CRT_RENDER_COUNTERS)) return CRT_E_UNSUPPORTED;
+    return CRT_OK;
+}
+
 // Every CRT_E_UNSUPPORTED rule of a frame, checked before the frame changes any state. A frame the session's kernel form
 // cannot render is refused, never rendered by another kernel behind the caller's back.
 static int refuse_unsupported(int flags, uint32_t numMeshes)
@@ -363,6 +388,7 @@ static int refuse_unsupported(int flags, uint32_t numMeshes)
     }
     if ((flags & CRT_RENDER_FXAA) && g.groupSize <= 1 && g.nRanks > 1) return CRT_E_UNSUPPORTED;   // the filter reads across band edges
     RCCHK(refuse_ssaa(flags));
+    RCCHK(refuse_gbuffer(flags));
     // the three-frame mix: a synchronous frame of one device, without the other diagnostics or FXAA
     if ((flags & CRT_RENDER_DIAG_MIX3) && (frame_is_pipelined(flags) || g.groupSize > 1 || (flags & (CRT_RENDER_STAMPS | CRT_RENDER_WRITE_RAYS | CRT_RENDER_FXAA))))
         return CRT_E_UNSUPPORTED;
@@ -439,6 +465,7 @@ static int launch_passes(FrameCtx& c)
     const bool fxaaLocal = fxaa && g.groupSize <= 1;
     const size_t framePixels = (size_t)g.width * (size_t)g.height;
     if (fxaa && !is_secondary()) RCCHK(grow(fs.aux, fs.auxPixels, framePixels, fs.stream));
+    if (c.flags & CRT_RENDER_GBUFFER) RCCHK(grow(fs.gbuf, fs.gbufBytes, framePixels * CRT_GBUFFER_PIXEL_BYTES, fs.stream));
     if (!fxaa) F.epilogue = (unorm ? CRT_EPILOGUE_QUANTIZE : 0u) | (post ? CRT_EPILOGUE_POST : 0u);
     else if (fxaaLocal) F.epilogue = unorm ? CRT_EPILOGUE_QUANTIZE : 0u;
     // the kernel that stores the final pixel stores its four bytes too: for a read-back of the RGBA8 frame on one device (a
@@ -505,6 +532,7 @@ static int finish_frame(const FrameCtx& c)
     FrameSlot& fs = *c.fs; EventSet& es = *c.es;
     fs.frameIs8 = c.gather8;
     g.cur = c.slot;
+    if (c.flags & CRT_RENDER_GBUFFER) g.gbufSlot = c.slot;
     es.pending = true; es.flags = c.flags; es.seq = ++g.frameSeq; fs.frames++;
     if (c.T.order != nullptr && !(c.flags & CRT_RENDER_DIAG_MIX3)) {
         // did the view change since the last sorted frame? (camera matrices and position, instance tables)
@@ -704,6 +732,42 @@ int crt1_read_rays(float* dst, size_t floats)
     if (!dst || floats != (size_t)g.width * (size_t)g.height * 3) return CRT_E_BAD_ARGUMENT;
     RCCHK(sync_all());
     HIPCHK(hipMemcpy(dst, g.rays, floats * sizeof(float), hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
+// The planes of the most recently submitted CRT_RENDER_GBUFFER frame (its slot keeps them until its next G-buffer frame, a resize or
+// the shutdown; frames without the flag leave them alone).
+static char* gbuffer_plane(int plane)
+{
+    if (g.gbufSlot < 0 || !g.slot[g.gbufSlot].gbuf || gbuffer_plane_pixel_bytes(plane) == 0) return nullptr;
+    const CrtGBuffer gb = slot_gbuffer(g.slot[g.gbufSlot]);
+    const size_t pixels = (size_t)g.width * (size_t)g.height;
+    return plane == CRT_GBUFFER_GEOMETRY ? gb.geometry() : plane == CRT_GBUFFER_IDS ? gb.ids(pixels) : gb.albedo(pixels);
+}
+
+int crt1_read_gbuffer(int plane, void* dst, size_t bytes)
+{
+    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
+    const char* src = gbuffer_plane(plane);
+    if (!dst || !src || bytes != (size_t)g.width * (size_t)g.height * gbuffer_plane_pixel_bytes(plane)) return CRT_E_BAD_ARGUMENT;
+    RCCHK(sync_all());
+    HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
+void* crt1_gbuffer_device_ptr(int plane) { return g.initialized ? (void*)gbuffer_plane(plane) : nullptr; }
+
+// one pixel of the three planes: three small copies (16 + 16 + 4 B), no frame read
+int crt1_pick_pixel(int x, int y, CrtGBufferPixel* out)
+{
+    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
+    if (!out || !gbuffer_plane(CRT_GBUFFER_GEOMETRY)) return CRT_E_BAD_ARGUMENT;
+    if (x < 0 || y < 0 || x >= g.width || y >= g.height) return CRT_E_OUT_OF_RANGE;
+    RCCHK(sync_all());
+    const size_t idx = (size_t)y * (size_t)g.width + (size_t)x;
+    HIPCHK(hipMemcpy(out->normal, gbuffer_plane(CRT_GBUFFER_GEOMETRY) + idx * 16, 16, hipMemcpyDeviceToHost));   // normal[3], t
+    HIPCHK(hipMemcpy(&out->instance, gbuffer_plane(CRT_GBUFFER_IDS) + idx * 16, 16, hipMemcpyDeviceToHost));      // instance, triIndex, u, v
+    HIPCHK(hipMemcpy(&out->albedo, gbuffer_plane(CRT_GBUFFER_ALBEDO) + idx * 4, 4, hipMemcpyDeviceToHost));
     return CRT_OK;
 }
 

@@ -2,6 +2,7 @@
 //
 //   crt_trace_kernel        RayGen + Trace megakernel (kernel_main.cl:164-287), the default and dominant launch
 //   crt_trace_ssaa_kernel   the same body (trace_body) over a k x k supersampled frame, resolved in registers (CRT_RENDER_SSAA2 / SSAA4)
+//   crt_trace_gbuffer_kernel  the same body, also storing the first hit's normal, distance, ids and albedo planes (CRT_RENDER_GBUFFER)
 //   crt_primary_kernel /    wavefront form: one launch per bounce with ballot compaction (CRT_KERNEL=wavefront)
 //   crt_bounce_kernel
 //   crt_raygen_kernel       RayGen alone (kernel_main.cl:277-287), only for CRT_RENDER_WRITE_RAYS
@@ -334,11 +335,49 @@ __device__ __forceinline__ void lane_pixel_again(const CrtFrame& F, int b, int l
 // are multiples of k, k divides the 8x8 tile). The epilogue resolves them in registers in a fixed order -- lane ^ 1 (sx bit 0),
 // ^ 2 (sy bit 0), ^ 4 (sx bit 1), ^ 8 (sy bit 1), then x 1/k^2 (exact) -- and the lane of sub-index 0 applies the stages behind
 // Trace at OUTPUT coordinates and stores the W x H pixel.
+// GBUFFER (CRT_RENDER_GBUFFER): the lane also stores its pixel of the three first-hit planes `gb` (include/crt_api.h) from inside the
+// bounce-0 shading (shade_bounce's SINK), where normal, albedo and the hit record are in registers anyway: nothing is carried
+// through the second traversal, and the pixel's coordinates are recomputed as in the epilogue. ids and t are what crt_query_kernel
+// stores for the ray; a hit that upstream shades as sky (t > InfMinusOne, kernel_main.cl:219) has the normal and albedo of a miss.
+struct GBufferSink {
+    const CrtGBuffer* gb; const CrtFrame* F; int b, lane;
+    // byte offset of the lane's pixel in the albedo plane (x 4 in the other two): 32 bits (a frame of fewer than 2^28 pixels,
+    // refuse_gbuffer), so each store is a scalar plane base plus one VGPR of offset -- no 64-bit address per plane in registers
+    __device__ __forceinline__ uint32_t pixel_offset() const
+    {
+        int gx, gy;
+        lane_pixel_again(*F, b, lane, gx, gy);
+        return ((uint32_t)gy * (uint32_t)F->width + (uint32_t)gx) << 2;
+    }
+    template <class T> static __device__ __forceinline__ void store(char* plane, uint32_t byteOffset, T v) { *reinterpret_cast<T*>(plane + byteOffset) = v; }
+    __device__ __forceinline__ size_t pixels() const { return (size_t)((uint32_t)F->width * (uint32_t)F->height); }   // wave-uniform
+    __device__ __forceinline__ void hit(const Closest& c, v3 normal, uint32_t albedo) const
+    {
+        const uint32_t off = pixel_offset();
+        store(gb->geometry(), off << 2, make_float4(normal.x, normal.y, normal.z, c.hit.t));
+        store(gb->ids(pixels()), off << 2, make_uint4((uint32_t)c.hitInstance, c.hit.tri, __float_as_uint(c.hit.u), __float_as_uint(c.hit.v)));
+        store(gb->albedo(pixels()), off, albedo);
+    }
+    __device__ __forceinline__ void miss(const Closest& c) const
+    {
+        const uint32_t off = pixel_offset();
+        // Closest::anyHit without keeping that register alive through the traversal: a hit's t is below the distance the ray
+        // started with (intersect_triangle: t < out.t), and Closest::distance is that t
+        const bool anyHit = c.distance < no_hit().distance;
+        store(gb->geometry(), off << 2, make_float4(0.0f, 0.0f, 0.0f, c.distance));
+        store(gb->ids(pixels()), off << 2, anyHit ? make_uint4((uint32_t)c.hitInstance, c.hit.tri, __float_as_uint(c.hit.u), __float_as_uint(c.hit.v)) : make_uint4(0xFFFFFFFFu, 0u, 0u, 0u));
+        store(gb->albedo(pixels()), off, 0u);
+    }
+};
+#define CRT_TRACE_PLAIN 0     // trace_body's CASE
+#define CRT_TRACE_SSAA 1
+#define CRT_TRACE_GBUFFER 2
 template <bool SHADOW, bool TLAS> using CrtTraceStack = CrtStackT<(TLAS ? CRT_TLAS_PARK : 0) + (SHADOW ? 1 : 0)>;
-template <bool COUNT, bool STAMP, bool SHADOW, bool TLAS, bool REFRACT, bool SSAA, class STK>
+template <bool COUNT, bool STAMP, bool SHADOW, bool TLAS, bool REFRACT, int CASE, class STK>
 __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame& F, float4* __restrict__ out, unsigned long long* __restrict__ counters,
-                                           const STK& stack, int b, int lane)
+                                           const STK& stack, int b, int lane, const CrtGBuffer* gb = nullptr)
 {
+    constexpr bool SSAA = CASE == CRT_TRACE_SSAA, GBUFFER = CASE == CRT_TRACE_GBUFFER;
     constexpr int kParkNdl = TLAS ? CRT_TLAS_PARK : 0;
     LaneCounters lc; zero_counters(lc);
     WaveStampStart t0 = { 0, 0 };
@@ -353,11 +392,17 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
             if (COUNT) { lc.rays++; if (bounce == 0) lc.primary++; else lc.secondary++; }
             // SHADOW: the path's energy waits in the parked LDS slot while the ray is traced (the one value these instantiations
             // would otherwise spill to scratch); the shadow ray's n.l uses the same slot later, when the energy is dead
-            if (SHADOW) stack.park(kParkNdl, __float_as_uint(ps.energy));
+            // (GBUFFER: the same -- the plane stores' addresses take the register the plain kernel keeps the energy in)
+            if (SHADOW || GBUFFER) stack.park(kParkNdl, __float_as_uint(ps.energy));
             Closest c = closest_hit<COUNT, STAMP, false, TLAS>(S, ps.o, ps.d, stack, lc);
-            if (SHADOW) ps.energy = __uint_as_float(stack.parked(kParkNdl));
+            if (SHADOW || GBUFFER) ps.energy = __uint_as_float(stack.parked(kParkNdl));
             float ndl = 0.0f;
-            const int cont = shade_bounce<SHADOW, REFRACT>(S, c, ps, bounce, F.lightY, F.lightZ, &ndl);
+            int cont;
+            if constexpr (!GBUFFER) cont = shade_bounce<SHADOW, REFRACT>(S, c, ps, bounce, F.lightY, F.lightZ, &ndl);
+            else {
+                const GBufferSink sink = { gb, &F, b, lane };
+                cont = shade_bounce<SHADOW, REFRACT, GBufferSink>(S, c, ps, bounce, F.lightY, F.lightZ, &ndl, &sink);
+            }
             if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
             if (!cont) break;
             if (SHADOW && cont == 1) {
@@ -410,7 +455,7 @@ void crt_trace_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out, unsig
 {
     __shared__ uint32_t s_stack[CRT_LDS_SLOTS * CRT_BLOCK];
     const CrtTraceStack<SHADOW, TLAS> stack = { (crt_lds_u32_ptr)s_stack + threadIdx.x, S.stackOverflow };
-    trace_body<COUNT, STAMP, SHADOW, TLAS, REFRACT, false>(S, F, out, counters, stack, blockIdx.x, (int)(threadIdx.x & 63));
+    trace_body<COUNT, STAMP, SHADOW, TLAS, REFRACT, CRT_TRACE_PLAIN>(S, F, out, counters, stack, blockIdx.x, (int)(threadIdx.x & 63));
 }
 
 // Supersampled Trace: trace_body's SSAA case. No stamps (refused).
@@ -422,7 +467,21 @@ void crt_trace_ssaa_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out, 
 {
     __shared__ uint32_t s_stack[CRT_LDS_SLOTS * CRT_BLOCK];
     const CrtTraceStack<SHADOW, TLAS> stack = { (crt_lds_u32_ptr)s_stack + threadIdx.x, S.stackOverflow };
-    trace_body<COUNT, false, SHADOW, TLAS, REFRACT, true>(S, F, out, counters, stack, blockIdx.x, (int)(threadIdx.x & 63));
+    trace_body<COUNT, false, SHADOW, TLAS, REFRACT, CRT_TRACE_SSAA>(S, F, out, counters, stack, blockIdx.x, (int)(threadIdx.x & 63));
+}
+
+// Trace with the first-hit planes: trace_body's GBUFFER case. No counters, no stamps (refused): eight instantiations. Every one has
+// the parked LDS slot of the SHADOW stack (the path's energy waits there during a traversal). Seven fit the plain kernel's budget
+// (64 VGPRs, 8 waves/SIMD, no scratch). <1,1,1> -- shadow rays, instance tree and refraction at once -- spills 69 SGPRs where its
+// crt_trace_kernel twin spills 60: a second VGPR of spill lanes, which at 64 VGPRs pushes the pixel's radiance into scratch (16 B
+// per lane around the first traversal). It is bounded at 7 waves/SIMD instead and takes 68 VGPRs without scratch.
+template <bool SHADOW, bool TLAS, bool REFRACT>
+__global__ __launch_bounds__(CRT_BLOCK, (SHADOW && TLAS && REFRACT) ? CRT_WAVES_PER_SIMD - 1 : CRT_WAVES_PER_SIMD)
+void crt_trace_gbuffer_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out, CrtGBuffer gb)
+{
+    __shared__ uint32_t s_stack[CRT_LDS_SLOTS * CRT_BLOCK];
+    const CrtTraceStack<true, TLAS> stack = { (crt_lds_u32_ptr)s_stack + threadIdx.x, S.stackOverflow };
+    trace_body<false, false, SHADOW, TLAS, REFRACT, CRT_TRACE_GBUFFER>(S, F, out, nullptr, stack, blockIdx.x, (int)(threadIdx.x & 63), &gb);
 }
 
 // ---- wavefront form of Trace: one launch per bounce with ballot compaction in between ----------------

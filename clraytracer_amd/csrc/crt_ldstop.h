@@ -73,5 +73,5 @@ __global__ __launch_bounds__(CRT_BLOCK * CRT_TOP_WAVES) void crt_trace_ldstop_ke
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);   // wave-uniform: the block number stays in SGPRs
     const int vb = (int)(((blockIdx.x >> 3) * CRT_TOP_WAVES + (uint32_t)wave) * 8u + (blockIdx.x & 7u));
     const CrtStackTop stack = { (crt_lds_u32_ptr)s_stack + wave * (CRT_TOP_LDS_SLOTS * CRT_BLOCK) + lane, S.stackOverflow, (crt_lds_f32x4_ptr)s_top, (uint32_t)vb };
-    trace_body<COUNT, false, false, false, false, false>(S, F, out, counters, stack, vb, lane);
+    trace_body<COUNT, false, false, false, false, CRT_TRACE_PLAIN>(S, F, out, counters, stack, vb, lane);
 }

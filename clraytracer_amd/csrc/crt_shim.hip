@@ -46,7 +46,7 @@ const char* crt_error_string(int code)
     case CRT_OK: return "ok";
     case CRT_E_NOT_INITIALIZED: return "crt: not initialized (crt_init failed or was not called)";
     case CRT_E_BAD_ARGUMENT: return "crt: bad argument or invalid scene data";
-    case CRT_E_OUT_OF_RANGE: return "crt: upload exceeds a fixed device pool";
+    case CRT_E_OUT_OF_RANGE: return "crt: out of range (an upload beyond a fixed device pool, a pixel outside the frame)";
     case CRT_E_NO_DEVICE: return "crt: no usable HIP device";
     case CRT_E_UNSUPPORTED: return "crt: unsupported";
     default: return code > 0 ? hipGetErrorString((hipError_t)code) : "crt: unknown error";
@@ -240,7 +240,7 @@ int crt_render(const CrtTraceArgs* args, const float invView[16], const float in
     if (!args || !invView || !invProj) return CRT_E_BAD_ARGUMENT;
     if (flags & (CRT_RENDER_WRITE_RAYS | CRT_RENDER_STAMPS)) return CRT_E_UNSUPPORTED;   // single-device diagnostics
     if ((flags & CRT_RENDER_SSAA2) && (flags & CRT_RENDER_SSAA4)) return CRT_E_BAD_ARGUMENT;
-    { Use u(0); RCCHK(refuse_ssaa(flags)); }
+    { Use u(0); RCCHK(refuse_ssaa(flags)); RCCHK(refuse_gbuffer(flags)); }
     // The dispatcher decides the frame slot once for every device (the devices' own rotation counters are not used in a
     // session: a device that owns no rows of a short frame, or whose submission failed, stays in step).
     RenderPlan plan;
@@ -297,6 +297,9 @@ int crt_read_output_rgba8(uint8_t* dst, size_t bytes) { NEED_SESSION(); RCCHK(dr
 int crt_map_host_frame_back(int framesBack, const void** ptr, size_t* bytes) { ON_PRIMARY(crt1_map_host_frame_back(framesBack, ptr, bytes)); }
 int crt_map_host_frame(const void** ptr, size_t* bytes) { return crt_map_host_frame_back(0, ptr, bytes); }
 int crt_read_rays(float* dst, size_t floats) { NEED_SESSION(); if (M.n > 1) return CRT_E_UNSUPPORTED; ON_PRIMARY(crt1_read_rays(dst, floats)); }
+int crt_read_gbuffer(int plane, void* dst, size_t bytes) { ON_PRIMARY(crt1_read_gbuffer(plane, dst, bytes)); }
+void* crt_gbuffer_device_ptr(int plane) { if (M.n == 0) return nullptr; Use u(0); return crt1_gbuffer_device_ptr(plane); }
+int crt_pick_pixel(int x, int y, CrtGBufferPixel* out) { ON_PRIMARY(crt1_pick_pixel(x, y, out)); }
 void* crt_output_device_ptr(void) { if (M.n == 0) return nullptr; Use u(0); return crt1_output_device_ptr(); }
 float crt_last_kernel_ms(int which) { if (M.n == 0) return -1.0f; Use u(0); return crt1_last_kernel_ms(which); }
 int crt_frame_time_stats(CrtFrameStats* out, int reset)

@@ -30,6 +30,9 @@ struct FrameSlot {
     float4* aux = nullptr; size_t auxPixels = 0;   // CRT_RENDER_FXAA: the unfiltered frame the filter reads (allocated on first use)
     CrtBounceRay* blockQueue = nullptr; size_t blockQueueCap = 0;   // CRT_KERNEL=block / wavefront: bounce-ray queue, one 64- or 128-record range per workgroup of the primary launch
     uint32_t* wfCount = nullptr; size_t wfCap = 0;                  // CRT_KERNEL=wavefront: per primary wave {continuing rays}, {offset within its XCD}, then the 8 per-XCD totals
+    // CRT_RENDER_GBUFFER: this slot's first-hit planes, one allocation of 36 B per pixel (geometry, ids, albedo back to back), made on
+    // the slot's first G-buffer frame (slot_gbuffer)
+    char* gbuf = nullptr; size_t gbufBytes = 0;
     uint32_t* ovf = nullptr; size_t ovfWords = 0;   // traversal-stack overflow area of this slot's launches (CrtStack), one block per workgroup
     uint32_t* lists = nullptr; size_t listsCap = 0;   // feedback launch lists: order, costs, sort keys, lengths (prepare_launch_lists)
     int orderSlots = -1; int orderKey[7] = { 0, 0, 0, 0, 0, 0, 0 };
@@ -65,6 +68,7 @@ struct State {
     FrameSlot slot[CRT_MAX_FRAMES_IN_FLIGHT]; int nSlots = 3;
     hipStream_t stream = nullptr;              // == slot[0].stream: uploads, queries, diagnostics
     int cur = 0;                               // slot of the most recently submitted frame
+    int gbufSlot = -1;                         // ... of the most recently submitted CRT_RENDER_GBUFFER frame; -1: none since crt_init / the last resize
     int readbackRing[CRT_MAX_FRAMES_IN_FLIGHT] = { -1, -1, -1, -1, -1, -1, -1, -1 }; unsigned readbackCount = 0;   // slots of the latest CRT_RENDER_READBACK frames
     unsigned asyncSeq = 0; bool othersBusy = false;   // frames possibly running on slots > 0
     // Start-up stagger of a burst of frames in flight: frames submitted to an idle device start together, run in lockstep and have
@@ -267,8 +271,9 @@ int alloc_frame_buffers(int w, int h)
         if (fs.out) (void)hipFree(fs.out);
         fs.out = outs[i];
         if (fs.aux) { (void)hipFree(fs.aux); fs.aux = nullptr; fs.auxPixels = 0; }
+        if (fs.gbuf) { (void)hipFree(fs.gbuf); fs.gbuf = nullptr; fs.gbufBytes = 0; }
     }
-    g.width = w; g.height = h; g.readbackCount = 0; g.pipelinedLatencyMs = 0.0f;
+    g.width = w; g.height = h; g.readbackCount = 0; g.pipelinedLatencyMs = 0.0f; g.gbufSlot = -1;
     return CRT_OK;
 }
 

@@ -127,7 +127,7 @@ static void release_all()
                      g.texels, g.materials, g.textures, g.rays, g.counters, g.err, g.triReachBits, g.topPairs, g.topRootRefs,
                      g.queryBuf, g.buildBuf, g.buildTris, g.stamps, g.noCullBounds };
     for (FrameSlot& fs : g.slot) {
-        void* q[] = { fs.out, fs.aux, fs.blockQueue, fs.wfCount, fs.ovf, fs.lists, fs.mixOrder, fs.packBuf, fs.instBlock, fs.devInstances };
+        void* q[] = { fs.out, fs.aux, fs.blockQueue, fs.wfCount, fs.ovf, fs.lists, fs.mixOrder, fs.packBuf, fs.instBlock, fs.devInstances, fs.gbuf };
         for (void* p : q) if (p) (void)hipFree(p);
         if (fs.staging) (void)hipHostFree(fs.staging);
         if (fs.staged) (void)hipEventDestroy(fs.staged);

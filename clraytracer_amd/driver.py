@@ -94,7 +94,7 @@ class Session:
             self.width, self.height = int(width), int(height)
 
     # ---- rendering through the mirrored Renderer ----
-    def render(self, sun_angle=None, postprocess=False, shadows=False, pipelined=False, refraction=False, fxaa=False, ssaa=1):
+    def render(self, sun_angle=None, postprocess=False, shadows=False, pipelined=False, refraction=False, fxaa=False, ssaa=1, gbuffer=False):
         if ssaa not in (1, 2, 4):
             raise ValueError(f"ssaa must be 1, 2 or 4, not {ssaa!r}")
         self.h.crth_set_postprocess(1 if postprocess else 0)
@@ -102,6 +102,7 @@ class Session:
         self.h.crth_set_refraction(1 if refraction else 0)    # extension, off upstream
         self.h.crth_set_fxaa(1 if fxaa else 0)                # extension: dead code upstream (kernel_main.cl:349)
         self.h.crth_set_supersampling(int(ssaa))              # extension: k x k supersampling, 1, 2 or 4
+        self.h.crth_set_gbuffer(1 if gbuffer else 0)          # extension: also write the first-hit planes (read_gbuffer, pick)
         self.h.crth_set_pipelined(1 if pipelined else 0)      # frames in flight; output()/uploads wait
         frame = self.h.crth_render(float(self.scene.sun_angle if sun_angle is None else sun_angle))
         if frame == 0:
@@ -115,6 +116,30 @@ class Session:
             self._check("Renderer::MapOutput")
             raise CrtError("Renderer::MapOutput returned null")
         return _lib.as_array(ptr, self.width * self.height * 4, np.float32).reshape(self.height, self.width, 4)
+
+    def read_gbuffer(self):
+        """The first-hit planes of the last frame rendered with gbuffer=True (Renderer::MapGBuffer): {"geometry", "ids", "albedo"} ->
+        (height, width) arrays of _lib.GBUFFER_GEOMETRY_DTYPE / GBUFFER_IDS_DTYPE / uint32."""
+        planes = {}
+        for name, (plane, dtype) in _lib.GBUFFER_PLANE_DTYPES.items():
+            ptr = self.h.crth_map_gbuffer(plane)
+            if not ptr:
+                self._raise_and_clear(f"Renderer::MapGBuffer({name})")
+            planes[name] = _lib.as_array(ptr, self.width * self.height, dtype).reshape(self.height, self.width)
+        return planes
+
+    def pick(self, x, y):
+        """What the primary ray of pixel (x, y) hit in that frame (Renderer::PickPixel): one _lib.GBUFFER_PIXEL_DTYPE record."""
+        out = np.zeros(1, _lib.GBUFFER_PIXEL_DTYPE)
+        if not self.h.crth_pick_pixel(int(x), int(y), out.ctypes.data):
+            self._raise_and_clear(f"Renderer::PickPixel({x}, {y})")
+        return out[0]
+
+    def _raise_and_clear(self, what):
+        # a failed query (no G-buffer frame yet, a pixel outside the frame) must not poison the session's later _check()s
+        rc = self.h.crth_last_error()
+        self.h.crth_clear_error()
+        raise CrtError(f"{what}: error {rc}: {self.hip.crt_error_string(rc).decode()}")
 
     # ---- direct C-ABI access (same device state the mirror drives) ----
     def trace_args(self, sun_angle=None):
@@ -160,6 +185,15 @@ class Session:
         b, bpp = C.c_uint64(0), C.c_int(0)
         _lib.check(self.hip.crt_debug_last_gather(C.byref(b), C.byref(bpp)), "crt_debug_last_gather")
         return int(b.value), int(bpp.value)
+
+    def read_gbuffer_raw(self):
+        """The same planes through crt_read_gbuffer."""
+        planes = {}
+        for name, (plane, dtype) in _lib.GBUFFER_PLANE_DTYPES.items():
+            out = np.empty((self.height, self.width), dtype)
+            _lib.check(self.hip.crt_read_gbuffer(plane, out.ctypes.data, out.nbytes), f"crt_read_gbuffer({name})")
+            planes[name] = out
+        return planes
 
     def read_rays(self):
         out = np.empty((self.height, self.width, 3), np.float32)

@@ -18,7 +18,8 @@ namespace {
     bool postProcess = true;   // upstream always runs PostProcess (Renderer.cpp:360-363)
     bool shadows = false, pipelined = false, unorm8 = false, refraction = false, fxaa = false;
     int supersampling = 1;     // k of k x k supersampling: 1, 2 or 4 (CRT_RENDER_SSAA2 / SSAA4)
-    std::vector<unsigned char> hostFrame8;
+    bool gbuffer = false;      // CRT_RENDER_GBUFFER
+    std::vector<unsigned char> hostFrame8, hostPlane[3];
     float timeSeconds = 0.0f;
     unsigned frameIndex = 0;
     int lastError = 0;
@@ -57,6 +58,7 @@ void Renderer::SetSupersampling(int factor)
     if (factor != 1 && factor != 2 && factor != 4) { lastError = CRT_E_BAD_ARGUMENT; std::fprintf(stderr, "[Renderer] SetSupersampling(%d): factor must be 1, 2 or 4\n", factor); return; }
     supersampling = factor;
 }
+void Renderer::SetGBuffer(bool enabled) { gbuffer = enabled; }
 void Renderer::SetUnorm8(bool enabled) { unorm8 = enabled; }
 void Renderer::SetPipelined(bool enabled) { pipelined = enabled; }
 void Renderer::SetTime(float seconds) { timeSeconds = seconds; }
@@ -183,7 +185,7 @@ unsigned Renderer::Render(float sunAngle)
     args.cameraPos[0] = camera.position.x; args.cameraPos[1] = camera.position.y; args.cameraPos[2] = camera.position.z;
     args.time = timeSeconds; args.numMeshes = g_NumMeshInstances; args.sunAngle = sunAngle;
     const int flags = (postProcess ? CRT_RENDER_POSTPROCESS : 0) | (shadows ? CRT_RENDER_SHADOWS : 0) | (refraction ? CRT_RENDER_REFRACTION : 0) | (fxaa ? CRT_RENDER_FXAA : 0) | (pipelined ? CRT_RENDER_ASYNC : 0) | (unorm8 ? CRT_RENDER_UNORM8 : 0)
-                    | (supersampling == 2 ? CRT_RENDER_SSAA2 : supersampling == 4 ? CRT_RENDER_SSAA4 : 0);
+                    | (supersampling == 2 ? CRT_RENDER_SSAA2 : supersampling == 4 ? CRT_RENDER_SSAA4 : 0) | (gbuffer ? CRT_RENDER_GBUFFER : 0);
     if (!check(crt_render(&args, &camera.inverseView.m[0][0], &camera.inverseProjection.m[0][0], flags), "crt_render")) return 0;
     return ++frameIndex;
 }
@@ -204,6 +206,22 @@ const unsigned char* Renderer::MapOutputRGBA8()
     hostFrame8.resize(n);
     if (!check(crt_read_output_rgba8(hostFrame8.data(), n), "crt_read_output_rgba8")) return nullptr;
     return hostFrame8.data();
+}
+
+const void* Renderer::MapGBuffer(int plane)
+{
+    if (!deviceReady) { lastError = CRT_E_NOT_INITIALIZED; return nullptr; }
+    if (plane < CRT_GBUFFER_GEOMETRY || plane > CRT_GBUFFER_ALBEDO) { lastError = CRT_E_BAD_ARGUMENT; return nullptr; }
+    const size_t n = (size_t)camera.projWidth * (size_t)camera.projHeight * (plane == CRT_GBUFFER_ALBEDO ? 4 : 16);
+    hostPlane[plane].resize(n);
+    if (!check(crt_read_gbuffer(plane, hostPlane[plane].data(), n), "crt_read_gbuffer")) return nullptr;
+    return hostPlane[plane].data();
+}
+
+bool Renderer::PickPixel(int x, int y, CrtGBufferPixel& out)
+{
+    if (!deviceReady) { lastError = CRT_E_NOT_INITIALIZED; return false; }
+    return check(crt_pick_pixel(x, y, &out), "crt_pick_pixel");
 }
 
 void Renderer::Terminate()

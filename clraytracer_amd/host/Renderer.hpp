@@ -42,6 +42,9 @@ namespace Renderer
     void SetShadows(bool enabled);        // extension: the shadow ray upstream leaves as a TODO (kernel_main.cl:256-258); off by default
     void SetFXAA(bool enabled);           // extension: upstream's FXAA (kernel_main.cl:289-340) is dead code (call commented out, kernel_main.cl:349); runs it as the first PostProcess stage; off by default
     void SetSupersampling(int factor);    // extension: k x k supersampled anti-aliasing resolved in the Trace kernel, factor 1 (default), 2 or 4; any other value sets LastError() to CRT_E_BAD_ARGUMENT and keeps the setting
+    void SetGBuffer(bool enabled);        // extension: Render() also writes the first-hit planes (CRT_RENDER_GBUFFER: normal + distance, instance / triangle / barycentrics, albedo); off by default
+    const void* MapGBuffer(int plane);    // host copy of plane CRT_GBUFFER_GEOMETRY / IDS / ALBEDO of the last G-buffer frame (width*height elements), valid until next Render; null without one
+    bool PickPixel(int x, int y, CrtGBufferPixel& out); // what that frame's primary ray hit at pixel (x, y): 36 bytes from the device, no ray cast (replaces CPU_RayCast(ScreenPointToRaySSE(mouse)), Engine.cpp:112-126)
     void SetRefraction(bool enabled);     // extension: upstream's README TODO "refraction / transculency": materials with MTL d < 1 transmit; off by default
     void SetPipelined(bool enabled);      // Render() returns without waiting (frames in flight); MapOutput()/uploads wait. Off by default (upstream clFinish()es)
     void SetTime(float seconds);          // TraceArgs.time (Window::GetTime upstream)

@@ -35,7 +35,7 @@ int crth_initialize_host_only(int width, int height)
 
 void crth_terminate(void) { if (hostOnly) ResourceManager::Finalize(); else Renderer::Terminate(); hostOnly = false; }
 int crth_last_error(void) { return hostOnlyError ? hostOnlyError : Renderer::LastError(); }
-void crth_clear_error(void) { Renderer::ClearError(); }
+void crth_clear_error(void) { hostOnlyError = 0; Renderer::ClearError(); }
 
 void crth_prepare_meshes(void) { ResourceManager::PrepareMeshes(); }
 int crth_import_texture(const char* path) { return ResourceManager::ImportTexture(path); }
@@ -98,6 +98,14 @@ void crth_set_shadows(int enabled) { Renderer::SetShadows(enabled != 0); }
 void crth_set_refraction(int enabled) { Renderer::SetRefraction(enabled != 0); }
 void crth_set_fxaa(int enabled) { Renderer::SetFXAA(enabled != 0); }
 void crth_set_supersampling(int factor) { Renderer::SetSupersampling(factor); }
+void crth_set_gbuffer(int enabled) { Renderer::SetGBuffer(enabled != 0); }
+// (a host-only session has no frame: the refusal is reported like crth_render's, not as "error 0")
+const void* crth_map_gbuffer(int plane) { if (hostOnly) { hostOnlyError = CRT_E_NOT_INITIALIZED; return nullptr; } return Renderer::MapGBuffer(plane); }
+int crth_pick_pixel(int x, int y, CrtGBufferPixel* out)
+{
+    if (hostOnly) { hostOnlyError = CRT_E_NOT_INITIALIZED; return 0; }
+    return (out && Renderer::PickPixel(x, y, *out)) ? 1 : 0;
+}
 void crth_set_unorm8(int enabled) { Renderer::SetUnorm8(enabled != 0); }
 const unsigned char* crth_map_output_rgba8(void) { return hostOnly ? nullptr : Renderer::MapOutputRGBA8(); }
 void crth_set_pipelined(int enabled) { Renderer::SetPipelined(enabled != 0); }

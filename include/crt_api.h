@@ -30,7 +30,7 @@ enum {
     CRT_OK = 0,
     CRT_E_NOT_INITIALIZED = -1,
     CRT_E_BAD_ARGUMENT    = -2,
-    CRT_E_OUT_OF_RANGE    = -3,   /* upload beyond a fixed-size device pool */
+    CRT_E_OUT_OF_RANGE    = -3,   /* upload beyond a fixed-size device pool; crt_pick_pixel outside the frame */
     CRT_E_NO_DEVICE       = -4,
     CRT_E_UNSUPPORTED     = -5
 };
@@ -69,9 +69,28 @@ enum {
                                      (UNORM8, PostProcess, FXAA, read-back) see the resolved W x H frame. Counters count every subsample
                                      ray. With CRT_RENDER_SSAA4: CRT_E_BAD_ARGUMENT. Refused (CRT_E_UNSUPPORTED): with STAMPS, WRITE_RAYS
                                      or DIAG_MIX3, under a CRT_KERNEL form other than the default, above 7680 x 4320 virtual pixels */
-    CRT_RENDER_SSAA4       = 4096  /* extension: the same with 4x4 subsamples (virtual frame 4W x 4H, shift 3/8 px; the pair sums are
+    CRT_RENDER_SSAA4       = 4096, /* extension: the same with 4x4 subsamples (virtual frame 4W x 4H, shift 3/8 px; the pair sums are
                                      repeated: sx bit 0, sy bit 0, sx bit 1, sy bit 1, then times 1/16) */
+    CRT_RENDER_GBUFFER     = 8192  /* extension: the Trace launch also writes the three first-hit planes below (CRT_GBUFFER_*), what the
+                                     pixel's PRIMARY ray hit, for picking, denoisers and ID views: crt_read_gbuffer, crt_pick_pixel,
+                                     crt_gbuffer_device_ptr. The colour frame is the same bits as without the flag; the planes do not
+                                     depend on the other flags (with REFRACTION: the first hit, whichever ray continues). The planes
+                                     belong to the frame slot (frames in flight keep their own; 36 B per pixel, allocated on the slot's
+                                     first such frame); under crt_set_row_bands only this rank's rows are written. Refused
+                                     (CRT_E_UNSUPPORTED): with SSAA2 / SSAA4, STAMPS, DIAG_MIX3 or COUNTERS, under a CRT_KERNEL form other
+                                     than the default, in a session of several devices */
 };
+
+/* The planes of a CRT_RENDER_GBUFFER frame: W x H elements each, row-major like the frame. The world-space hit point is
+ * cameraPos + t * rayDir (t is the same parameter in instance space and in world space).
+ *   GEOMETRY  float[4]: record.normal of kernel_main.cl:236 (x, y, z), then t.                 Miss: 0, 0, 0, 99999.0f
+ *   IDS       { int32 instance; uint32 triIndex; float u; float v; }: what crt_query_hits
+ *             returns for the pixel's ray.                                                     Miss: -1, 0, 0.0f, 0.0f
+ *   ALBEDO    uint32: 0xFF000000 | b << 16 | g << 8 | r, the bytes of MultiplyColorU32(pixel,
+ *             material.color) (kernel_main.cl:245) before the / 255.                           Miss: 0
+ * A hit beyond upstream's InfMinusOne (t > 99998, shaded as sky, kernel_main.cl:219) keeps its ids and t but has the normal and
+ * albedo of a miss. */
+enum { CRT_GBUFFER_GEOMETRY = 0, CRT_GBUFFER_IDS = 1, CRT_GBUFFER_ALBEDO = 2 };
 
 /* Device work counters of the last CRT_RENDER_COUNTERS / crt_query_hits launch. Same meaning as
  * the oracle's OrcStats so tests can require exact equality. */
@@ -179,6 +198,15 @@ int crt_map_host_frame(const void** ptr, size_t* bytes);
 int crt_map_host_frame_back(int framesBack, const void** ptr, size_t* bytes);
 int crt_read_rays(float* dst, size_t floats);                 /* width*height*3, after WRITE_RAYS */
 void* crt_output_device_ptr(void);
+/* The first-hit planes of the most recently submitted CRT_RENDER_GBUFFER frame (later frames without the flag leave them alone).
+ * crt_read_gbuffer copies a whole plane (bytes = width * height * 16, or * 4 for CRT_GBUFFER_ALBEDO) after waiting for the frames in
+ * flight; CRT_E_BAD_ARGUMENT for an unknown plane, a wrong size, or when no such frame has been submitted since crt_init or the last
+ * crt_resize that changed the frame. crt_gbuffer_device_ptr: the plane on the device, NULL under the same conditions.
+ * crt_pick_pixel: one pixel of all three planes (36 bytes travel, not a frame) -- the GPU's answer to upstream's mouse pick
+ * CPU_RayCast(camera.ScreenPointToRaySSE(mouse)) (Engine.cpp:112-126); CRT_E_OUT_OF_RANGE outside the frame. */
+int crt_read_gbuffer(int plane, void* dst, size_t bytes);
+void* crt_gbuffer_device_ptr(int plane);
+int crt_pick_pixel(int x, int y, CrtGBufferPixel* out);
 int crt_owned_rows(void);                                     /* rows this rank renders per frame */
 
 /* Timing of the last crt_render measured with HIP events on the launch stream.

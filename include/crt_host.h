@@ -58,6 +58,9 @@ void crth_set_postprocess(int enabled);
 void crth_set_shadows(int enabled);                          /* Renderer::SetShadows (extension) */
 void crth_set_fxaa(int enabled);                             /* Renderer::SetFXAA (extension) */
 void crth_set_supersampling(int factor);                     /* Renderer::SetSupersampling (extension): 1, 2 or 4 */
+void crth_set_gbuffer(int enabled);                          /* Renderer::SetGBuffer (extension): frames also write the first-hit planes */
+const void* crth_map_gbuffer(int plane);                     /* Renderer::MapGBuffer: CRT_GBUFFER_GEOMETRY / IDS / ALBEDO, null on failure */
+int crth_pick_pixel(int x, int y, CrtGBufferPixel* out);     /* Renderer::PickPixel: 1, or 0 on failure (crth_last_error) */
 void crth_set_refraction(int enabled);                       /* Renderer::SetRefraction (extension) */
 void crth_set_unorm8(int enabled);                           /* Renderer::SetUnorm8 (hazard H8) */
 const unsigned char* crth_map_output_rgba8(void);            /* Renderer::MapOutputRGBA8 */

@@ -80,6 +80,18 @@ typedef struct CrtRayHit {
     int32_t instance;                 /* -1: miss */
 } CrtRayHit;
 
+/* One pixel of the three first-hit planes of a CRT_RENDER_GBUFFER frame (crt_pick_pixel; crt_api.h describes the planes):
+ * hit: record.normal (kernel_main.cl:236), the hit record as CrtRayHit holds it, 0xFF000000 | b << 16 | g << 8 | r of record.color;
+ * miss: normal 0, t = 99999, instance -1, everything else 0. */
+typedef struct CrtGBufferPixel {
+    float normal[3];
+    float t;
+    int32_t instance;                 /* -1: miss */
+    uint32_t triIndex;
+    float u, v;
+    uint32_t albedo;
+} CrtGBufferPixel;
+
 /* Compile-time limits of the reference. */
 enum {
     CRT_MAX_INSTANCES   = 401,        /* Renderer.hpp:16 */
@@ -102,6 +114,7 @@ static_assert(sizeof(CrtTexture) == 16, "Texture must be 16 B");
 static_assert(sizeof(CrtRGB8) == 3, "RGB8 must be 3 B");
 static_assert(sizeof(CrtMeshInstance) == 80, "MeshInstance must be 80 B");
 static_assert(sizeof(CrtTraceArgs) == 24, "TraceArgs must be 24 B");
+static_assert(sizeof(CrtGBufferPixel) == 36, "GBufferPixel must be 36 B (16 + 16 + 4, the three planes)");
 #endif
 #endif
 

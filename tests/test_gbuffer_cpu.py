@@ -1,0 +1,153 @@
+"""CRT_RENDER_GBUFFER without a GPU: the ABI (flag, plane constants, entry points in both headers and both ctypes tables, the 36-byte
+pixel), the registers of crt_trace_gbuffer_kernel's eight instantiations (hipcc cross-compiles crt_shim.hip for gfx950, as
+test_kernel_resources does), and the numpy reference the GPU tests compare the planes with (tests/gbuffer_ref.py), pinned here against
+the C oracle: shading bounce 0 from the reference planes must reproduce the oracle's primary-only frame bit for bit."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from clraytracer_amd import _lib, driver, scenes
+import gbuffer_ref
+import oracle_lib
+from util import bits
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = "/opt/rocm/bin/hipcc"
+ORC_EXT_PRIMARY_ONLY = 4                  # oracle/crt_oracle.h
+
+
+def header(name):
+    return open(os.path.join(ROOT, "include", name)).read()
+
+
+def test_flag_planes_and_declarations():
+    api, types, host = header("crt_api.h"), header("crt_types.h"), header("crt_host.h")
+    assert re.search(r"CRT_RENDER_GBUFFER\s*=\s*8192\b", api)
+    for name, value in (("CRT_GBUFFER_GEOMETRY", 0), ("CRT_GBUFFER_IDS", 1), ("CRT_GBUFFER_ALBEDO", 2)):
+        assert re.search(r"%s\s*=\s*%d\b" % (name, value), api), name
+    assert "int crt_read_gbuffer(int plane, void* dst, size_t bytes);" in api
+    assert "void* crt_gbuffer_device_ptr(int plane);" in api
+    assert "int crt_pick_pixel(int x, int y, CrtGBufferPixel* out);" in api
+    assert re.search(r"typedef struct CrtGBufferPixel \{\s*float normal\[3\];\s*float t;\s*int32_t instance;[^}]*uint32_t triIndex;\s*float u, v;\s*"
+                     r"uint32_t albedo;\s*\} CrtGBufferPixel;", types)
+    assert re.search(r"static_assert\(sizeof\(CrtGBufferPixel\) == 36,", types)
+    assert "void crth_set_gbuffer(int enabled);" in host
+    assert "const void* crth_map_gbuffer(int plane);" in host
+    assert "int crth_pick_pixel(int x, int y, CrtGBufferPixel* out);" in host
+
+
+def test_bindings_and_dtypes():
+    for n in ("crt_read_gbuffer", "crt_gbuffer_device_ptr", "crt_pick_pixel"):
+        assert n in _lib.HIP_API and hasattr(_lib.hip(), n), n
+    for n in ("crth_set_gbuffer", "crth_map_gbuffer", "crth_pick_pixel"):
+        assert n in _lib.HOST_API and hasattr(_lib.host(), n), n
+    assert _lib.CRT_RENDER_GBUFFER == 8192
+    assert (_lib.CRT_GBUFFER_GEOMETRY, _lib.CRT_GBUFFER_IDS, _lib.CRT_GBUFFER_ALBEDO) == (0, 1, 2)
+    assert _lib.GBUFFER_PIXEL_DTYPE.itemsize == 36
+    assert _lib.GBUFFER_GEOMETRY_DTYPE.itemsize == 16 and _lib.GBUFFER_IDS_DTYPE.itemsize == 16 and _lib.GBUFFER_ALBEDO_DTYPE.itemsize == 4
+    # one pixel is the three plane elements back to back
+    p = _lib.GBUFFER_PIXEL_DTYPE
+    assert [p.fields[f][1] for f in ("normal", "t", "instance", "tri", "u", "v", "albedo")] == [0, 12, 16, 20, 24, 28, 32]
+    # without a session the new entry points refuse like the others
+    hip = _lib.hip()
+    assert hip.crt_read_gbuffer(0, None, 0) == -1 and hip.crt_pick_pixel(0, 0, None) == -1 and not hip.crt_gbuffer_device_ptr(0)
+
+
+def test_session_surface_without_a_device():
+    import inspect
+    assert inspect.signature(driver.Session.render).parameters["gbuffer"].default is False
+    assert callable(driver.Session.read_gbuffer) and callable(driver.Session.pick)
+    with driver.Session(64, 48, host_only=True) as s:
+        s.load_scene(scenes.get("tiny"))
+        # ... and says why: CRT_E_NOT_INITIALIZED, not "error 0"; the refusal does not outlive the report
+        with pytest.raises(_lib.CrtError, match="error -1: "):
+            s.read_gbuffer()
+        assert s.h.crth_last_error() == 0
+        with pytest.raises(_lib.CrtError, match="error -1: "):
+            s.pick(1, 1)
+        assert s.h.crth_last_error() == 0
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC) or shutil.which("c++filt") is None, reason="needs hipcc and c++filt")
+def test_gbuffer_instantiations_keep_the_plain_kernels_budget():
+    flags = re.search(r"^HIPFLAGS = (.*)$", open(os.path.join(ROOT, "Makefile")).read(), re.M).group(1)
+    flags = flags.replace("$(ARCH)", "gfx950").split()
+    cmd = [HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "clraytracer_amd/csrc/crt_shim.hip"), "-o", os.devnull]
+    p = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    rows, cur = {}, None
+    for line in p.stderr.splitlines():
+        m = re.search(r"remark: +Function Name: (\S+)", line)
+        if m:
+            name = subprocess.run(["c++filt", m.group(1)], stdout=subprocess.PIPE, text=True).stdout.strip()
+            cur = rows.setdefault(re.sub(r"\(.*", "", name).replace("void ", ""), {})
+            continue
+        m = re.search(r"remark: +([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = int(m.group(2))
+    gb = {k: v for k, v in rows.items() if k.startswith("crt_trace_gbuffer_kernel<")}
+    assert len(gb) == 8, sorted(rows)
+    for name, r in gb.items():
+        assert r["ScratchSize"] == 0 and r["AGPRs"] == 0 and r["LDS Size"] == 5120, (name, r)
+        if name == "crt_trace_gbuffer_kernel<true, true, true>":
+            # shadow rays + instance tree + refraction at once: bounded at 7 waves/SIMD (DESIGN.md 4c says why), 68 VGPRs
+            assert r["VGPRs"] == 68 and r["Occupancy"] == 7, (name, r)
+        else:
+            assert r["VGPRs"] == 64 and r["Occupancy"] == 8, (name, r)
+    # the kernels a frame without the flag reaches are counted by name elsewhere (test_kernel_resources, test_ssaa_kernel_resources);
+    # the new entry is neither a crt_trace_kernel nor a crt_trace_ssaa_kernel instantiation
+    assert len([k for k in rows if k.startswith("crt_trace_kernel<false, false,")]) == 8
+    assert len([k for k in rows if k.startswith("crt_trace_ssaa_kernel<")]) == 16
+
+
+@pytest.mark.parametrize("name,w,h", [("tiny", 200, 120), ("cornell-1k", 333, 187), ("sponza-sibenik", 320, 180), ("nanosuit-demo", 256, 144)])
+def test_reference_planes_shade_to_the_oracles_primary_only_frame(name, w, h, nthreads):
+    sc = scenes.get(name)
+    with driver.Session(w, h, host_only=True) as s:
+        s.load_scene(sc)
+        a = {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in s.arenas().items()}
+        iv, ip, pos = s.camera()
+    orc = oracle_lib.Oracle(a, nthreads=nthreads)
+    rays = orc.raygen(w, h, iv, ip)
+    planes = gbuffer_ref.reference_planes(a, orc, rays, pos)
+    got, shaded = gbuffer_ref.shade_primary(a, planes, rays, pos, sc.sun_angle)
+    # the oracle's frame of bounce 0 alone
+    ref = np.zeros((h, w, 4), np.float32)
+    args = oracle_lib.CrtTraceArgs()
+    args.cameraPos[0], args.cameraPos[1], args.cameraPos[2] = [float(x) for x in pos]
+    args.time = 0.0; args.numMeshes = orc.s.numInstances; args.sunAngle = float(sc.sun_angle)
+    st = oracle_lib.OrcStats()
+    oracle_lib.lib().orc_trace_ex(C.byref(orc.s), C.byref(args), rays.ctypes.data, w, h, 0, h, ref.ctypes.data, C.byref(st), nthreads, ORC_EXT_PRIMARY_ONLY)
+    hits = int(shaded.sum())
+    equal = (bits(got) == bits(ref[..., :3])).all(axis=2)
+    print(f"{name} {w}x{h}: {int((equal & shaded).sum())} of {hits} hit pixels bit-equal")
+    assert hits >= 2000 and hits == st.as_dict()["hits"]
+    assert (equal | ~shaded).all(), f"{int((~equal & shaded).sum())} of {hits} hit pixels differ"
+    assert not np.isnan(planes["geometry"]["normal"]).any()
+    # the planes' own invariants: a miss is (0, 0, 0, 99999), -1, 0; a hit is opaque and names an instance
+    miss = planes["ids"]["instance"] < 0
+    assert np.array_equal(miss, ~shaded)
+    assert (planes["geometry"]["t"][miss] == gbuffer_ref.MISS_T).all() and (planes["geometry"]["normal"][miss] == 0).all()
+    assert (planes["albedo"][miss] == 0).all() and (planes["ids"]["tri"][miss] == 0).all()
+    assert ((planes["albedo"][~miss] >> 24) == 0xFF).all()
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC) or shutil.which("c++filt") is None, reason="needs hipcc and c++filt")
+def test_every_earlier_kernel_keeps_its_resource_line():
+    """tools/kernel_resources.py prints, for every kernel that existed before crt_trace_gbuffer_kernel, the line it printed then
+    (tests/golden/kernel_resources_before_gbuffer.txt is its output at that commit), in the same order; what it prints besides are
+    the eight new instantiations."""
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    now = p.stdout.splitlines()
+    before = open(os.path.join(ROOT, "tests", "golden", "kernel_resources_before_gbuffer.txt")).read().splitlines()
+    assert len(before) == 86
+    assert [l for l in now if not l.startswith("crt_trace_gbuffer_kernel<")] == before
+    new = [l for l in now if l.startswith("crt_trace_gbuffer_kernel<")]
+    assert len(new) == 8 and len(set(l.split(" VGPR")[0].strip() for l in new)) == 8 and len(now) == len(before) + 8

@@ -54,6 +54,110 @@ __device__ __forceinline__ float bvh_area(const float* mn, const float* mx)
     return (e0 * e0 + e1 * e0) + (e2 * e2 + 0.0f);
 }
 
+// ---- the steps every tier shares, each written once ----
+// The fold step of every min/max in upstream's builder, exactly `a < x ? a : x` / `a > x ? a : x` -- never fminf / fmaxf: x survives
+// when either operand is a NaN and when a and x are zeros of either sign, and that is what the zero-sign fix-up below and the
+// byte-exact tests rest on.
+template <class T> __device__ __forceinline__ T bvh_min(T a, T x) { return a < x ? a : x; }
+template <class T> __device__ __forceinline__ T bvh_max(T a, T x) { return a > x ? a : x; }
+
+// grows the box (mn, mx) by the three vertices of triangle t, v0 v1 v2 per component as UpdateNodeBounds does (BVH.cpp:54-74)
+__device__ __forceinline__ void bvh_grow_tri(const float* t, float mn[3], float mx[3])
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int v = 0; v < 3; ++v) { const float x = t[4 * v + c]; mn[c] = bvh_min(mn[c], x); mx[c] = bvh_max(mx[c], x); }
+}
+// the box of triangle t alone
+__device__ __forceinline__ void bvh_tri_box(const float* t, float mn[3], float mx[3])
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { mn[c] = 1e30f; mx[c] = -1e30f; }
+    bvh_grow_tri(t, mn, mx);
+}
+// aabb::grow(aabb) (BVH.cpp:29-37): both corners of the box b go into both the minimum and the maximum; an empty b is skipped
+__device__ __forceinline__ void bvh_grow_box(float mn[3], float mx[3], const float bmn[3], const float bmx[3])
+{
+    if (bmn[0] == 1e30f) return;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        mn[c] = bvh_min(mn[c], bmn[c]); mx[c] = bvh_max(mx[c], bmn[c]);
+        mn[c] = bvh_min(mn[c], bmx[c]); mx[c] = bvh_max(mx[c], bmx[c]);
+    }
+}
+
+// The bin of a centroid (BVH.cpp:115-129), scale = CRT_BVH_BINS / (cmax - cmin): clamped high first, then low, as upstream's
+// min(BINS - 1, (int)..) followed by the guard against a negative index.
+__device__ __forceinline__ int bvh_bin_index(float centroid, float cmin, float scale)
+{
+    int b = f2i((centroid - cmin) * scale);
+    b = (CRT_BVH_BINS - 1) < b ? (CRT_BVH_BINS - 1) : b;
+    if (b < 0) b = 0;
+    return b;
+}
+// The bins of one node: cnt[3][BINS] and bmin/bmax[3][BINS][3] as ordered images, flat, in LDS or global memory.
+__device__ __forceinline__ void bvh_bins_clear(uint32_t* cnt, uint32_t* bmin, uint32_t* bmax, int tid, int stride)
+{
+    for (int j = tid; j < 3 * CRT_BVH_BINS; j += stride) cnt[j] = 0;
+    for (int j = tid; j < 9 * CRT_BVH_BINS; j += stride) { bmin[j] = bvh_ordered(1e30f); bmax[j] = bvh_ordered(-1e30f); }
+}
+// triangle t into its bin of every axis whose centroid range (cmin, cmax) is not empty
+__device__ __forceinline__ void bvh_bins_add(uint32_t* cnt, uint32_t* bmin, uint32_t* bmax, const float* t, const float cmin[3], const float cmax[3])
+{
+    float tmn[3], tmx[3];
+    bvh_tri_box(t, tmn, tmx);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (cmax[a] == cmin[a]) continue;
+        const int b = bvh_bin_index(t[3 + 4 * a], cmin[a], (float)CRT_BVH_BINS / (cmax[a] - cmin[a]));
+        atomicAdd(&cnt[a * CRT_BVH_BINS + b], 1u);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { atomicMin(&bmin[(a * CRT_BVH_BINS + b) * 3 + c], bvh_ordered(tmn[c])); atomicMax(&bmax[(a * CRT_BVH_BINS + b) * 3 + c], bvh_ordered(tmx[c])); }
+    }
+}
+
+// The sign of a zero bound. The sequential fold keeps the LAST zero it meets (triangles in order, v0 v1 v2), the order-free
+// reductions here keep either. So where a finished bound (rmin, rmax) is zero, every triangle notes its zeros in
+// last[0..2] (minimum) / last[3..5] (maximum) as the sequence number 3 * triangle + vertex (i = the triangle's index in the
+// node; -1 = none), the node takes the maximum of those, and the bound is re-read from that vertex.
+__device__ __forceinline__ bool bvh_any_zero(const float rmin[3], const float rmax[3])
+{
+    return rmin[0] == 0.0f || rmax[0] == 0.0f || rmin[1] == 0.0f || rmax[1] == 0.0f || rmin[2] == 0.0f || rmax[2] == 0.0f;
+}
+__device__ __forceinline__ void bvh_note_zeros(const float* t, uint32_t i, const float rmin[3], const float rmax[3], int last[6])
+{
+    const bool any = bvh_any_zero(rmin, rmax);                 // invariant in the caller's loop: without a zero bound a vertex costs one test
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            const float x = t[4 * v + c];
+            if (any && x == 0.0f) {
+                const int s = (int)(i * 3 + v);
+                if (rmin[c] == 0.0f) last[c] = bvh_max(last[c], s);
+                if (rmax[c] == 0.0f) last[3 + c] = bvh_max(last[3 + c], s);
+            }
+        }
+}
+// component c of the bounds: a zero is re-read from the vertex last[] names
+__device__ __forceinline__ void bvh_resolve_zero(const CrtTri* tris, uint32_t first, const int last[6], int c, float rmin[3], float rmax[3])
+{
+    if (rmin[c] == 0.0f && last[c] >= 0) rmin[c] = bvh_tri_f(tris, (size_t)first + last[c] / 3)[4 * (last[c] % 3) + c];
+    if (rmax[c] == 0.0f && last[3 + c] >= 0) rmax[c] = bvh_tri_f(tris, (size_t)first + last[3 + c] / 3)[4 * (last[3 + c] % 3) + c];
+}
+
+// Where the partition loop leaves element x of a node of n triangles: the closed form derived in the file header (restated on the
+// CPU by tests/test_oracle_extensions.py). L = number of left-class elements, G = number of holes; rk[x] = rank of a front
+// right-class element among the holes / of a back left-class element in back order, hl = the holes, bl = the back-order indices.
+__device__ __forceinline__ uint32_t bvh_partition_dest(uint32_t x, bool isLeft, uint32_t L, uint32_t G, uint32_t n, const uint32_t* rk, const uint32_t* hl, const uint32_t* bl)
+{
+    const auto backSlot = [&](uint32_t m) { return m == 0 ? 0u : bl[m - 1] + 1u; };   // of front right #m: l_{m-1} + 1, l_0 = -1
+    if (x < L) return isLeft ? x : n - 1 - backSlot(rk[x]);
+    if (isLeft) return hl[rk[x]];
+    return x == L ? n - 1 - backSlot(G) : x - 1;               // the right-class element AT L comes after all G front ones
+}
+
 // BVH.cpp:232-234
 __global__ void crt_bvh_centroids(CrtTri* __restrict__ tris, size_t first, size_t count)
 {
@@ -66,7 +170,7 @@ __global__ void crt_bvh_centroids(CrtTri* __restrict__ tris, size_t first, size_
 }
 
 // The nodes of one level are kept in three compact id lists by size: BIG nodes (> CRT_BVH_SMALL triangles) are cut into chunks of
-// CRT_BVH_CHUNK triangles, one workgroup per chunk (crt_bvh_big_*); MID nodes get one wave each (crt_bvh_bounds_wave, crt_bvh_mid);
+// CRT_BVH_CHUNK triangles, one workgroup per chunk (crt_bvh_big_*); MID nodes get one wave each (crt_bvh_mid);
 // TINY nodes (<= CRT_BVH_TINY triangles -- the bulk of the deep levels: the builder splits down to one or two triangles per leaf) get
 // one THREAD each that replays upstream's sequential code literally (crt_bvh_tiny).
 #ifndef CRT_BVH_SMALL
@@ -94,26 +198,33 @@ __host__ __device__ __forceinline__ unsigned long long bvh_pack_one(int cls)
     return cls == CRT_BVH_CLASS_TINY ? CRT_BVH_PACK_TINY(1) : (cls == CRT_BVH_CLASS_MID ? CRT_BVH_PACK_MID(1) : CRT_BVH_PACK_BIG(1));
 }
 struct CrtBuildLists { uint32_t* list[3]; };   // next level's id lists (device pointers)
+// an undecided node without children and with empty bounds
+__device__ __forceinline__ CrtBuildNode bvh_fresh_node(uint32_t first, uint32_t count, uint32_t mesh, uint32_t depth, uint32_t rightTurns, uint32_t isRight)
+{
+    CrtBuildNode c;
+    c.first = first; c.count = count; c.left = c.right = CRT_BVH_NONE;
+    for (int k = 0; k < 3; ++k) { c.bmin[k] = 1e30f; c.bmax[k] = -1e30f; }
+    c.splitPos = 0.0f; c.axis = 0; c.state = 0; c.mesh = mesh; c.depth = depth; c.rightTurns = rightTurns; c.isRight = isRight;
+    return c;
+}
 // writes the two child records of `node`; `before` = the packed counter before this node's two children were added
 __device__ __forceinline__ void bvh_new_children(CrtBuildNode* nodes, CrtBuildNode& node, uint32_t first, uint32_t L, uint32_t n,
                                                  uint32_t levelEnd, unsigned long long before, const CrtBuildLists& next)
 {
     const uint32_t id = levelEnd + bvh_unpack(before, 0) + bvh_unpack(before, 1) + bvh_unpack(before, 2);
     node.left = id; node.right = id + 1;
-    CrtBuildNode c;
-    c.left = c.right = CRT_BVH_NONE; c.splitPos = 0.0f; c.axis = 0; c.state = 0; c.mesh = node.mesh; c.depth = node.depth + 1; c.rightTurns = node.rightTurns; c.isRight = 0;
-    for (int k = 0; k < 3; ++k) { c.bmin[k] = 1e30f; c.bmax[k] = -1e30f; }
-    c.first = first; c.count = L; nodes[id] = c;
-    c.first = first + L; c.count = n - L; c.rightTurns = node.rightTurns + 1; c.isRight = 1; nodes[id + 1] = c;
+    const uint32_t mesh = node.mesh, depth = node.depth + 1, turns = node.rightTurns;   // read before the stores: `node` is one of `nodes`
+    nodes[id] = bvh_fresh_node(first, L, mesh, depth, turns, 0);
+    nodes[id + 1] = bvh_fresh_node(first + L, n - L, mesh, depth, turns + 1, 1);
     const int cl = bvh_class(L), cr = bvh_class(n - L);
     next.list[cl][bvh_unpack(before, cl)] = id;
     next.list[cr][bvh_unpack(before + bvh_pack_one(cl), cr)] = id + 1;
 }
 
 // wave-level reductions on ordered images / indices
-__device__ __forceinline__ uint32_t bvh_wave_min(uint32_t v) { for (int off = 32; off > 0; off >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64); v = o < v ? o : v; } return v; }
-__device__ __forceinline__ uint32_t bvh_wave_max(uint32_t v) { for (int off = 32; off > 0; off >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64); v = o > v ? o : v; } return v; }
-__device__ __forceinline__ int bvh_wave_max_i(int v) { for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(v, off, 64); v = o > v ? o : v; } return v; }
+__device__ __forceinline__ uint32_t bvh_wave_min(uint32_t v) { for (int off = 32; off > 0; off >>= 1) v = bvh_min((uint32_t)__shfl_xor((int)v, off, 64), v); return v; }
+__device__ __forceinline__ uint32_t bvh_wave_max(uint32_t v) { for (int off = 32; off > 0; off >>= 1) v = bvh_max((uint32_t)__shfl_xor((int)v, off, 64), v); return v; }
+__device__ __forceinline__ int bvh_wave_max_i(int v) { for (int off = 32; off > 0; off >>= 1) v = bvh_max(__shfl_xor(v, off, 64), v); return v; }
 // what one lane wrote (LDS or global) is read by another lane of the same wave after this
 __device__ __forceinline__ void bvh_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); __builtin_amdgcn_wave_barrier(); }
 
@@ -138,24 +249,8 @@ __device__ __forceinline__ void bvh_sweep_lanes(const uint32_t* cnt, const uint3
                 float bmn[3], bmx[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) { bmn[c] = bvh_unordered(bmin[(a * CRT_BVH_BINS + i) * 3 + c]); bmx[c] = bvh_unordered(bmax[(a * CRT_BVH_BINS + i) * 3 + c]); }
-                const bool grow = bmn[0] != 1e30f;           // aabb::grow(aabb) (BVH.cpp:29-37): skipped for an empty box
-                if (i <= p) {
-                    leftSum += c_;
-                    if (grow)
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            lmn[c] = lmn[c] < bmn[c] ? lmn[c] : bmn[c]; lmx[c] = lmx[c] > bmn[c] ? lmx[c] : bmn[c];
-                            lmn[c] = lmn[c] < bmx[c] ? lmn[c] : bmx[c]; lmx[c] = lmx[c] > bmx[c] ? lmx[c] : bmx[c];
-                        }
-                } else {
-                    rightSum += c_;
-                    if (grow)
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            rmn[c] = rmn[c] < bmn[c] ? rmn[c] : bmn[c]; rmx[c] = rmx[c] > bmn[c] ? rmx[c] : bmn[c];
-                            rmn[c] = rmn[c] < bmx[c] ? rmn[c] : bmx[c]; rmx[c] = rmx[c] > bmx[c] ? rmx[c] : bmx[c];
-                        }
-                }
+                if (i <= p) { leftSum += c_; bvh_grow_box(lmn, lmx, bmn, bmx); }
+                else { rightSum += c_; bvh_grow_box(rmn, rmx, bmn, bmx); }
             }
             const float planeCost = (float)leftSum * bvh_area(lmn, lmx) + (float)rightSum * bvh_area(rmn, rmx);
             const float scale = (hi - lo) / (float)CRT_BVH_BINS;
@@ -238,6 +333,20 @@ __device__ __forceinline__ uint32_t bvh_block_sum(uint32_t v, uint32_t* s_red)
     return t;
 }
 
+// What a workgroup of a BIG kernel works on: its node (slot in the level's BIG list, scratch, record, triangle range) and its chunk of it,
+// triangles lo .. hi of the node's n.
+template <class Node, class Big> struct CrtChunk { uint32_t slot; Big& B; Node& node; uint32_t first, n, chunk, lo, hi; };
+template <class Node, class Big>
+__device__ __forceinline__ CrtChunk<Node, Big> bvh_chunk(Node* nodes, const uint32_t* list, Big* big, const uint32_t* chunkNode)
+{
+    const uint32_t k = chunkNode[blockIdx.x];
+    Big& B = big[k];
+    Node& node = nodes[list[k]];
+    const uint32_t first = node.first, n = node.count;
+    const uint32_t chunk = blockIdx.x - B.chunkBase, lo = chunk * CRT_BVH_CHUNK, hi = (lo + CRT_BVH_CHUNK) < n ? (lo + CRT_BVH_CHUNK) : n;
+    return { k, B, node, first, n, chunk, lo, hi };
+}
+
 // level 0: the roots; BIG ones get their slot (mesh order, as the host fills the BIG list) and their chunks
 __global__ void crt_bvh_init_roots(CrtBuildNode* __restrict__ nodes, const uint32_t* __restrict__ meshTriCounts, int numMeshes, uint32_t firstTri,
                                    CrtBigScratch* __restrict__ big, uint32_t* __restrict__ chunkNode)
@@ -245,14 +354,11 @@ __global__ void crt_bvh_init_roots(CrtBuildNode* __restrict__ nodes, const uint3
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     uint32_t cur = firstTri, slot = 0, chunk = 0;
     for (int m = 0; m < numMeshes; ++m) {
-        CrtBuildNode n;
-        n.first = cur; n.count = meshTriCounts[m]; n.left = n.right = CRT_BVH_NONE;
-        for (int c = 0; c < 3; ++c) { n.bmin[c] = 1e30f; n.bmax[c] = -1e30f; }
-        n.splitPos = 0.0f; n.axis = 0; n.state = 0; n.mesh = (uint32_t)m; n.depth = 0; n.rightTurns = 0; n.isRight = 0;
-        nodes[m] = n;
-        cur += meshTriCounts[m];
-        if (bvh_class(n.count) == CRT_BVH_CLASS_BIG) {
-            const uint32_t nch = bvh_chunks(n.count);
+        const uint32_t count = meshTriCounts[m];
+        nodes[m] = bvh_fresh_node(cur, count, (uint32_t)m, 0, 0, 0);
+        cur += count;
+        if (bvh_class(count) == CRT_BVH_CLASS_BIG) {
+            const uint32_t nch = bvh_chunks(count);
             big[slot].chunkBase = chunk; big[slot].nChunks = nch;
             for (uint32_t c = 0; c < nch; ++c) chunkNode[chunk + c] = slot;
             chunk += nch; ++slot;
@@ -268,90 +374,53 @@ __global__ void crt_bvh_big_reset(CrtBigScratch* __restrict__ big, uint32_t coun
     for (int c = 0; c < 3; ++c) { B.bmin[c] = B.cmin[c] = bvh_ordered(1e30f); B.bmax[c] = B.cmax[c] = bvh_ordered(-1e30f); }
     for (int c = 0; c < 6; ++c) B.last[c] = -1;
     B.L = 0; B.G = 0;
-    for (int j = 0; j < 3 * CRT_BVH_BINS; ++j) B.cnt[j] = 0;
-    for (int j = 0; j < 9 * CRT_BVH_BINS; ++j) { B.bbmin[j] = bvh_ordered(1e30f); B.bbmax[j] = bvh_ordered(-1e30f); }
+    bvh_bins_clear(B.cnt, B.bbmin, B.bbmax, 0, 1);
 }
 
 // UpdateNodeBounds (BVH.cpp:54-74) + the centroid range of FindBestSplitPlane (BVH.cpp:108-113): min/max reductions, order-free.
 __global__ void __launch_bounds__(CRT_BVH_BIG_THREADS) crt_bvh_big_bounds(const CrtBuildNode* __restrict__ nodes, const uint32_t* __restrict__ list, CrtBigScratch* __restrict__ big,
                                                                           const uint32_t* __restrict__ chunkNode, const CrtTri* __restrict__ tris)
 {
-    const uint32_t k = chunkNode[blockIdx.x];
-    CrtBigScratch& B = big[k];
-    const CrtBuildNode& node = nodes[list[k]];
-    const uint32_t first = node.first, n = node.count;
-    const uint32_t lo = (blockIdx.x - B.chunkBase) * CRT_BVH_CHUNK, hi = (lo + CRT_BVH_CHUNK) < n ? (lo + CRT_BVH_CHUNK) : n;
+    const auto ch = bvh_chunk(nodes, list, big, chunkNode);
     float mn[3] = { 1e30f, 1e30f, 1e30f }, mx[3] = { -1e30f, -1e30f, -1e30f };
     float cn[3] = { 1e30f, 1e30f, 1e30f }, cx[3] = { -1e30f, -1e30f, -1e30f };
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        const float* t = bvh_tri_f(tris, (size_t)first + i);
+    for (uint32_t i = ch.lo + threadIdx.x; i < ch.hi; i += blockDim.x) {
+        const float* t = bvh_tri_f(tris, (size_t)ch.first + i);
+        bvh_grow_tri(t, mn, mx);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-#pragma unroll
-            for (int v = 0; v < 3; ++v) { const float x = t[4 * v + c]; mn[c] = mn[c] < x ? mn[c] : x; mx[c] = mx[c] > x ? mx[c] : x; }
-            const float ce = t[3 + 4 * c]; cn[c] = cn[c] < ce ? cn[c] : ce; cx[c] = cx[c] > ce ? cx[c] : ce;
-        }
+        for (int c = 0; c < 3; ++c) { const float ce = t[3 + 4 * c]; cn[c] = bvh_min(cn[c], ce); cx[c] = bvh_max(cx[c], ce); }
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const uint32_t a = bvh_wave_min(bvh_ordered(mn[c])), b = bvh_wave_max(bvh_ordered(mx[c]));
         const uint32_t d = bvh_wave_min(bvh_ordered(cn[c])), e = bvh_wave_max(bvh_ordered(cx[c]));
-        if ((threadIdx.x & 63) == 0) { atomicMin(&B.bmin[c], a); atomicMax(&B.bmax[c], b); atomicMin(&B.cmin[c], d); atomicMax(&B.cmax[c], e); }
+        if ((threadIdx.x & 63) == 0) { atomicMin(&ch.B.bmin[c], a); atomicMax(&ch.B.bmax[c], b); atomicMin(&ch.B.cmin[c], d); atomicMax(&ch.B.cmax[c], e); }
     }
 }
 
 // The bins of FindBestSplitPlane (BVH.cpp:115-129): per workgroup in LDS, then one global atomic per non-empty bin word. Also the
-// look-up behind the sign of a zero bound (see crt_bvh_bounds_wave), which needs the finished bounds and reads the same triangles.
+// look-up behind the sign of a zero bound (bvh_note_zeros), which needs the finished bounds and reads the same triangles.
 __global__ void __launch_bounds__(CRT_BVH_BIG_THREADS) crt_bvh_big_bins(const CrtBuildNode* __restrict__ nodes, const uint32_t* __restrict__ list, CrtBigScratch* __restrict__ big,
                                                                         const uint32_t* __restrict__ chunkNode, const CrtTri* __restrict__ tris)
 {
     __shared__ uint32_t s_cnt[3 * CRT_BVH_BINS];
     __shared__ uint32_t s_bmin[9 * CRT_BVH_BINS], s_bmax[9 * CRT_BVH_BINS];
-    const uint32_t k = chunkNode[blockIdx.x];
-    CrtBigScratch& B = big[k];
-    const CrtBuildNode& node = nodes[list[k]];
-    const uint32_t first = node.first, n = node.count;
-    const uint32_t lo = (blockIdx.x - B.chunkBase) * CRT_BVH_CHUNK, hi = (lo + CRT_BVH_CHUNK) < n ? (lo + CRT_BVH_CHUNK) : n;
-    for (int j = threadIdx.x; j < 3 * CRT_BVH_BINS; j += blockDim.x) s_cnt[j] = 0;
-    for (int j = threadIdx.x; j < 9 * CRT_BVH_BINS; j += blockDim.x) { s_bmin[j] = bvh_ordered(1e30f); s_bmax[j] = bvh_ordered(-1e30f); }
+    const auto ch = bvh_chunk(nodes, list, big, chunkNode);
+    CrtBigScratch& B = ch.B;
+    bvh_bins_clear(s_cnt, s_bmin, s_bmax, threadIdx.x, blockDim.x);
     float cmin[3], cmax[3], rmin[3], rmax[3];
-    bool anyZero = false;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         cmin[a] = bvh_unordered(B.cmin[a]); cmax[a] = bvh_unordered(B.cmax[a]);
         rmin[a] = bvh_unordered(B.bmin[a]); rmax[a] = bvh_unordered(B.bmax[a]);
-        anyZero = anyZero || rmin[a] == 0.0f || rmax[a] == 0.0f;
     }
+    const bool anyZero = bvh_any_zero(rmin, rmax);
     __syncthreads();
     int last[6] = { -1, -1, -1, -1, -1, -1 };
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        const float* t = bvh_tri_f(tris, (size_t)first + i);
-        float tmn[3], tmx[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float l = 1e30f, h = -1e30f;
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                const float x = t[4 * v + c]; l = l < x ? l : x; h = h > x ? h : x;
-                if (anyZero && x == 0.0f) {
-                    const int s = (int)(i * 3 + v);
-                    if (rmin[c] == 0.0f) last[c] = last[c] > s ? last[c] : s;
-                    if (rmax[c] == 0.0f) last[3 + c] = last[3 + c] > s ? last[3 + c] : s;
-                }
-            }
-            tmn[c] = l; tmx[c] = h;
-        }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            if (cmax[a] == cmin[a]) continue;
-            const float scale = (float)CRT_BVH_BINS / (cmax[a] - cmin[a]);
-            int b = f2i((t[3 + 4 * a] - cmin[a]) * scale);
-            b = (CRT_BVH_BINS - 1) < b ? (CRT_BVH_BINS - 1) : b;
-            if (b < 0) b = 0;
-            atomicAdd(&s_cnt[a * CRT_BVH_BINS + b], 1u);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { atomicMin(&s_bmin[(a * CRT_BVH_BINS + b) * 3 + c], bvh_ordered(tmn[c])); atomicMax(&s_bmax[(a * CRT_BVH_BINS + b) * 3 + c], bvh_ordered(tmx[c])); }
-        }
+    for (uint32_t i = ch.lo + threadIdx.x; i < ch.hi; i += blockDim.x) {
+        const float* t = bvh_tri_f(tris, (size_t)ch.first + i);
+        bvh_note_zeros(t, i, rmin, rmax, last);
+        bvh_bins_add(s_cnt, s_bmin, s_bmax, t, cmin, cmax);
     }
     if (anyZero)
 #pragma unroll
@@ -372,34 +441,30 @@ __global__ void __launch_bounds__(CRT_BVH_BIG_THREADS) crt_bvh_big_sweep(CrtBuil
                                                                          uint32_t* __restrict__ chunkL)
 {
     __shared__ uint32_t s_red[CRT_BVH_BIG_THREADS / 64];
-    const uint32_t k = chunkNode[blockIdx.x];
-    const CrtBigScratch& B = big[k];
-    CrtBuildNode& node = nodes[list[k]];
-    const uint32_t first = node.first, n = node.count;
-    const uint32_t chunk = blockIdx.x - B.chunkBase;
-    const uint32_t lo = chunk * CRT_BVH_CHUNK, hi = (lo + CRT_BVH_CHUNK) < n ? (lo + CRT_BVH_CHUNK) : n;
+    const auto ch = bvh_chunk(nodes, list, big, chunkNode);
+    const CrtBigScratch& B = ch.B; CrtBuildNode& node = ch.node;
+    const uint32_t first = ch.first, n = ch.n;
     float cmin[3], cmax[3], rmin[3], rmax[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         cmin[c] = bvh_unordered(B.cmin[c]); cmax[c] = bvh_unordered(B.cmax[c]);
         rmin[c] = bvh_unordered(B.bmin[c]); rmax[c] = bvh_unordered(B.bmax[c]);
-        if (rmin[c] == 0.0f && B.last[c] >= 0) rmin[c] = bvh_tri_f(src, (size_t)first + B.last[c] / 3)[4 * (B.last[c] % 3) + c];
-        if (rmax[c] == 0.0f && B.last[3 + c] >= 0) rmax[c] = bvh_tri_f(src, (size_t)first + B.last[3 + c] / 3)[4 * (B.last[3 + c] % 3) + c];
+        bvh_resolve_zero(src, first, B.last, c, rmin, rmax);
     }
     int axis; float splitPos, bestCost;                        // every wave replays the sweep: no broadcast needed
     bvh_sweep_lanes(B.cnt, B.bbmin, B.bbmax, cmin, cmax, threadIdx.x & 63, axis, splitPos, bestCost);
     const float nosplitCost = (float)n * bvh_area(rmin, rmax);
     const bool isLeaf = bestCost >= nosplitCost;
-    if (chunk == 0 && threadIdx.x == 0) {
+    if (ch.chunk == 0 && threadIdx.x == 0) {
         for (int c = 0; c < 3; ++c) { node.bmin[c] = rmin[c]; node.bmax[c] = rmax[c]; }
         node.axis = axis; node.splitPos = splitPos; node.state = isLeaf ? 2u : 1u;
     }
     if (isLeaf) {
-        for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) bvh_copy_tri(dst, (size_t)first + i, src, (size_t)first + i);
+        for (uint32_t i = ch.lo + threadIdx.x; i < ch.hi; i += blockDim.x) bvh_copy_tri(dst, (size_t)first + i, src, (size_t)first + i);
         return;
     }
     uint32_t c = 0;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) c += bvh_centroid(src, (size_t)first + i, axis) < splitPos ? 1u : 0u;
+    for (uint32_t i = ch.lo + threadIdx.x; i < ch.hi; i += blockDim.x) c += bvh_centroid(src, (size_t)first + i, axis) < splitPos ? 1u : 0u;
     c = bvh_block_sum(c, s_red);
     if (threadIdx.x == 0) chunkL[blockIdx.x] = c;
 }
@@ -410,24 +475,21 @@ __global__ void __launch_bounds__(CRT_BVH_BIG_THREADS) crt_bvh_big_count(const C
                                                                          uint32_t* __restrict__ chunkFR, uint32_t* __restrict__ chunkBL)
 {
     __shared__ uint32_t s_red[CRT_BVH_BIG_THREADS / 64];
-    const uint32_t k = chunkNode[blockIdx.x];
-    CrtBigScratch& B = big[k];
-    const CrtBuildNode& node = nodes[list[k]];
-    if (node.state != 1u) return;
-    const uint32_t first = node.first, n = node.count;
-    const uint32_t chunk = blockIdx.x - B.chunkBase;
-    const uint32_t lo = chunk * CRT_BVH_CHUNK, hi = (lo + CRT_BVH_CHUNK) < n ? (lo + CRT_BVH_CHUNK) : n;
-    const int axis = node.axis; const float splitPos = node.splitPos;
+    const auto ch = bvh_chunk(nodes, list, big, chunkNode);
+    CrtBigScratch& B = ch.B;
+    if (ch.node.state != 1u) return;
+    const uint32_t first = ch.first;
+    const int axis = ch.node.axis; const float splitPos = ch.node.splitPos;
     uint32_t l = 0;
     for (uint32_t j = threadIdx.x; j < B.nChunks; j += blockDim.x) l += chunkL[B.chunkBase + j];
     const uint32_t L = bvh_block_sum(l, s_red);
     uint32_t fr = 0, bl = 0;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+    for (uint32_t i = ch.lo + threadIdx.x; i < ch.hi; i += blockDim.x) {
         const bool isLeft = bvh_centroid(src, (size_t)first + i, axis) < splitPos;
         fr += (i < L && !isLeft) ? 1u : 0u; bl += (i >= L && isLeft) ? 1u : 0u;
     }
     fr = bvh_block_sum(fr, s_red); bl = bvh_block_sum(bl, s_red);
-    if (threadIdx.x == 0) { chunkFR[blockIdx.x] = fr; chunkBL[blockIdx.x] = bl; if (chunk == 0) B.L = L; }
+    if (threadIdx.x == 0) { chunkFR[blockIdx.x] = fr; chunkBL[blockIdx.x] = bl; if (ch.chunk == 0) B.L = L; }
 }
 
 // The tables of the closed form (see the header): rank of every right-class element of the front region among the holes and
@@ -439,14 +501,11 @@ __global__ void __launch_bounds__(CRT_BVH_BIG_THREADS) crt_bvh_big_tables(const 
 {
     __shared__ uint32_t s_red[CRT_BVH_BIG_THREADS / 64];
     __shared__ uint32_t s_wave[16];
-    const uint32_t k = chunkNode[blockIdx.x];
-    CrtBigScratch& B = big[k];
-    const CrtBuildNode& node = nodes[list[k]];
-    if (node.state != 1u) return;
-    const uint32_t first = node.first, n = node.count, L = B.L;
-    const uint32_t chunk = blockIdx.x - B.chunkBase;
-    const uint32_t lo = chunk * CRT_BVH_CHUNK, hi = (lo + CRT_BVH_CHUNK) < n ? (lo + CRT_BVH_CHUNK) : n;
-    const int axis = node.axis; const float splitPos = node.splitPos;
+    const auto ch = bvh_chunk(nodes, list, big, chunkNode);
+    CrtBigScratch& B = ch.B;
+    if (ch.node.state != 1u) return;
+    const uint32_t first = ch.first, n = ch.n, L = B.L, chunk = ch.chunk, lo = ch.lo, hi = ch.hi;
+    const int axis = ch.node.axis; const float splitPos = ch.node.splitPos;
     uint32_t* rk = rank + (first - poolFirst); uint32_t* hl = holes + (first - poolFirst); uint32_t* bl = backL + (first - poolFirst);
     uint32_t gb = 0, ga = 0, bb = 0;                           // holes in earlier chunks / in all chunks; back-order left-class elements in later chunks
     for (uint32_t j = threadIdx.x; j < B.nChunks; j += blockDim.x) {
@@ -473,8 +532,8 @@ __global__ void __launch_bounds__(CRT_BVH_BIG_THREADS) crt_bvh_big_tables(const 
     }
 }
 
-// The move itself (closed form), then -- by the node's first chunk -- the children: two node records, their list slots, and for a BIG
-// child its chunks. A partition that left one side empty (BVH.cpp:194) is only flagged here (state 3): its triangles are copied
+// The move itself (bvh_partition_dest), then -- by the node's first chunk -- the children: two node records, their list slots, and for a
+// BIG child its chunks. A partition that left one side empty (BVH.cpp:194) is only flagged here (state 3): its triangles are copied
 // back by crt_bvh_big_degenerate, which the host launches when the level's control word says there was one.
 __global__ void __launch_bounds__(CRT_BVH_BIG_THREADS) crt_bvh_big_scatter(CrtBuildNode* __restrict__ nodes, const uint32_t* __restrict__ list, const CrtBigScratch* __restrict__ big,
                                                                            const uint32_t* __restrict__ chunkNode, const CrtTri* __restrict__ src, CrtTri* __restrict__ dst, uint32_t poolFirst,
@@ -483,30 +542,20 @@ __global__ void __launch_bounds__(CRT_BVH_BIG_THREADS) crt_bvh_big_scatter(CrtBu
                                                                            CrtBigScratch* __restrict__ nextBig, uint32_t* __restrict__ nextChunkNode)
 {
     __shared__ uint32_t s_fill[2][3];                          // per BIG child: slot, chunkBase, nChunks
-    const uint32_t k = chunkNode[blockIdx.x];
-    const CrtBigScratch& B = big[k];
-    CrtBuildNode& node = nodes[list[k]];
+    const auto ch = bvh_chunk(nodes, list, big, chunkNode);
+    CrtBuildNode& node = ch.node;
     if (node.state != 1u) return;
-    const uint32_t first = node.first, n = node.count, L = B.L, G = B.G;
-    const uint32_t chunk = blockIdx.x - B.chunkBase;
-    const uint32_t lo = chunk * CRT_BVH_CHUNK, hi = (lo + CRT_BVH_CHUNK) < n ? (lo + CRT_BVH_CHUNK) : n;
+    const uint32_t first = ch.first, n = ch.n, L = ch.B.L, G = ch.B.G;
     const int axis = node.axis; const float splitPos = node.splitPos;
     const uint32_t* rk = rank + (first - poolFirst); const uint32_t* hl = holes + (first - poolFirst); const uint32_t* bl = backL + (first - poolFirst);
-    for (uint32_t x = lo + threadIdx.x; x < hi; x += blockDim.x) {
+    for (uint32_t x = ch.lo + threadIdx.x; x < ch.hi; x += blockDim.x) {
         const bool isLeft = bvh_centroid(src, (size_t)first + x, axis) < splitPos;
-        uint32_t dest;
-        if (x < L) {
-            if (isLeft) dest = x;
-            else { const uint32_t m = rk[x]; const uint32_t slot = m == 0 ? 0u : bl[m - 1] + 1u; dest = n - 1 - slot; }
-        } else if (isLeft) dest = hl[rk[x]];
-        else if (x == L) { const uint32_t slot = G == 0 ? 0u : bl[G - 1] + 1u; dest = n - 1 - slot; }
-        else dest = x - 1;
-        bvh_copy_tri(dst, (size_t)first + dest, src, (size_t)first + x);
+        bvh_copy_tri(dst, (size_t)first + bvh_partition_dest(x, isLeft, L, G, n, rk, hl, bl), src, (size_t)first + x);
     }
-    if (chunk != 0) return;
+    if (ch.chunk != 0) return;
     if (L == 0 || L == n) {
         if (threadIdx.x == 0) { atomicAdd(&ctl->degenerate, 1u); }
-        return;                                                // node.state is set by crt_bvh_big_degenerate (other chunks still read it here)
+        return;                                                // node.state is set by crt_bvh_big_degenerate_mark (other chunks still read it here)
     }
     if (threadIdx.x == 0) {
         const int cl = bvh_class(L), cr = bvh_class(n - L);
@@ -532,14 +581,10 @@ __global__ void __launch_bounds__(CRT_BVH_BIG_THREADS) crt_bvh_big_scatter(CrtBu
 __global__ void __launch_bounds__(CRT_BVH_BIG_THREADS) crt_bvh_big_degenerate(CrtBuildNode* __restrict__ nodes, const uint32_t* __restrict__ list, const CrtBigScratch* __restrict__ big,
                                                                               const uint32_t* __restrict__ chunkNode, CrtTri* __restrict__ src, const CrtTri* __restrict__ dst)
 {
-    const uint32_t k = chunkNode[blockIdx.x];
-    const CrtBigScratch& B = big[k];
-    CrtBuildNode& node = nodes[list[k]];
-    const uint32_t first = node.first, n = node.count;
-    if (node.left != CRT_BVH_NONE || (node.state != 1u && node.state != 3u) || !(B.L == 0 || B.L == n)) return;
-    const uint32_t chunk = blockIdx.x - B.chunkBase;
-    const uint32_t lo = chunk * CRT_BVH_CHUNK, hi = (lo + CRT_BVH_CHUNK) < n ? (lo + CRT_BVH_CHUNK) : n;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) bvh_copy_tri(src, (size_t)first + i, dst, (size_t)first + i);
+    const auto ch = bvh_chunk(nodes, list, big, chunkNode);
+    const CrtBuildNode& node = ch.node;
+    if (node.left != CRT_BVH_NONE || (node.state != 1u && node.state != 3u) || !(ch.B.L == 0 || ch.B.L == ch.n)) return;
+    for (uint32_t i = ch.lo + threadIdx.x; i < ch.hi; i += blockDim.x) bvh_copy_tri(src, (size_t)ch.first + i, dst, (size_t)ch.first + i);
 }
 __global__ void crt_bvh_big_degenerate_mark(CrtBuildNode* __restrict__ nodes, const uint32_t* __restrict__ list, const CrtBigScratch* __restrict__ big, uint32_t count)
 {
@@ -556,46 +601,21 @@ __global__ void crt_bvh_big_degenerate_mark(CrtBuildNode* __restrict__ nodes, co
 // 21 candidate planes are evaluated by 21 lanes instead of one thread, and the workgroup's waves share ONE atomic.
 #define CRT_BVH_WAVES 8
 #define CRT_BVH_LDS_TABLE 128         // partition tables of nodes up to this size live in LDS, larger ones in the global scratch
-// UpdateNodeBounds (BVH.cpp:54-74) for the nodes list[0 .. count): min/max reductions per wave.
-// (round 5: called at the top of crt_bvh_mid -- the wave reads its node's triangles for the bins anyway; as a kernel of its own it was 12
-// launches of a 1 M-triangle build. All 64 lanes of the node's wave must call.)
+// UpdateNodeBounds (BVH.cpp:54-74) of one MID node: min/max reductions per wave. All 64 lanes of the node's wave must call.
 __device__ __forceinline__ void bvh_bounds_wave_body(CrtBuildNode& node, const uint32_t first, const uint32_t n, const uint32_t lane, const CrtTri* __restrict__ tris)
 {
     float mn[3] = { 1e30f, 1e30f, 1e30f }, mx[3] = { -1e30f, -1e30f, -1e30f };
-    for (uint32_t i = lane; i < n; i += 64) {
-        const float* t = bvh_tri_f(tris, (size_t)first + i);
-#pragma unroll
-        for (int v = 0; v < 3; ++v)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { const float x = t[4 * v + c]; mn[c] = mn[c] < x ? mn[c] : x; mx[c] = mx[c] > x ? mx[c] : x; }
-    }
+    for (uint32_t i = lane; i < n; i += 64) bvh_grow_tri(bvh_tri_f(tris, (size_t)first + i), mn, mx);
     float rmin[3], rmax[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) { rmin[c] = bvh_unordered(bvh_wave_min(bvh_ordered(mn[c]))); rmax[c] = bvh_unordered(bvh_wave_max(bvh_ordered(mx[c]))); }
-    bool anyZero = false;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) anyZero = anyZero || rmin[c] == 0.0f || rmax[c] == 0.0f;
-    // sign of a zero bound: the sequential fold `acc < x ? acc : x` keeps the LAST zero it meets (tris in order, v0 v1 v2)
-    if (anyZero) {
+    if (bvh_any_zero(rmin, rmax)) {
         int last[6] = { -1, -1, -1, -1, -1, -1 };
-        for (uint32_t i = lane; i < n; i += 64) {
-            const float* t = bvh_tri_f(tris, (size_t)first + i);
+        for (uint32_t i = lane; i < n; i += 64) bvh_note_zeros(bvh_tri_f(tris, (size_t)first + i), i, rmin, rmax, last);
 #pragma unroll
-            for (int v = 0; v < 3; ++v)
+        for (int c = 0; c < 6; ++c) last[c] = bvh_wave_max_i(last[c]);
 #pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    if (t[4 * v + c] == 0.0f) {
-                        const int s = (int)(i * 3 + v);
-                        if (rmin[c] == 0.0f) last[c] = last[c] > s ? last[c] : s;
-                        if (rmax[c] == 0.0f) last[3 + c] = last[3 + c] > s ? last[3 + c] : s;
-                    }
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int a = bvh_wave_max_i(last[c]), b = bvh_wave_max_i(last[3 + c]);
-            if (rmin[c] == 0.0f && a >= 0) rmin[c] = bvh_tri_f(tris, (size_t)first + a / 3)[4 * (a % 3) + c];
-            if (rmax[c] == 0.0f && b >= 0) rmax[c] = bvh_tri_f(tris, (size_t)first + b / 3)[4 * (b % 3) + c];
-        }
+        for (int c = 0; c < 3; ++c) bvh_resolve_zero(tris, first, last, c, rmin, rmax);
     }
     if (lane == 0)
         for (int c = 0; c < 3; ++c) { node.bmin[c] = rmin[c]; node.bmax[c] = rmax[c]; }
@@ -619,44 +639,23 @@ __global__ void __launch_bounds__(64 * CRT_BVH_WAVES) crt_bvh_mid(CrtBuildNode* 
     const uint32_t first = node.first, n = node.count;
     unsigned long long inc = 0; uint32_t L = 0;
     if (live) {
+        uint32_t* cnt = &s_cnt[w][0][0]; uint32_t* bmin = &s_bmin[w][0][0][0]; uint32_t* bmax = &s_bmax[w][0][0][0];   // this wave's bins
         bvh_bounds_wave_body(node, first, n, lane, src);       // lane 0 stores the bounds; the wave syncs below come before anybody reads them
-        for (int j = lane; j < 3 * CRT_BVH_BINS; j += 64) (&s_cnt[w][0][0])[j] = 0;
-        for (int j = lane; j < 9 * CRT_BVH_BINS; j += 64) { (&s_bmin[w][0][0][0])[j] = bvh_ordered(1e30f); (&s_bmax[w][0][0][0])[j] = bvh_ordered(-1e30f); }
+        bvh_bins_clear(cnt, bmin, bmax, lane, 64);
         float cmin[3], cmax[3];
         {
             float mn[3] = { 1e30f, 1e30f, 1e30f }, mx[3] = { -1e30f, -1e30f, -1e30f };
             for (uint32_t i = lane; i < n; i += 64)
 #pragma unroll
-                for (int a = 0; a < 3; ++a) { const float v = bvh_centroid(src, (size_t)first + i, a); mn[a] = mn[a] < v ? mn[a] : v; mx[a] = mx[a] > v ? mx[a] : v; }
+                for (int a = 0; a < 3; ++a) { const float v = bvh_centroid(src, (size_t)first + i, a); mn[a] = bvh_min(mn[a], v); mx[a] = bvh_max(mx[a], v); }
 #pragma unroll
             for (int a = 0; a < 3; ++a) { cmin[a] = bvh_unordered(bvh_wave_min(bvh_ordered(mn[a]))); cmax[a] = bvh_unordered(bvh_wave_max(bvh_ordered(mx[a]))); }
         }
         bvh_wave_sync();
-        for (uint32_t i = lane; i < n; i += 64) {
-            const float* t = bvh_tri_f(src, (size_t)first + i);
-            float tmn[3], tmx[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float lo = 1e30f, hi = -1e30f;
-#pragma unroll
-                for (int v = 0; v < 3; ++v) { const float x = t[4 * v + c]; lo = lo < x ? lo : x; hi = hi > x ? hi : x; }
-                tmn[c] = lo; tmx[c] = hi;
-            }
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                if (cmax[a] == cmin[a]) continue;
-                const float scale = (float)CRT_BVH_BINS / (cmax[a] - cmin[a]);
-                int b = f2i((t[3 + 4 * a] - cmin[a]) * scale);
-                b = (CRT_BVH_BINS - 1) < b ? (CRT_BVH_BINS - 1) : b;
-                if (b < 0) b = 0;
-                atomicAdd(&s_cnt[w][a][b], 1u);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { atomicMin(&s_bmin[w][a][b][c], bvh_ordered(tmn[c])); atomicMax(&s_bmax[w][a][b][c], bvh_ordered(tmx[c])); }
-            }
-        }
+        for (uint32_t i = lane; i < n; i += 64) bvh_bins_add(cnt, bmin, bmax, bvh_tri_f(src, (size_t)first + i), cmin, cmax);
         bvh_wave_sync();
         int axis; float splitPos, bestCost;
-        bvh_sweep_lanes(&s_cnt[w][0][0], &s_bmin[w][0][0][0], &s_bmax[w][0][0][0], cmin, cmax, lane, axis, splitPos, bestCost);
+        bvh_sweep_lanes(cnt, bmin, bmax, cmin, cmax, lane, axis, splitPos, bestCost);
         const float nosplitCost = (float)n * bvh_area(node.bmin, node.bmax);
         const bool isLeaf = bestCost >= nosplitCost;
         if (lane == 0) { node.axis = axis; node.splitPos = splitPos; node.state = isLeaf ? 2u : 1u; }
@@ -695,14 +694,7 @@ __global__ void __launch_bounds__(64 * CRT_BVH_WAVES) crt_bvh_mid(CrtBuildNode* 
             bvh_wave_sync();                                  // tables complete (G == GB by counting)
             for (uint32_t x = lane; x < n; x += 64) {
                 const bool isLeft = bvh_centroid(src, (size_t)first + x, axis) < splitPos;
-                uint32_t dest;
-                if (x < L) {
-                    if (isLeft) dest = x;
-                    else { const uint32_t m = rk[x]; const uint32_t slot = m == 0 ? 0u : bl[m - 1] + 1u; dest = n - 1 - slot; }
-                } else if (isLeft) dest = hl[rk[x]];
-                else if (x == L) { const uint32_t slot = G == 0 ? 0u : bl[G - 1] + 1u; dest = n - 1 - slot; }
-                else dest = x - 1;
-                bvh_copy_tri(dst, (size_t)first + dest, src, (size_t)first + x);
+                bvh_copy_tri(dst, (size_t)first + bvh_partition_dest(x, isLeft, L, G, n, rk, hl, bl), src, (size_t)first + x);
             }
             if (L == 0 || L == n) {                           // BVH.cpp:194: stays a leaf, triangles stay permuted -> both buffers
                 bvh_wave_sync();
@@ -727,16 +719,11 @@ __global__ void __launch_bounds__(64 * CRT_BVH_WAVES) crt_bvh_mid(CrtBuildNode* 
     }
 }
 
-// UpdateNodeBounds for TINY nodes: one thread per node, the sequential fold itself. (round 5: called at the top of crt_bvh_tiny; as a
-// kernel of its own it was 14 launches of a 1 M-triangle build)
+// UpdateNodeBounds for TINY nodes: one thread per node, the sequential fold itself.
 __device__ __forceinline__ void bvh_bounds_tiny_body(CrtBuildNode& node, const CrtTri* __restrict__ tris)
 {
     float mn[3] = { 1e30f, 1e30f, 1e30f }, mx[3] = { -1e30f, -1e30f, -1e30f };
-    for (uint32_t i = 0; i < node.count; ++i) {
-        const float* t = bvh_tri_f(tris, (size_t)node.first + i);
-        for (int c = 0; c < 3; ++c)
-            for (int v = 0; v < 3; ++v) { const float x = t[4 * v + c]; mn[c] = mn[c] < x ? mn[c] : x; mx[c] = mx[c] > x ? mx[c] : x; }
-    }
+    for (uint32_t i = 0; i < node.count; ++i) bvh_grow_tri(bvh_tri_f(tris, (size_t)node.first + i), mn, mx);
     for (int c = 0; c < 3; ++c) { node.bmin[c] = mn[c]; node.bmax[c] = mx[c]; }
 }
 
@@ -755,19 +742,10 @@ __device__ __forceinline__ void bvh_tiny_body(CrtBuildNode* __restrict__ nodes, 
     float tmn[N][3], tmx[N][3];
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-        if ((uint32_t)i < n) {
-            const float* t = bvh_tri_f(src, (size_t)first + i);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float lo = 1e30f, hi = -1e30f;
-#pragma unroll
-                for (int v = 0; v < 3; ++v) { const float x = t[4 * v + c]; lo = lo < x ? lo : x; hi = hi > x ? hi : x; }
-                tmn[i][c] = lo; tmx[i][c] = hi;
-            }
-        } else {
+        if ((uint32_t)i < n) bvh_tri_box(bvh_tri_f(src, (size_t)first + i), tmn[i], tmx[i]);
+        else
 #pragma unroll
             for (int c = 0; c < 3; ++c) { tmn[i][c] = 1e30f; tmx[i][c] = -1e30f; }
-        }
     }
     float bestCost = 1e30f, splitPos = 0.0f; int bestAxis = 0;
 #pragma unroll
@@ -778,17 +756,12 @@ __device__ __forceinline__ void bvh_tiny_body(CrtBuildNode* __restrict__ nodes, 
         for (int i = 0; i < N; ++i) cen[i] = (uint32_t)i < n ? bvh_centroid(src, (size_t)first + i, a) : 0.0f;
 #pragma unroll
         for (int i = 0; i < N; ++i)
-            if ((uint32_t)i < n) { const float v = cen[i]; boundsMin = boundsMin < v ? boundsMin : v; boundsMax = boundsMax > v ? boundsMax : v; }
+            if ((uint32_t)i < n) { boundsMin = bvh_min(boundsMin, cen[i]); boundsMax = bvh_max(boundsMax, cen[i]); }
         if (boundsMax == boundsMin) continue;
         const float scale = (float)CRT_BVH_BINS / (boundsMax - boundsMin);
         int bin[N];
 #pragma unroll
-        for (int i = 0; i < N; ++i) {
-            int b = f2i((cen[i] - boundsMin) * scale);
-            b = (CRT_BVH_BINS - 1) < b ? (CRT_BVH_BINS - 1) : b;
-            if (b < 0) b = 0;
-            bin[i] = (uint32_t)i < n ? b : CRT_BVH_BINS;          // absent triangles are on neither side
-        }
+        for (int i = 0; i < N; ++i) { const int b = bvh_bin_index(cen[i], boundsMin, scale); bin[i] = (uint32_t)i < n ? b : CRT_BVH_BINS; }   // absent triangles are on neither side
         const float pscale = (boundsMax - boundsMin) / (float)CRT_BVH_BINS;
 #pragma unroll
         for (int p = 0; p < CRT_BVH_BINS - 1; ++p) {
@@ -801,8 +774,8 @@ __device__ __forceinline__ void bvh_tiny_body(CrtBuildNode* __restrict__ nodes, 
                 leftCount += isL ? 1 : 0; rightCount += isR ? 1 : 0;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    if (isL) { lmn[c] = lmn[c] < tmn[i][c] ? lmn[c] : tmn[i][c]; lmx[c] = lmx[c] > tmx[i][c] ? lmx[c] : tmx[i][c]; }
-                    if (isR) { rmn[c] = rmn[c] < tmn[i][c] ? rmn[c] : tmn[i][c]; rmx[c] = rmx[c] > tmx[i][c] ? rmx[c] : tmx[i][c]; }
+                    if (isL) { lmn[c] = bvh_min(lmn[c], tmn[i][c]); lmx[c] = bvh_max(lmx[c], tmx[i][c]); }
+                    if (isR) { rmn[c] = bvh_min(rmn[c], tmn[i][c]); rmx[c] = bvh_max(rmx[c], tmx[i][c]); }
                 }
             }
             const float planeCost = (float)leftCount * bvh_area(lmn, lmx) + (float)rightCount * bvh_area(rmn, rmx);
@@ -893,7 +866,7 @@ __global__ void __launch_bounds__(CRT_BVH_SCAN_THREADS) crt_bvh_scan_blocks(uint
 {
     __shared__ uint32_t s_part[CRT_BVH_SCAN_THREADS];
     const uint32_t per = (nb + blockDim.x - 1) / blockDim.x;
-    const uint32_t lo = threadIdx.x * per, hi = (lo + per) < nb ? (lo + per) : nb;
+    const uint32_t lo = threadIdx.x * per, hi = bvh_min(lo + per, nb);
     uint32_t v = 0;
     for (uint32_t i = lo; i < hi; ++i) v += sums[i];
     s_part[threadIdx.x] = v;

@@ -141,7 +141,8 @@ def test_reference_planes_shade_to_the_oracles_primary_only_frame(name, w, h, nt
 def test_every_earlier_kernel_keeps_its_resource_line():
     """tools/kernel_resources.py prints, for every kernel that existed before crt_trace_gbuffer_kernel, the line it printed then
     (tests/golden/kernel_resources_before_gbuffer.txt is its output at that commit), in the same order; what it prints besides are
-    the eight new instantiations."""
+    the eight new instantiations. (Two lines were re-recorded when the BuildBVH kernels were rewritten over shared helpers, both downwards:
+    crt_bvh_big_bins 32 -> 30 VGPRs and 57 -> 55 SGPRs, crt_bvh_big_scatter 54 -> 53 SGPRs.)"""
     import sys
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]

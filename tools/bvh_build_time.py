@@ -37,8 +37,11 @@ with driver.Session(64, 48, device=0) as s:
     nd = np.zeros(used.value, _lib.NODE_DTYPE)
     assert hip.crt_download_bvh_nodes(nd.ctypes.data, 0, nd.nbytes) == 0
     same = used.value == used_h and nd.tobytes() == nodes[:used_h].tobytes()
+    levels, launches = C.c_uint32(0), C.c_uint32(0)
+    hip.crt_debug_build_stats(C.byref(levels), C.byref(launches))
     if os.environ.get("CRT_DEBUG_BVH_REPLAY"):
         print(f"CRT_DEBUG_BVH_REPLAY: build 1 records every level's list sizes ({times[0] * 1e3:.2f} ms, the shipped path), builds 2.. enqueue all launches back to back "
               f"from the recording, no publish kernel, no host wait per level: {', '.join(f'{t * 1e3:.2f}' for t in times[1:])} ms; nodes identical to the host builder's: {same}")
     print(f"{name}: {len(tris)} triangles in {len(c)} meshes -> {used.value} nodes (host {used_h}); host BuildBVH {t_host * 1e3:.1f} ms, "
-          f"crt_build_bvh {best * 1e3:.1f} ms (incl. relayout for rendering); whole load_scene {t_load * 1e3:.0f} ms")
+          f"crt_build_bvh {best * 1e3:.1f} ms (incl. relayout for rendering) in {levels.value} levels, {launches.value} launches; whole load_scene {t_load * 1e3:.0f} ms; "
+          f"nodes identical to the host builder's: {same}")

@@ -229,6 +229,8 @@ struct LaneCounters {
     uint32_t shadowRays, shadowHits;      // CRT_RENDER_SHADOWS only
     uint32_t culled;                      // instance visits the sphere cull answered (counted in traversals/pops/innerVisits as upstream's one pop + one root visit)
 };
+// n instance visits answered by the sphere cull: each is the one pop + one root visit upstream spends on it
+__device__ __forceinline__ void count_culled(LaneCounters& lc, uint32_t n) { lc.traversals += n; lc.pops += n; lc.innerVisits += n; lc.culled += n; }
 
 // kernel_main.cl:108-117
 __device__ __forceinline__ float intersect_aabb(v3 o, v3 inv, float4 bmin, float4 bmax, float minSoFar)
@@ -561,7 +563,7 @@ __device__ __forceinline__ unsigned long long candidate_mask(const CrtDevScene& 
         const bool cull = (bs.w >= 0.0f) && ((oc2 * dd - b * b > r2 * dd) || (b < 0.0f && oc2 > r2));
         if (!cull) cand |= 1ull << k;
     }
-    if (COUNT && !DEFER_COUNT) { const uint32_t culled = cnt - (uint32_t)__popcll(cand); lc.traversals += culled; lc.pops += culled; lc.innerVisits += culled; lc.culled += culled; }
+    if (COUNT && !DEFER_COUNT) { const uint32_t culled = cnt - (uint32_t)__popcll(cand); count_culled(lc, culled); }
     return cand;
 }
 
@@ -671,7 +673,7 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
         const bool fits = tlas_candidates(S, o, d, stack, listed);
         if (__ballot(!fits) == 0) {
             int prev = -1;                                        // last instance entered (ANYHIT + COUNT: culled ones in between)
-            if (COUNT && !ANYHIT) { const uint32_t culled = S.numInstances - listed; lc.traversals += culled; lc.pops += culled; lc.innerVisits += culled; lc.culled += culled; }
+            if (COUNT && !ANYHIT) { const uint32_t culled = S.numInstances - listed; count_culled(lc, culled); }
             bool done = false;
             for (;;) {
                 const bool wEnter = !done && !T.active;
@@ -682,9 +684,9 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
                     const uint32_t k = (ANYHIT && c.anyHit) ? 0xFFFFu : candidate_list_next(stack, prev);
                     if (k == 0xFFFFu) {
                         done = true;
-                        if (COUNT && ANYHIT && !c.anyHit) { const uint32_t n = S.numInstances - (uint32_t)(prev + 1); lc.traversals += n; lc.pops += n; lc.innerVisits += n; lc.culled += n; }
+                        if (COUNT && ANYHIT && !c.anyHit) { const uint32_t n = S.numInstances - (uint32_t)(prev + 1); count_culled(lc, n); }
                     } else {
-                        if (COUNT && ANYHIT) { const uint32_t n = k - (uint32_t)(prev + 1); lc.traversals += n; lc.pops += n; lc.innerVisits += n; lc.culled += n; }
+                        if (COUNT && ANYHIT) { const uint32_t n = k - (uint32_t)(prev + 1); count_culled(lc, n); }
                         prev = (int)k;
                         T.template enter<STK::kTop>(S, k, o, d, c.distance, lc);
                     }
@@ -712,7 +714,7 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
                 if (ANYHIT && c.anyHit) done = true;           // occluded: later instances are never visited
                 else if (cand == 0) {                          // this lane is finished with the chunk
                     done = true;
-                    if (COUNT && ANYHIT) { const uint32_t n = (uint32_t)__popcll(culledLeft); lc.traversals += n; lc.pops += n; lc.innerVisits += n; lc.culled += n; culledLeft = 0; }
+                    if (COUNT && ANYHIT) { const uint32_t n = (uint32_t)__popcll(culledLeft); count_culled(lc, n); culledLeft = 0; }
                 } else {
                     if (ITERS) { if (first_active_lane()) lc.traversals++; }
                     const uint32_t k = (uint32_t)__ffsll((long long)cand) - 1u;
@@ -720,7 +722,7 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
                     if (COUNT && ANYHIT) {
                         const unsigned long long below = culledLeft & ((1ull << k) - 1ull);
                         const uint32_t n = (uint32_t)__popcll(below);
-                        lc.traversals += n; lc.pops += n; lc.innerVisits += n; lc.culled += n; culledLeft &= ~below;
+                        count_culled(lc, n); culledLeft &= ~below;
                     }
                     T.template enter<STK::kTop>(S, base + k, o, d, c.distance, lc);
                 }

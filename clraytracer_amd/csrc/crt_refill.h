@@ -199,7 +199,7 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
                 const unsigned long long cand = candidate_mask<false>(S, ps.o, ps.d, 0u, cnt, none);
                 if (cand == 0 && S.numInstances <= 64u) {
                     // no instance can be hit: closest_hit would return the initial miss (kernel_main.cl:219-224: skybox, break)
-                    if (COUNT) { lc.rays++; lc.primary++; lc.misses++; lc.traversals += cnt; lc.pops += cnt; lc.innerVisits += cnt; lc.culled += cnt; }
+                    if (COUNT) { lc.rays++; lc.primary++; lc.misses++; count_culled(lc, cnt); }
                     (void)shade_bounce(S, no_hit(), ps, 0, F.lightY, F.lightZ);
                     out[(size_t)py * (size_t)F.width + (size_t)px] = make_float4(ps.result.x, ps.result.y, ps.result.z, 1.0f);
                 } else listed = true;

@@ -55,14 +55,14 @@ const char* crt_error_string(int code)
 
 int crt_row_owner(int row, int bandRows, int nRanks)
 {
-    if (row < 0 || bandRows < CRT_TILE || bandRows % CRT_TILE != 0 || nRanks < 1) return CRT_E_BAD_ARGUMENT;
+    if (row < 0 || !valid_bands(bandRows, 0, nRanks)) return CRT_E_BAD_ARGUMENT;
     return (row / bandRows) % nRanks;
 }
 
 // pure: the block list a rank's gather / read-back copies (needs no device; tests/test_distributed.py)
 int crt_band_plan(int height, int bandRows, int rank, int nRanks, int out[4])
 {
-    if (!out || height < 0 || bandRows < CRT_TILE || bandRows % CRT_TILE != 0 || nRanks < 1 || rank < 0 || rank >= nRanks) return CRT_E_BAD_ARGUMENT;
+    if (!out || height < 0 || !valid_bands(bandRows, rank, nRanks)) return CRT_E_BAD_ARGUMENT;
     const BandPlan p = band_plan(height, bandRows, rank, nRanks);
     out[0] = p.firstRow; out[1] = p.fullBands; out[2] = p.tailRow; out[3] = p.tailRows;
     return CRT_OK;

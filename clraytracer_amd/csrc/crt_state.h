@@ -283,6 +283,8 @@ int alloc_frame_buffers(int w, int h)
 // The rows rank `rank` of `nRanks` owns, as one strided block list: `fullBands` bands of `bandRows` rows starting at row
 // `firstRow` and repeating every bandRows * nRanks rows, plus `tailRows` rows of a last, partial band at row `tailRow`.
 struct BandPlan { int firstRow, fullBands, tailRow, tailRows; };
+// what every caller of band_plan has to hold: bands of whole tile rows, and `rank` one of `nRanks`
+bool valid_bands(int bandRows, int rank, int nRanks) { return bandRows >= CRT_TILE && bandRows % CRT_TILE == 0 && nRanks >= 1 && rank >= 0 && rank < nRanks; }
 BandPlan band_plan(int height, int bandRows, int rank, int nRanks)
 {
     BandPlan p = { rank * bandRows, 0, 0, 0 };

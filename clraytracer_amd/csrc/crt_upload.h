@@ -10,10 +10,19 @@ const char* crt1_device_name(void) { return g.deviceName; }
 
 int crt1_upload_texels(const void* rgb8, size_t byteOffset, size_t bytes);
 
-static int init_impl(int device, int width, int height)
+// an integer / a float / an on-off switch (0 = off, any other number = on) from the environment; `dflt` when the variable is not set
+int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+float env_float(const char* name, float dflt) { const char* e = getenv(name); return e ? (float)atof(e) : dflt; }
+bool env_on(const char* name, bool dflt) { const char* e = getenv(name); return e ? atoi(e) != 0 : dflt; }
+
+// the values of CRT_KERNEL ("default" first: the error text lists them in this order)
+const struct { const char* name; Form form; } kKernelForms[] = {
+    { "default", Form::Mega }, { "wavefront", Form::Wavefront }, { "refill", Form::Refill }, { "block", Form::Block }, { "ldstop", Form::LdsTop } };
+
+// ---- the steps of init_impl; a failure leaves a half-built State for the caller's destroy_group / release_all ----
+
+int open_device(int device)
 {
-    if (g.initialized) return CRT_E_BAD_ARGUMENT;
-    if (width < 16 || height < 16) return CRT_E_BAD_ARGUMENT;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return CRT_E_NO_DEVICE;
     if (device < 0 || device >= n) return CRT_E_BAD_ARGUMENT;
@@ -22,10 +31,16 @@ static int init_impl(int device, int width, int height)
     HIPCHK(hipGetDeviceProperties(&prop, device));
     snprintf(g.deviceName, sizeof g.deviceName, "%s (%s, %d CUs)", prop.name, prop.gcnArchName, prop.multiProcessorCount);
     g.device = device;
-    // frames in flight: 3 by default; more pays when a frame is small against its slowest tile (a rank's 1/8 share of a
-    // frame: DESIGN.md 6). Each slot has its own stream; past four the runtime needs GPU_MAX_HW_QUEUES raised before
-    // its first call, or it folds the streams onto four hardware queues (crt_init_devices does that when it still can).
-    { const char* e = getenv("CRT_FRAMES_IN_FLIGHT"); g.nSlots = e ? atoi(e) : 3; if (g.nSlots < 1) g.nSlots = 1; if (g.nSlots > CRT_MAX_FRAMES_IN_FLIGHT) g.nSlots = CRT_MAX_FRAMES_IN_FLIGHT; }
+    g.numCUs = prop.multiProcessorCount;
+    return CRT_OK;
+}
+
+// frames in flight: 3 by default; more pays when a frame is small against its slowest tile (a rank's 1/8 share of a
+// frame: DESIGN.md 6). Each slot has its own stream; past four the runtime needs GPU_MAX_HW_QUEUES raised before
+// its first call, or it folds the streams onto four hardware queues (crt_init_devices does that when it still can).
+int create_frame_slots()
+{
+    g.nSlots = std::min(std::max(env_int("CRT_FRAMES_IN_FLIGHT", 3), 1), CRT_MAX_FRAMES_IN_FLIGHT);
     for (int si = 0; si < g.nSlots; ++si) {
         FrameSlot& fs = g.slot[si];
         HIPCHK(hipStreamCreateWithFlags(&fs.stream, hipStreamNonBlocking));
@@ -36,15 +51,17 @@ static int init_impl(int device, int width, int height)
         HIPCHK(hipMalloc(&fs.devInstances, CRT_MAX_INSTANCES * sizeof(CrtDevInstance)));
         HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&fs.staging), kStageBytes, hipHostMallocDefault));
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&fs.stagingDev), fs.staging, 0));     // the refresh kernel reads the pinned block itself
-        HIPCHK(hipEventCreateWithFlags(&fs.staged, hipEventDisableTiming));
+        for (hipEvent_t* ev : { &fs.staged, &fs.partDone, &fs.slotDone }) HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
         HIPCHK(hipEventRecord(fs.staged, fs.stream));
-        HIPCHK(hipEventCreateWithFlags(&fs.partDone, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&fs.slotDone, hipEventDisableTiming));
         fs.instVersion = 0;
     }
     HIPCHK(hipEventCreate(&g.statStart));
     g.stream = g.slot[0].stream; g.cur = 0; g.asyncSeq = 0; g.othersBusy = false;
+    return CRT_OK;
+}
 
+int alloc_pools()
+{
     g.triCap = (size_t)CRT_MAX_TRIANGLES * 2;           // ResourceManager.cpp:158
     g.nodeCap = (size_t)CRT_MAX_TRIANGLES * 2;          // ResourceManager.cpp:159 (MAX_BVHMEMORY * 2)
     g.texelByteCap = CRT_MAX_TEXTURE_BYTES * 2;         // ResourceManager.cpp:163
@@ -69,37 +86,44 @@ static int init_impl(int device, int width, int height)
     HIPCHK(hipMalloc(&g.err, sizeof(int)));
     HIPCHK(hipMalloc(&g.triReachBits, sizeof(uint32_t)));
     HIPCHK(hipMemset(g.triReachBits, 0, sizeof(uint32_t)));
-    {   // the "never cull" bounds table of frames whose rays start beyond the cull's proven range
-        static float4 never[CRT_MAX_INSTANCES];
-        for (float4& b : never) b = make_float4(0.f, 0.f, 0.f, -1.0f);
-        HIPCHK(hipMalloc(&g.noCullBounds, sizeof never));
-        HIPCHK(hipMemcpy(g.noCullBounds, never, sizeof never, hipMemcpyHostToDevice));
+    // the "never cull" bounds table of frames whose rays start beyond the cull's proven range
+    static float4 never[CRT_MAX_INSTANCES];
+    for (float4& b : never) b = make_float4(0.f, 0.f, 0.f, -1.0f);
+    HIPCHK(hipMalloc(&g.noCullBounds, sizeof never));
+    HIPCHK(hipMemcpy(g.noCullBounds, never, sizeof never, hipMemcpyHostToDevice));
+    return CRT_OK;
+}
+
+int read_environment()
+{
+    // CRT_KERNEL: the Trace kernel structure of this session. Unset / "" / "default": the megakernel (faster);
+    // "wavefront", "refill", "block": the opt-in compaction forms, "ldstop": tree tops staged in LDS. Anything else is a typo, not a wish for
+    // the default: the session refuses to start, so a form's test cannot pass on the megakernel because the name stopped matching.
+    const char* e = getenv("CRT_KERNEL");
+    const auto* form = std::begin(kKernelForms);
+    while (e && *e && form != std::end(kKernelForms) && strcmp(e, form->name) != 0) ++form;
+    if (form == std::end(kKernelForms)) {
+        fprintf(stderr, "crt_init: CRT_KERNEL=%s is not one of ", e);
+        for (const auto& k : kKernelForms) fprintf(stderr, "%s%s", k.name, &k + 1 == std::end(kKernelForms) ? "\n" : ", ");
+        return CRT_E_BAD_ARGUMENT;
     }
-    g.numCUs = prop.multiProcessorCount;
-    {   // CRT_KERNEL: the Trace kernel structure of this session. Unset / "" / "default": the megakernel (faster);
-        // "wavefront", "refill", "block": the opt-in compaction forms, "ldstop": tree tops staged in LDS. Anything else is a typo, not a wish for
-        // the default: the session refuses to start, so a form's test cannot pass on the megakernel because the name stopped matching.
-        const char* e = getenv("CRT_KERNEL");
-        g.form = Form::Mega;
-        if (e && *e && strcmp(e, "default") != 0) {
-            if (strcmp(e, "wavefront") == 0) g.form = Form::Wavefront;
-            else if (strcmp(e, "ldstop") == 0) g.form = Form::LdsTop;
-            else if (strcmp(e, "refill") == 0) g.form = Form::Refill;
-            else if (strcmp(e, "block") == 0) g.form = Form::Block;
-            else { fprintf(stderr, "crt_init: CRT_KERNEL=%s is not one of default, wavefront, refill, block, ldstop\n", e); return CRT_E_BAD_ARGUMENT; }
-        }
-    }
-    { const char* e = getenv("CRT_SPLIT_BETA"); g.splitBeta = e ? (float)atof(e) : CRT_SPLIT_BETA; }
-    { const char* e = getenv("CRT_SPLIT_BETA_ASYNC"); g.splitBetaAsync = e ? (float)atof(e) : CRT_SPLIT_BETA_ASYNC; }
-    { const char* e = getenv("CRT_COST_SPREAD"); g.costSpread = e ? (float)atof(e) : 0.8f; }
-    { const char* e = getenv("CRT_SPLIT");               // tuning knob: cap on quadrant-split tiles per XCD (both modes)
-      if (e) { int v = atoi(e); v = v < 0 ? 0 : (v > CRT_MAX_SPLIT ? CRT_MAX_SPLIT : v); g.maxSplit = g.maxSplitPipelined = v; }
-      else { g.maxSplit = CRT_MAX_SPLIT; g.maxSplitPipelined = CRT_MAX_SPLIT_PIPELINED; } }
-    { const char* e = getenv("CRT_GATHER_RGBA8"); g.gather8 = !(e && atoi(e) == 0); }
+    g.form = form->form;
+    g.splitBeta = env_float("CRT_SPLIT_BETA", CRT_SPLIT_BETA);
+    g.splitBetaAsync = env_float("CRT_SPLIT_BETA_ASYNC", CRT_SPLIT_BETA_ASYNC);
+    g.costSpread = env_float("CRT_COST_SPREAD", 0.8f);
+    const char* split = getenv("CRT_SPLIT");            // tuning knob: cap on quadrant-split tiles per XCD (both modes)
+    g.maxSplit = split ? std::min(std::max(atoi(split), 0), CRT_MAX_SPLIT) : CRT_MAX_SPLIT; g.maxSplitPipelined = split ? g.maxSplit : CRT_MAX_SPLIT_PIPELINED;
+    g.gather8 = env_on("CRT_GATHER_RGBA8", true);
     { const char* e = getenv("CRT_TLAS"); g.forceTlas = e ? (atoi(e) != 0 ? 1 : 0) : -1; }
-    { const char* e = getenv("CRT_STAGGER_US"); g.staggerUs = e ? atoi(e) : -1; }
-    { const char* e = getenv("CRT_FEEDBACK"); g.feedback = !(e && atoi(e) == 0); }
-    { const char* e = getenv("CRT_FEEDBACK_ASYNC"); g.feedbackAsync = (e && atoi(e) != 0); }
+    g.staggerUs = env_int("CRT_STAGGER_US", -1);
+    g.feedback = env_on("CRT_FEEDBACK", true);
+    g.feedbackAsync = env_on("CRT_FEEDBACK_ASYNC", false);
+    return CRT_OK;
+}
+
+// the empty scene: no nodes, roots, instances or texels, every mesh's root reference an empty leaf
+int reset_scene()
+{
     HIPCHK(hipMemset(g.roots, 0, CRT_MAX_MESHES * sizeof(uint32_t)));
     { std::vector<uint32_t> e(CRT_MAX_MESHES, crt_empty_ref((uint32_t)g.triCap)); HIPCHK(hipMemcpy(g.rootRefs, e.data(), e.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(g.topRootRefs, e.data(), e.size() * sizeof(uint32_t), hipMemcpyHostToDevice)); }
@@ -110,9 +134,20 @@ static int init_impl(int device, int width, int height)
     memset(g.hInstances, 0, sizeof g.hInstances); memset(g.hRoots, 0, sizeof g.hRoots);
     memset(g.hHaveRoot, 0, sizeof g.hHaveRoot); g.instVersion = 1;
     rebuild_instance_master();
+    return CRT_OK;
+}
+
+static int init_impl(int device, int width, int height)
+{
+    if (g.initialized) return CRT_E_BAD_ARGUMENT;
+    if (width < 16 || height < 16) return CRT_E_BAD_ARGUMENT;
+    RCCHK(open_device(device));
+    RCCHK(create_frame_slots());
+    RCCHK(alloc_pools());
+    RCCHK(read_environment());
+    RCCHK(reset_scene());
     g.bandRows = 16; g.rank = 0; g.nRanks = 1;
-    int rc = alloc_frame_buffers(width, height);
-    if (rc) return rc;
+    RCCHK(alloc_frame_buffers(width, height));
     g.initialized = true;
     // default white / black texels (ResourceManager.cpp:168-177)
     const unsigned char def[6] = { 0xFF, 0xFF, 0xFF, 0, 0, 0 };
@@ -157,28 +192,30 @@ int crt1_resize(int width, int height)
 int crt1_set_row_bands(int bandRows, int rank, int nRanks)
 {
     if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (bandRows < CRT_TILE || bandRows % CRT_TILE != 0 || nRanks < 1 || rank < 0 || rank >= nRanks) return CRT_E_BAD_ARGUMENT;
+    if (!valid_bands(bandRows, rank, nRanks)) return CRT_E_BAD_ARGUMENT;
     RCCHK(sync_all());
     g.bandRows = bandRows; g.rank = rank; g.nRanks = nRanks;
     return CRT_OK;
 }
 
-
 int crt1_owned_rows(void)
 {
     if (!g.initialized) return 0;
-    int rows = 0;
-    const int tpb = g.bandRows / CRT_TILE;
-    for (int y = 0; y < g.height; ++y) if ((((y / CRT_TILE) / tpb) % g.nRanks) == g.rank) ++rows;
-    return rows;
+    const BandPlan p = band_plan(g.height, g.bandRows, g.rank, g.nRanks);
+    return p.fullBands * g.bandRows + p.tailRows;
 }
+
+// The prologue of every upload and read-back of a pool, in this order: no session; nothing to do (CRT_OK); no buffer, or `first` / `count` not whole
+// multiples of `unit`; beyond the pool's `cap` (first, count and cap in the same units: bytes where unit is a record's size, else elements).
+#define SPANCHK(p, first, count, unit, cap) do { \
+    if (!g.initialized) return CRT_E_NOT_INITIALIZED; \
+    if ((count) == 0) return CRT_OK; \
+    if (!(p) || (first) % (unit) || (count) % (unit)) return CRT_E_BAD_ARGUMENT; \
+    if ((first) + (count) > (cap)) return CRT_E_OUT_OF_RANGE; } while (0)
 
 int crt1_upload_triangles(const void* tris, size_t byteOffset, size_t bytes)
 {
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (bytes == 0) return CRT_OK;
-    if (!tris || byteOffset % sizeof(CrtTri) || bytes % sizeof(CrtTri)) return CRT_E_BAD_ARGUMENT;
-    if (byteOffset + bytes > g.triCap * sizeof(CrtTri)) return CRT_E_OUT_OF_RANGE;
+    SPANCHK(tris, byteOffset, bytes, sizeof(CrtTri), g.triCap * sizeof(CrtTri));
     RCCHK(quiesce());
     HIPCHK(hipMemcpyAsync(reinterpret_cast<char*>(g.rawTris) + byteOffset, tris, bytes, hipMemcpyHostToDevice, g.stream));
     const size_t first = byteOffset / sizeof(CrtTri), count = bytes / sizeof(CrtTri);
@@ -211,10 +248,7 @@ int crt1_upload_triangles(const void* tris, size_t byteOffset, size_t bytes)
 
 int crt1_upload_bvh_nodes(const void* nodes, size_t byteOffset, size_t bytes)
 {
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (bytes == 0) return CRT_OK;
-    if (!nodes || byteOffset % sizeof(CrtBVHNode) || bytes % sizeof(CrtBVHNode)) return CRT_E_BAD_ARGUMENT;
-    if (byteOffset + bytes > g.nodeCap * sizeof(CrtBVHNode)) return CRT_E_OUT_OF_RANGE;
+    SPANCHK(nodes, byteOffset, bytes, sizeof(CrtBVHNode), g.nodeCap * sizeof(CrtBVHNode));
     RCCHK(quiesce());
     HIPCHK(hipMemcpyAsync(reinterpret_cast<char*>(g.rawNodes) + byteOffset, nodes, bytes, hipMemcpyHostToDevice, g.stream));
     const uint32_t high = (uint32_t)((byteOffset + bytes) / sizeof(CrtBVHNode));
@@ -224,10 +258,7 @@ int crt1_upload_bvh_nodes(const void* nodes, size_t byteOffset, size_t bytes)
 
 int crt1_upload_bvh_roots(const uint32_t* roots, size_t firstMesh, size_t count)
 {
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (count == 0) return CRT_OK;
-    if (!roots) return CRT_E_BAD_ARGUMENT;
-    if (firstMesh + count > CRT_MAX_MESHES) return CRT_E_OUT_OF_RANGE;
+    SPANCHK(roots, firstMesh, count, 1, CRT_MAX_MESHES);
     RCCHK(quiesce());
     HIPCHK(hipMemcpyAsync(g.roots + firstMesh, roots, count * sizeof(uint32_t), hipMemcpyHostToDevice, g.stream));
     memcpy(g.hRoots + firstMesh, roots, count * sizeof(uint32_t));
@@ -235,36 +266,21 @@ int crt1_upload_bvh_roots(const uint32_t* roots, size_t firstMesh, size_t count)
     return rebuild_bvh_layout();
 }
 
-int crt1_upload_materials(const void* materials, size_t first, size_t count)
+// a range of a fixed table of `elem`-byte records, `cap` of them
+int upload_table(void* table, size_t elem, size_t cap, const void* src, size_t first, size_t count)
 {
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (count == 0) return CRT_OK;
-    if (!materials) return CRT_E_BAD_ARGUMENT;
-    if (first + count > CRT_MAX_MATERIALS) return CRT_E_OUT_OF_RANGE;
+    SPANCHK(src, first, count, 1, cap);
     RCCHK(quiesce());
-    HIPCHK(hipMemcpyAsync(g.materials + first, materials, count * sizeof(CrtMaterial), hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(static_cast<char*>(table) + first * elem, src, count * elem, hipMemcpyHostToDevice, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
     return CRT_OK;
 }
-
-int crt1_upload_texture_table(const void* textures, size_t count)
-{
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (count == 0) return CRT_OK;
-    if (!textures) return CRT_E_BAD_ARGUMENT;
-    if (count > CRT_MAX_TEXTURES) return CRT_E_OUT_OF_RANGE;
-    RCCHK(quiesce());
-    HIPCHK(hipMemcpyAsync(g.textures, textures, count * sizeof(CrtTexture), hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    return CRT_OK;
-}
+int crt1_upload_materials(const void* materials, size_t first, size_t count) { return upload_table(g.materials, sizeof(CrtMaterial), CRT_MAX_MATERIALS, materials, first, count); }
+int crt1_upload_texture_table(const void* textures, size_t count) { return upload_table(g.textures, sizeof(CrtTexture), CRT_MAX_TEXTURES, textures, 0, count); }
 
 int crt1_upload_texels(const void* rgb8, size_t byteOffset, size_t bytes)
 {
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (bytes == 0) return CRT_OK;
-    if (!rgb8) return CRT_E_BAD_ARGUMENT;
-    if (byteOffset + bytes > g.texelByteCap) return CRT_E_OUT_OF_RANGE;
+    SPANCHK(rgb8, byteOffset, bytes, 1, g.texelByteCap);
     RCCHK(quiesce());
     HIPCHK(hipMemcpyAsync(g.rawTexels + byteOffset, rgb8, bytes, hipMemcpyHostToDevice, g.stream));
     if (byteOffset + bytes > g.texelBytesHigh) g.texelBytesHigh = byteOffset + bytes;
@@ -281,10 +297,7 @@ int crt1_upload_texels(const void* rgb8, size_t byteOffset, size_t bytes)
 
 int crt1_upload_instances(const void* instances, size_t first, size_t count)
 {
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (count == 0) return CRT_OK;
-    if (!instances) return CRT_E_BAD_ARGUMENT;
-    if (first + count > CRT_MAX_INSTANCES) return CRT_E_OUT_OF_RANGE;
+    SPANCHK(instances, first, count, 1, CRT_MAX_INSTANCES);
     const CrtMeshInstance* in = static_cast<const CrtMeshInstance*>(instances);
     for (size_t i = 0; i < count; ++i) if (in[i].meshIndex >= CRT_MAX_MESHES) return CRT_E_BAD_ARGUMENT;
     // host only: frames already submitted keep the tables they were submitted with, every later frame (on whichever
@@ -297,34 +310,19 @@ int crt1_upload_instances(const void* instances, size_t first, size_t count)
 
 // Read back the reference-layout pools (after crt1_build_bvh: the reordered triangles with their centroids, the nodes,
 // the roots), e.g. to keep host arenas in step with the device.
-int crt1_download_triangles(void* dst, size_t byteOffset, size_t bytes)
+int download_pool(void* dst, const void* pool, size_t unit, size_t cap, size_t byteOffset, size_t bytes)
 {
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (bytes == 0) return CRT_OK;
-    if (!dst || byteOffset % sizeof(CrtTri) || bytes % sizeof(CrtTri)) return CRT_E_BAD_ARGUMENT;
-    if (byteOffset + bytes > g.triCap * sizeof(CrtTri)) return CRT_E_OUT_OF_RANGE;
+    SPANCHK(dst, byteOffset, bytes, unit, cap * unit);
     RCCHK(sync_all());
-    HIPCHK(hipMemcpy(dst, reinterpret_cast<const char*>(g.rawTris) + byteOffset, bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dst, static_cast<const char*>(pool) + byteOffset, bytes, hipMemcpyDeviceToHost));
     return CRT_OK;
 }
-
-int crt1_download_bvh_nodes(void* dst, size_t byteOffset, size_t bytes)
-{
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (bytes == 0) return CRT_OK;
-    if (!dst || byteOffset % sizeof(CrtBVHNode) || bytes % sizeof(CrtBVHNode)) return CRT_E_BAD_ARGUMENT;
-    if (byteOffset + bytes > g.nodeCap * sizeof(CrtBVHNode)) return CRT_E_OUT_OF_RANGE;
-    RCCHK(sync_all());
-    HIPCHK(hipMemcpy(dst, reinterpret_cast<const char*>(g.rawNodes) + byteOffset, bytes, hipMemcpyDeviceToHost));
-    return CRT_OK;
-}
+int crt1_download_triangles(void* dst, size_t byteOffset, size_t bytes) { return download_pool(dst, g.rawTris, sizeof(CrtTri), g.triCap, byteOffset, bytes); }
+int crt1_download_bvh_nodes(void* dst, size_t byteOffset, size_t bytes) { return download_pool(dst, g.rawNodes, sizeof(CrtBVHNode), g.nodeCap, byteOffset, bytes); }
 
 int crt1_download_bvh_roots(uint32_t* dst, size_t firstMesh, size_t count)
 {
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (count == 0) return CRT_OK;
-    if (!dst) return CRT_E_BAD_ARGUMENT;
-    if (firstMesh + count > CRT_MAX_MESHES) return CRT_E_OUT_OF_RANGE;
+    SPANCHK(dst, firstMesh, count, 1, CRT_MAX_MESHES);
     RCCHK(sync_all());
     HIPCHK(hipMemcpy(dst, g.roots + firstMesh, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return CRT_OK;

@@ -107,6 +107,8 @@ def test_band_plan_partitions_every_frame():
                     rows = [first + k * band * n + j for k in range(full) for j in range(band)] + [tail_row + j for j in range(tail_rows)]
                     assert all(0 <= y < height and hip.crt_row_owner(y, band, n) == r for y in rows), (height, band, n, r)
                     seen[rows] += 1
+                    # the closed form crt_owned_rows computes from the plan (the entry point itself needs a session: not called here)
+                    assert full * band + tail_rows == sum(hip.crt_row_owner(y, band, n) == r for y in range(height)), (height, band, n, r)
                 assert (seen == 1).all(), (height, band, n)
     assert hip.crt_band_plan(100, 12, 0, 2, (C.c_int * 4)()) != 0          # band height must be a multiple of the tile height
 

@@ -6,7 +6,6 @@ import ctypes as C
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,7 +13,7 @@ import pytest
 from clraytracer_amd import _lib, driver, scenes
 import gbuffer_ref
 import oracle_lib
-from util import bits
+from util import bits, kernel_resource_rows, kernel_resources, resource_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
@@ -75,21 +74,7 @@ def test_session_surface_without_a_device():
 
 @pytest.mark.skipif(not os.path.exists(HIPCC) or shutil.which("c++filt") is None, reason="needs hipcc and c++filt")
 def test_gbuffer_instantiations_keep_the_plain_kernels_budget():
-    flags = re.search(r"^HIPFLAGS = (.*)$", open(os.path.join(ROOT, "Makefile")).read(), re.M).group(1)
-    flags = flags.replace("$(ARCH)", "gfx950").split()
-    cmd = [HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "clraytracer_amd/csrc/crt_shim.hip"), "-o", os.devnull]
-    p = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    rows, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"remark: +Function Name: (\S+)", line)
-        if m:
-            name = subprocess.run(["c++filt", m.group(1)], stdout=subprocess.PIPE, text=True).stdout.strip()
-            cur = rows.setdefault(re.sub(r"\(.*", "", name).replace("void ", ""), {})
-            continue
-        m = re.search(r"remark: +([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+    rows = kernel_resources()
     gb = {k: v for k, v in rows.items() if k.startswith("crt_trace_gbuffer_kernel<")}
     assert len(gb) == 8, sorted(rows)
     for name, r in gb.items():
@@ -143,10 +128,7 @@ def test_every_earlier_kernel_keeps_its_resource_line():
     (tests/golden/kernel_resources_before_gbuffer.txt is its output at that commit), in the same order; what it prints besides are
     the eight new instantiations. (Two lines were re-recorded when the BuildBVH kernels were rewritten over shared helpers, both downwards:
     crt_bvh_big_bins 32 -> 30 VGPRs and 57 -> 55 SGPRs, crt_bvh_big_scatter 54 -> 53 SGPRs.)"""
-    import sys
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    now = p.stdout.splitlines()
+    now = [resource_line(name, r) for name, r in kernel_resource_rows()]
     before = open(os.path.join(ROOT, "tests", "golden", "kernel_resources_before_gbuffer.txt")).read().splitlines()
     assert len(before) == 86
     assert [l for l in now if not l.startswith("crt_trace_gbuffer_kernel<")] == before

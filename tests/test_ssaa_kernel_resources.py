@@ -4,9 +4,10 @@ and the C wrapper of Renderer::SetSupersampling is bound."""
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
+
+from util import kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
@@ -14,21 +15,7 @@ HIPCC = "/opt/rocm/bin/hipcc"
 
 @pytest.mark.skipif(not os.path.exists(HIPCC) or shutil.which("c++filt") is None, reason="needs hipcc and c++filt")
 def test_ssaa_instantiations_fit_the_plain_kernels_budget():
-    flags = re.search(r"^HIPFLAGS = (.*)$", open(os.path.join(ROOT, "Makefile")).read(), re.M).group(1)
-    flags = flags.replace("$(ARCH)", "gfx950").split()
-    cmd = [HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "clraytracer_amd/csrc/crt_shim.hip"), "-o", os.devnull]
-    p = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    rows, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"remark: +Function Name: (\S+)", line)
-        if m:
-            name = subprocess.run(["c++filt", m.group(1)], stdout=subprocess.PIPE, text=True).stdout.strip()
-            cur = rows.setdefault(re.sub(r"\(.*", "", name).replace("void ", ""), {})
-            continue
-        m = re.search(r"remark: +([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+    rows = kernel_resources()
     plain = {k: v for k, v in rows.items() if k.startswith("crt_trace_ssaa_kernel<false,")}
     counted = {k: v for k, v in rows.items() if k.startswith("crt_trace_ssaa_kernel<true,")}
     assert len(plain) == 8 and len(counted) == 8, sorted(rows)

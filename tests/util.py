@@ -1,5 +1,14 @@
 """Shared helpers for the parity tests."""
+import importlib.util
+import os
+
 import numpy as np
+
+# tools/ is no package: the resource compile (one per process, memoised there) and the tool's line format are imported by path
+_spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "kernel_resources.py"))
+_kernel_resources = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(_kernel_resources)
+kernel_resources, kernel_resource_rows, resource_line = _kernel_resources.kernel_resources, _kernel_resources.kernel_resource_rows, _kernel_resources.resource_line
 
 
 def seeded_rays(scene_arenas, cam_pos, n, seed):

@@ -3,41 +3,71 @@
 VGPRs, AGPRs, scratch bytes per lane, occupancy, LDS bytes. Runs without a GPU (hipcc cross-compiles).
 
     python tools/kernel_resources.py [filter-substring] [-D...]
+
+The tests read the same figures through kernel_resources() / kernel_resource_rows() (tests/util.py imports this file by path): one compile per process.
 """
+import functools
 import os
 import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = "/opt/rocm/bin/hipcc"
+
+
+def kernel_resource_rows(defs=()):
+    """[(demangled kernel name, {remark field: int})] of crt_shim.hip built with the Makefile's HIPFLAGS (+ defs), one entry per remark block in
+    the compiler's order. (The two kernels in an anonymous namespace both demangle to the empty name here: a list keeps both.)"""
+    return _compile(tuple(defs))
+
+
+@functools.lru_cache(maxsize=None)
+def _compile(defs):
+    flags = re.search(r"^HIPFLAGS = (.*)$", open(os.path.join(ROOT, "Makefile")).read(), re.M).group(1)
+    flags = flags.replace("$(ARCH)", "gfx950").split()
+    cmd = [HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "clraytracer_amd/csrc/crt_shim.hip"), "-o", os.devnull] + list(defs)
+    p = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True, timeout=900)
+    if p.returncode:
+        raise RuntimeError(f"hipcc failed ({p.returncode}):\n{p.stderr[-2000:]}")
+    rows, cur = [], None
+    for line in p.stderr.splitlines():
+        m = re.search(r"remark: +Function Name: (\S+)", line)
+        if m:
+            name = subprocess.run(["c++filt", m.group(1)], stdout=subprocess.PIPE, text=True).stdout.strip()
+            cur = {}
+            rows.append((re.sub(r"\(.*", "", name).replace("void ", ""), cur))
+            continue
+        m = re.search(r"remark: +([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = int(m.group(2))
+    return rows
+
+
+def kernel_resources(defs=()):
+    """{demangled kernel name: {remark field: int}} over the same (memoised) compile."""
+    rows = {}
+    for name, r in kernel_resource_rows(defs):
+        rows.setdefault(name, {}).update(r)
+    return rows
+
+
+def resource_line(name, r):
+    return (f"{name:70s} VGPR {r.get('VGPRs', -1):3d} AGPR {r.get('AGPRs', -1):3d} scratch {r.get('ScratchSize', -1):4d} occ {r.get('Occupancy', -1):2d} "
+            f"LDS {r.get('LDS Size', -1):6d} SGPR {r.get('TotalSGPRs', -1):3d} spillV {r.get('VGPRs Spill', -1):3d}")
 
 
 def main():
     flt = [a for a in sys.argv[1:] if not a.startswith("-")]
     defs = [a for a in sys.argv[1:] if a.startswith("-")]
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC",
-           "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "clraytracer_amd/csrc/crt_shim.hip"), "-o", "/dev/null"] + defs
-    p = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
-    if p.returncode:
-        sys.stderr.write(p.stderr)
-        raise SystemExit(p.returncode)
-    cur = None
-    rows = []
-    for line in p.stderr.splitlines():
-        m = re.search(r"remark: +Function Name: (\S+)", line)
-        if m:
-            cur = {"name": m.group(1)}
-            rows.append(cur)
-            continue
-        m = re.search(r"remark: +([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    for r in rows:
-        name = subprocess.run(["c++filt", r["name"]], stdout=subprocess.PIPE, text=True).stdout.strip()
-        name = re.sub(r"\(.*", "", name).replace("void ", "")
-        if flt and not any(f in name for f in flt):
-            continue
-        print(f"{name:70s} VGPR {r.get('VGPRs', -1):3d} AGPR {r.get('AGPRs', -1):3d} scratch {r.get('ScratchSize', -1):4d} occ {r.get('Occupancy', -1):2d} LDS {r.get('LDS Size', -1):6d} SGPR {r.get('TotalSGPRs', -1):3d} spillV {r.get('VGPRs Spill', -1):3d}")
+    try:
+        rows = kernel_resource_rows(defs)
+    except RuntimeError as e:
+        sys.stderr.write(str(e) + "\n")
+        raise SystemExit(1)
+    for name, r in rows:
+        if not flt or any(f in name for f in flt):
+            print(resource_line(name, r))
 
 
 if __name__ == "__main__":

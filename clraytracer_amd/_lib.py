@@ -28,6 +28,15 @@ class CrtTraceArgs(C.Structure):
     _fields_ = [("cameraPos", C.c_float * 3), ("time", C.c_float), ("numMeshes", C.c_uint32), ("sunAngle", C.c_float)]
 
 
+class CrtRayBatch(C.Structure):
+    """A batch of rays on the device for crt_trace_rays (include/crt_types.h): pointers as integers, strides in floats (0 = one value for every ray)."""
+    _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p), ("tmax", C.c_void_p), ("originStride", C.c_uint32), ("dirStride", C.c_uint32),
+                ("n", C.c_uint64)]
+
+
+CRT_RAYS_CLOSEST, CRT_RAYS_OCCLUDED = 0, 1      # crt_trace_rays modes
+
+
 class CrtFrameStats(C.Structure):
     _fields_ = [("frames", C.c_uint64), ("sumMs", C.c_double * 4), ("extentMs", C.c_double), ("firstFrameMs", C.c_double)]
 
@@ -53,7 +62,7 @@ RAYHIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4"
 HITRECORD_DTYPE = np.dtype([("normal", "<f4", 3), ("uv", "<f4", 2), ("distance", "<f4"), ("color", "<u4"), ("index", "<u4")])
 assert TRI_DTYPE.itemsize == 80 and NODE_DTYPE.itemsize == 32 and MATERIAL_DTYPE.itemsize == 16
 assert TEXTURE_DTYPE.itemsize == 16 and INSTANCE_DTYPE.itemsize == 80 and RAYHIT_DTYPE.itemsize == 20
-assert HITRECORD_DTYPE.itemsize == 32
+assert HITRECORD_DTYPE.itemsize == 32 and C.sizeof(CrtRayBatch) == 40
 # the first-hit planes of a CRT_RENDER_GBUFFER frame (include/crt_api.h) and one pixel of all three (CrtGBufferPixel, crt_pick_pixel)
 CRT_RENDER_GBUFFER = 8192        # the crt_render flag
 CRT_GBUFFER_GEOMETRY, CRT_GBUFFER_IDS, CRT_GBUFFER_ALBEDO = 0, 1, 2
@@ -106,6 +115,8 @@ HIP_API = {
     "crt_render": (C.c_int, [C.POINTER(CrtTraceArgs), _fp, _fp, C.c_int]),
     "crt_sync": (C.c_int, []),
     "crt_query_hits": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, _vp]),
+    "crt_trace_rays": (C.c_int, [C.POINTER(CrtRayBatch), C.c_uint32, C.c_int, _vp, _vp]),
+    "crt_debug_rays_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "crt_read_output": (C.c_int, [_vp, _sz]),
     "crt_read_output_rows": (C.c_int, [_vp, C.c_int, C.c_int]),
     "crt_read_output_rgba8": (C.c_int, [_vp, _sz]),
@@ -174,6 +185,7 @@ HOST_API = {
     "crth_set_row_bands": (None, [C.c_int, C.c_int, C.c_int]),
     "crth_render": (C.c_uint, [_f]),
     "crth_map_output": (_vp, []),
+    "crth_trace_rays": (C.c_int, [C.POINTER(CrtRayBatch), C.c_int, _vp, _vp]),
     "crth_last_frame_ms": (C.c_float, []),
     "crth_cpu_raycast": (None, [_vp, _vp, C.c_int, _vp, C.c_int]),
     "crth_cpu_raycast_sse": (None, [_vp, _vp, C.c_int, _vp, C.c_int]),

@@ -287,10 +287,10 @@ __device__ __forceinline__ v3 mat3mul(const float* __restrict__ m, v3 v)
 
 struct Closest { float distance; int hitInstance; int anyHit; Triout hit; };
 // "no hit yet" (kernel_main.cl:189-190): what a ray without a candidate instance ends with, and shade_bounce's skybox case
-__device__ __forceinline__ Closest no_hit()
+__device__ __forceinline__ Closest no_hit(float distance = 99999.0f)
 {
     Closest c;
-    c.distance = 99999.0f; c.hitInstance = 0; c.anyHit = 0;
+    c.distance = distance; c.hitInstance = 0; c.anyHit = 0;
     c.hit.t = 0.0f; c.hit.u = 0.0f; c.hit.v = 0.0f; c.hit.tri = 0;
     return c;
 }
@@ -658,10 +658,16 @@ __device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stac
     }
 }
 
+// best0 (ray queries with a distance bound, crt_rays_kernel): the "closest so far" the loop starts with instead of upstream's 99999 --
+// nothing else changes, `t < out.t` and `tnear < minSoFar` do the rest (a NaN bound fails both: every ray a miss).
+// chunkedOnly (TLAS only, wave-uniform): take the chunked candidate loop although an instance tree exists -- what a wave of the TLAS
+// instantiation does anyway when a lane's candidates do not fit its list; crt_rays_kernel forces it for a wave with an origin beyond
+// the cull's proven range, whose scene then has the all-never bounds table. Both are defaulted and constant for every other caller.
 template <bool COUNT, bool ITERS = false, bool ANYHIT = false, bool TLAS = false, class STK = CrtStack>
-__device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d, const STK& stack, LaneCounters& lc)
+__device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d, const STK& stack, LaneCounters& lc, float best0 = 99999.0f,
+                                               bool chunkedOnly = false)
 {
-    Closest c = no_hit();
+    Closest c = no_hit(best0);
     Traversal<COUNT> T; T.reset();
 
     if constexpr (TLAS) {
@@ -670,7 +676,7 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
         // has more than CRT_TLAS_LIST candidates takes the chunked loop instead.
         static_assert(!TLAS || STK::kLds <= CRT_LDS_SLOTS - CRT_TLAS_PARK, "the candidate list needs CRT_TLAS_PARK parked slots");
         uint32_t listed = 0;
-        const bool fits = tlas_candidates(S, o, d, stack, listed);
+        const bool fits = !chunkedOnly && tlas_candidates(S, o, d, stack, listed);    // (chunkedOnly: no lane "fits", the wave takes the loop below)
         if (__ballot(!fits) == 0) {
             int prev = -1;                                        // last instance entered (ANYHIT + COUNT: culled ones in between)
             if (COUNT && !ANYHIT) { const uint32_t culled = S.numInstances - listed; count_culled(lc, culled); }

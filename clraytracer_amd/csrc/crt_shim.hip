@@ -3,13 +3,14 @@
 // Replaces the OpenCL side of the reference's Renderer.cpp / ResourceManager.cpp: device pools,
 // uploads, the per-frame RayGen -> Trace -> PostProcess launch (Renderer.cpp:305-375). Uploads
 // arrive in the reference's struct layouts and are re-laid-out on the device (crt_device.h).
-// One translation unit; the parts (round 5 split what used to be one 2,000-line file):
+// One translation unit (and crt_rays.hip, the ray-query kernel, beside it); the parts (round 5 split what used to be one 2,000-line file):
 //   kernels     crt_device.h (traversal + shading), crt_kernels.h (launches), crt_refill.h (opt-in in-wave compaction forms), crt_ldstop.h (opt-in: tree tops staged in LDS),
-//               crt_relayout.h (upload-time layouts), crt_bvh_build.h (device BuildBVH)
+//               crt_relayout.h (upload-time layouts), crt_bvh_build.h (device BuildBVH); crt_rays.h declares the ray-query kernel of the second unit, crt_rays.hip
 //   host state  crt_state.h (State / FrameSlot, helpers), crt_instances.h (instance tables, cull bounds, instance tree)
 //   entry impl  crt_upload.h (init, uploads, read-backs), crt_bvh_driver.h (crt_build_bvh), crt_frame.h (crt_render and what a frame
 //               needs), crt_multidev.h (several devices behind the same calls)
-// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared
+// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared crt_shim.hip crt_rays.hip (the Makefile's rule; a library of this unit alone links
+// but does not load: crt_frame.h refers to the kernels crt_rays.hip defines)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -20,6 +21,7 @@
 #include "crt_kernels.h"
 #include "crt_refill.h"
 #include "crt_ldstop.h"
+#include "crt_rays.h"
 #include "crt_relayout.h"
 #include "crt_bvh_build.h"
 #include <vector>
@@ -291,6 +293,14 @@ int crt_sync(void) { ON_ALL(crt1_sync()); }
 // reads go to the primary, which holds the gathered frame -- after every device has drained
 static int drain_secondaries() { for (int d = 1; d < M.n; ++d) { Use u(d); const int r = crt1_sync(); if (r != CRT_OK) return r; } return CRT_OK; }
 int crt_query_hits(const float* origins, const float* dirs, int n, uint32_t numInstances, CrtRayHit* out) { ON_PRIMARY(crt1_query_hits(origins, dirs, n, numInstances, out)); }
+// rays on the device belong to one GPU: refused in a session of several, before any device's state changes
+int crt_trace_rays(const CrtRayBatch* rays, uint32_t numInstances, int mode, void* out, void* stream)
+{
+    NEED_SESSION();
+    if (M.n > 1) return CRT_E_UNSUPPORTED;
+    ON_PRIMARY(crt1_trace_rays(rays, numInstances, mode, out, static_cast<hipStream_t>(stream)));
+}
+int crt_debug_rays_stats(uint64_t out[3]) { ON_PRIMARY(crt1_debug_rays_stats(out)); }
 int crt_read_output(float* dst, size_t floats) { NEED_SESSION(); RCCHK(drain_secondaries()); ON_PRIMARY(crt1_read_output(dst, floats)); }
 int crt_read_output_rows(float* dst, int row0, int rows) { NEED_SESSION(); RCCHK(drain_secondaries()); ON_PRIMARY(crt1_read_output_rows(dst, row0, rows)); }
 int crt_read_output_rgba8(uint8_t* dst, size_t bytes) { NEED_SESSION(); RCCHK(drain_secondaries()); ON_PRIMARY(crt1_read_output_rgba8(dst, bytes)); }

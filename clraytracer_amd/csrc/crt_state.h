@@ -59,6 +59,21 @@ struct FrameSlot {
     bool frameIs8 = false;
 };
 
+// The context of the ray queries on device buffers (crt_trace_rays, crt_frame.h): queries never touch a frame slot, so they neither wait
+// for the frames in flight nor make them wait. `fs` is used as a frame slot without a frame: its stream (the instance-table refresh
+// runs there), its copy of the instance tables with the staging block and `staged` event (ensure_slot_instances), and its overflow
+// area, one block per workgroup of the persistent grid. One query at a time: every launch makes the caller's stream wait for
+// `raysDone` of the one before (no host wait), and whatever edits shared device state waits for it on the host (quiesce).
+struct QueryContext {
+    FrameSlot fs;
+    bool ready = false;                        // allocated (by the first query)
+    uint32_t* ctl = nullptr;                   // device: [0] chunk counter, [1] chunks traced without the cull (CrtRaysArgs::ctl)
+    hipEvent_t raysDone = nullptr; bool inFlight = false;   // recorded behind the last query on the caller's stream; inFlight: not yet known to be over
+    bool refreshPending = false;               // a table refresh was queued on fs.stream and no raysDone covers it yet (a query that failed behind it): quiesce waits for fs.staged
+    unsigned long long chunks = 0, grid = 0;   // of the last query (crt_debug_rays_stats)
+    int residentPerCU[4] = { 0, 0, 0, 0 };     // hipOccupancyMaxActiveBlocksPerMultiprocessor of crt_rays_kernel<ANYHIT, TLAS>, [2 * ANYHIT + TLAS]; 0 = not asked yet
+};
+
 struct State {
     bool initialized = false;
     int device = -1;
@@ -120,6 +135,8 @@ struct State {
     float4* topPairs = nullptr; uint32_t* topRootRefs = nullptr;   // the tree-top table (CRT_TOP_PAIRS records) and every mesh's entry into it, rebuilt with the BVH layout
     char lastKernel[128] = { 0 };              // crt_debug_last_kernel: the Trace launch(es) of the most recently submitted frame
     char* queryBuf = nullptr; size_t queryBytes = 0;
+    QueryContext rayQuery;                     // crt_trace_rays
+    int raysGridCap = 0;                       // CRT_RAYS_GRID=n: at most n workgroups per query (tests: few waves walking many chunks); 0 = as many as are resident
     void* buildBuf = nullptr; size_t buildBytes = 0;          // crt_build_bvh scratch
     std::vector<CrtBuildCtl> buildReplay; unsigned long long buildReplayKey = 0;   // CRT_DEBUG_BVH_REPLAY (crt_bvh_driver.h): the level records of the last build
     unsigned buildLaunches = 0, buildLevels = 0;   // crt_debug_build_stats: kernel launches and levels of the last crt_build_bvh (before the re-layout)
@@ -171,9 +188,12 @@ template <class T> int grow(T*& p, size_t& cap, size_t count, hipStream_t s)
     return CRT_OK;
 }
 
-// Wait for frames still running on the second slot before anything touches shared device state.
+// Wait for frames still running on the second slot, and for the ray query in flight (it runs on the caller's stream), before anything
+// touches shared device state.
 int quiesce()
 {
+    if (g.rayQuery.inFlight) { HIPCHK(hipEventSynchronize(g.rayQuery.raysDone)); g.rayQuery.inFlight = false; }
+    if (g.rayQuery.refreshPending) { HIPCHK(hipEventSynchronize(g.rayQuery.fs.staged)); g.rayQuery.refreshPending = false; }   // it reads g.rootRefs
     if (g.othersBusy) {
         for (int i = 1; i < g.nSlots; ++i) HIPCHK(hipStreamSynchronize(g.slot[i].stream));
         g.othersBusy = false;

@@ -35,6 +35,21 @@ int open_device(int device)
     return CRT_OK;
 }
 
+// a slot's copy of the instance tables, its staging block and `staged` event, on the slot's stream (a frame slot, or the ray queries' context)
+int create_slot_tables(FrameSlot& fs)
+{
+    HIPCHK(hipMalloc(&fs.instBlock, kStageBytes));         // the slot's instance tables in the staging block's layout (crt_instances.h)
+    fs.instances = reinterpret_cast<CrtMeshInstance*>(fs.instBlock + kStageInst); fs.instBounds = reinterpret_cast<float4*>(fs.instBlock + kStageBounds);
+    fs.alwaysList = reinterpret_cast<uint32_t*>(fs.instBlock + kStageAlways); fs.tlas = reinterpret_cast<CrtTlasNode*>(fs.instBlock + kStageTlas);
+    HIPCHK(hipMalloc(&fs.devInstances, CRT_MAX_INSTANCES * sizeof(CrtDevInstance)));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&fs.staging), kStageBytes, hipHostMallocDefault));
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&fs.stagingDev), fs.staging, 0));     // the refresh kernel reads the pinned block itself
+    HIPCHK(hipEventCreateWithFlags(&fs.staged, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(fs.staged, fs.stream));
+    fs.instVersion = 0;
+    return CRT_OK;
+}
+
 // frames in flight: 3 by default; more pays when a frame is small against its slowest tile (a rank's 1/8 share of a
 // frame: DESIGN.md 6). Each slot has its own stream; past four the runtime needs GPU_MAX_HW_QUEUES raised before
 // its first call, or it folds the streams onto four hardware queues (crt_init_devices does that when it still can).
@@ -44,16 +59,10 @@ int create_frame_slots()
     for (int si = 0; si < g.nSlots; ++si) {
         FrameSlot& fs = g.slot[si];
         HIPCHK(hipStreamCreateWithFlags(&fs.stream, hipStreamNonBlocking));
+        HIPCHK(hipEventCreateWithFlags(&fs.partDone, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&fs.slotDone, hipEventDisableTiming));
         for (EventSet& es : fs.es) for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&es.ev[i]));
-        HIPCHK(hipMalloc(&fs.instBlock, kStageBytes));         // the slot's instance tables in the staging block's layout (crt_instances.h)
-        fs.instances = reinterpret_cast<CrtMeshInstance*>(fs.instBlock + kStageInst); fs.instBounds = reinterpret_cast<float4*>(fs.instBlock + kStageBounds);
-        fs.alwaysList = reinterpret_cast<uint32_t*>(fs.instBlock + kStageAlways); fs.tlas = reinterpret_cast<CrtTlasNode*>(fs.instBlock + kStageTlas);
-        HIPCHK(hipMalloc(&fs.devInstances, CRT_MAX_INSTANCES * sizeof(CrtDevInstance)));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&fs.staging), kStageBytes, hipHostMallocDefault));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&fs.stagingDev), fs.staging, 0));     // the refresh kernel reads the pinned block itself
-        for (hipEvent_t* ev : { &fs.staged, &fs.partDone, &fs.slotDone }) HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(fs.staged, fs.stream));
-        fs.instVersion = 0;
+        RCCHK(create_slot_tables(fs));
     }
     HIPCHK(hipEventCreate(&g.statStart));
     g.stream = g.slot[0].stream; g.cur = 0; g.asyncSeq = 0; g.othersBusy = false;
@@ -118,6 +127,7 @@ int read_environment()
     g.staggerUs = env_int("CRT_STAGGER_US", -1);
     g.feedback = env_on("CRT_FEEDBACK", true);
     g.feedbackAsync = env_on("CRT_FEEDBACK_ASYNC", false);
+    g.raysGridCap = std::max(env_int("CRT_RAYS_GRID", 0), 0);      // crt_trace_rays: cap on the persistent grid (0 = none)
     return CRT_OK;
 }
 
@@ -158,10 +168,16 @@ static int init_impl(int device, int width, int height)
 static void release_all()
 {
     for (FrameSlot& fs : g.slot) if (fs.stream) (void)hipStreamSynchronize(fs.stream);
+    if (g.rayQuery.raysDone) (void)hipEventSynchronize(g.rayQuery.raysDone);      // the last ray query runs on its caller's stream
+    if (g.rayQuery.fs.stream) (void)hipStreamSynchronize(g.rayQuery.fs.stream);
     void* ptrs[] = { g.rawTris, g.rawNodes, g.roots, g.rawTexels, g.pairs, g.triHot, g.triCold, g.bigLeaf, g.rootRefs,
                      g.texels, g.materials, g.textures, g.rays, g.counters, g.err, g.triReachBits, g.topPairs, g.topRootRefs,
-                     g.queryBuf, g.buildBuf, g.buildTris, g.stamps, g.noCullBounds };
-    for (FrameSlot& fs : g.slot) {
+                     g.queryBuf, g.buildBuf, g.buildTris, g.stamps, g.noCullBounds, g.rayQuery.ctl };
+    FrameSlot* slots[CRT_MAX_FRAMES_IN_FLIGHT + 1];
+    for (int i = 0; i < CRT_MAX_FRAMES_IN_FLIGHT; ++i) slots[i] = &g.slot[i];
+    slots[CRT_MAX_FRAMES_IN_FLIGHT] = &g.rayQuery.fs;                      // the ray queries' context owns a slot's tables, overflow area and stream
+    for (FrameSlot* sl : slots) {
+        FrameSlot& fs = *sl;
         void* q[] = { fs.out, fs.aux, fs.blockQueue, fs.wfCount, fs.ovf, fs.lists, fs.mixOrder, fs.packBuf, fs.instBlock, fs.devInstances, fs.gbuf };
         for (void* p : q) if (p) (void)hipFree(p);
         if (fs.staging) (void)hipHostFree(fs.staging);
@@ -174,7 +190,9 @@ static void release_all()
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (g.statStart) (void)hipEventDestroy(g.statStart);
     if (g.buildCtlHost) (void)hipHostFree(g.buildCtlHost);
-    for (FrameSlot& fs : g.slot) {
+    if (g.rayQuery.raysDone) (void)hipEventDestroy(g.rayQuery.raysDone);
+    for (FrameSlot* sl : slots) {
+        FrameSlot& fs = *sl;
         for (EventSet& es : fs.es) for (int i = 0; i < 4; ++i) if (es.ev[i]) (void)hipEventDestroy(es.ev[i]);
         if (fs.stream) (void)hipStreamDestroy(fs.stream);
     }

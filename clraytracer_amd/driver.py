@@ -13,6 +13,25 @@ from . import _lib
 from ._lib import CrtCounters, CrtError, CrtTraceArgs  # noqa: F401 (CrtError is re-exported: driver.CrtError)
 
 
+class RayHits:
+    """The records of Session.trace_rays(mode="closest"): `records` is one (n, 5) int32 tensor on the device holding n CrtRayHit {t, u, v,
+    triIndex, instance}; t, u, v (float32) and tri, instance (int32) are views of its columns. A miss: t = 99999, instance = -1, the rest 0."""
+
+    def __init__(self, records):
+        import torch
+        f = records.view(torch.float32)
+        self.records = records
+        self.t, self.u, self.v = f[:, 0], f[:, 1], f[:, 2]
+        self.tri, self.instance = records[:, 3], records[:, 4]
+
+    def __len__(self):
+        return self.records.shape[0]
+
+    def numpy(self):
+        """The records on the host as _lib.RAYHIT_DTYPE (synchronises with the stream that produced them)."""
+        return self.records.cpu().numpy().view(_lib.RAYHIT_DTYPE).reshape(-1)
+
+
 class Session:
     def __init__(self, width, height, device=0, host_only=False, devices=None):
         """device: one HIP ordinal; devices: a list of ordinals -> several GPUs in this process (Renderer::InitializeDevices;
@@ -21,6 +40,7 @@ class Session:
         self.hip = _lib.hip()
         self.width, self.height = int(width), int(height)
         self.host_only = bool(host_only)
+        self.device = int(devices[0]) if devices is not None else int(device)
         self.scene = None
         if host_only:
             ok = self.h.crth_initialize_host_only(self.width, self.height)
@@ -214,6 +234,60 @@ class Session:
         out = np.zeros(len(o), _lib.RAYHIT_DTYPE)
         _lib.check(self.hip.crt_query_hits(o.ctypes.data, d.ctypes.data, len(o), self.h.crth_num_instances(), out.ctypes.data), "crt_query_hits")
         return out
+
+    # ---- ray queries on device tensors (Renderer::TraceRays -> crt_trace_rays) ----
+    @staticmethod
+    def _ray_array(name, x, width):
+        """(rows, stride in floats) of a float32 tensor of `width`-vectors: (width,) or (1, width) = one value for every ray (stride 0)."""
+        import torch
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+            raise ValueError(f"{name}: a float32 torch tensor is required, not {getattr(x, 'dtype', type(x))}")
+        if width == 1:
+            if x.dim() != 1 or (x.shape[0] > 1 and x.stride(0) != 1):
+                raise ValueError(f"{name}: a contiguous tensor of shape (n,) is required, not shape {tuple(x.shape)}, strides {x.stride()}")
+            return x.shape[0], 1
+        if x.dim() == 1 and x.shape[0] == width and x.stride(0) == 1:
+            return 1, 0
+        if x.dim() != 2 or x.shape[1] != width or x.stride(1) != 1:
+            raise ValueError(f"{name}: shape (n, {width}) with a contiguous last dimension (or ({width},)) is required, not shape {tuple(x.shape)}, strides {x.stride()}")
+        if x.shape[0] == 1 or x.stride(0) == 0:
+            return x.shape[0], 0
+        if x.stride(0) < width:
+            raise ValueError(f"{name}: a row stride of at least {width} floats (or 0) is required, not {x.stride(0)}")
+        return x.shape[0], x.stride(0)
+
+    def trace_rays(self, origins, dirs, tmax=None, mode="closest"):
+        """Closest hit ("closest": a RayHits) or occlusion ("occluded": a torch.bool tensor) of n world-space rays given as float32 torch tensors
+        on the session's device: origins / dirs of shape (n, 3) -- packed, rows of a wider tensor such as x[:, :3] of (n, 4), or (3,) / (1, 3)
+        for one value shared by every ray -- and optionally tmax of shape (n,), the distance bound in units of the direction's length.
+        Enqueued on torch.cuda.current_stream() without synchronising; the result tensors are ordered on that stream like any torch op."""
+        import torch
+        if mode not in ("closest", "occluded"):
+            raise ValueError(f"mode must be 'closest' or 'occluded', not {mode!r}")
+        (no, so), (nd, sd) = self._ray_array("origins", origins, 3), self._ray_array("dirs", dirs, 3)
+        counts = [c for c, st in ((no, so), (nd, sd)) if st != 0 or c == 0]
+        if tmax is not None:
+            counts.append(self._ray_array("tmax", tmax, 1)[0])
+        n = counts[0] if counts else 1
+        if any(c != n for c in counts):
+            raise ValueError(f"origins, dirs and tmax disagree about the number of rays: {counts}")
+        for name, x in (("origins", origins), ("dirs", dirs), ("tmax", tmax)):
+            if x is not None and (x.device.type != "cuda" or x.device.index != self.device):
+                raise ValueError(f"{name}: the tensor is on {x.device}, the session on cuda:{self.device}")
+        dev = torch.device("cuda", self.device)
+        batch = _lib.CrtRayBatch(origins.data_ptr(), dirs.data_ptr(), tmax.data_ptr() if tmax is not None else None, so, sd, n)
+        closest = mode == "closest"
+        out = torch.empty((n, 5), dtype=torch.int32, device=dev) if closest else torch.empty(n, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if not self.h.crth_trace_rays(C.byref(batch), _lib.CRT_RAYS_CLOSEST if closest else _lib.CRT_RAYS_OCCLUDED, out.data_ptr(), stream):
+            self._raise_and_clear("Renderer::TraceRays")
+        return RayHits(out) if closest else out.view(torch.bool)
+
+    def rays_stats(self):
+        """(64-ray chunks, chunks traced without the instance cull, workgroups launched) of the last trace_rays, after waiting for it."""
+        out = (C.c_uint64 * 3)()
+        _lib.check(self.hip.crt_debug_rays_stats(out), "crt_debug_rays_stats")
+        return int(out[0]), int(out[1]), int(out[2])
 
     def set_row_bands(self, band_rows, rank, n_ranks):
         self.h.crth_set_row_bands(int(band_rows), int(rank), int(n_ranks))

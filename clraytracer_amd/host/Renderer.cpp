@@ -224,6 +224,12 @@ bool Renderer::PickPixel(int x, int y, CrtGBufferPixel& out)
     return check(crt_pick_pixel(x, y, &out), "crt_pick_pixel");
 }
 
+bool Renderer::TraceRays(const CrtRayBatch& rays, int mode, void* out, void* stream)
+{
+    if (!deviceReady) { lastError = CRT_E_NOT_INITIALIZED; return false; }
+    return check(crt_trace_rays(&rays, g_NumMeshInstances, mode, out, stream), "crt_trace_rays");
+}
+
 void Renderer::Terminate()
 {
     ResourceManager::Finalize();

@@ -45,6 +45,9 @@ namespace Renderer
     void SetGBuffer(bool enabled);        // extension: Render() also writes the first-hit planes (CRT_RENDER_GBUFFER: normal + distance, instance / triangle / barycentrics, albedo); off by default
     const void* MapGBuffer(int plane);    // host copy of plane CRT_GBUFFER_GEOMETRY / IDS / ALBEDO of the last G-buffer frame (width*height elements), valid until next Render; null without one
     bool PickPixel(int x, int y, CrtGBufferPixel& out); // what that frame's primary ray hit at pixel (x, y): 36 bytes from the device, no ray cast (replaces CPU_RayCast(ScreenPointToRaySSE(mouse)), Engine.cpp:112-126)
+    // extension: closest hit (CRT_RAYS_CLOSEST: CrtRayHit per ray) or occlusion (CRT_RAYS_OCCLUDED: one byte per ray) for a batch of rays on the device
+    // against the registered instances (as last uploaded), enqueued on `stream` (a hipStream_t; null: HIP's null stream) without waiting; false: LastError()
+    bool TraceRays(const CrtRayBatch& rays, int mode, void* out, void* stream = nullptr);
     void SetRefraction(bool enabled);     // extension: upstream's README TODO "refraction / transculency": materials with MTL d < 1 transmit; off by default
     void SetPipelined(bool enabled);      // Render() returns without waiting (frames in flight); MapOutput()/uploads wait. Off by default (upstream clFinish()es)
     void SetTime(float seconds);          // TraceArgs.time (Window::GetTime upstream)

@@ -115,6 +115,12 @@ unsigned crth_render(float sunAngle)
     if (hostOnly) { hostOnlyError = CRT_E_NOT_INITIALIZED; std::fprintf(stderr, "[crth] render requested in a host-only session: there is no CPU render path\n"); return 0; }
     return Renderer::Render(sunAngle);
 }
+int crth_trace_rays(const CrtRayBatch* rays, int mode, void* out, void* stream)
+{
+    if (hostOnly) { hostOnlyError = CRT_E_NOT_INITIALIZED; return 0; }
+    if (!rays) { hostOnlyError = CRT_E_BAD_ARGUMENT; return 0; }      // (reported through crth_last_error like the host-only refusals)
+    return Renderer::TraceRays(*rays, mode, out, stream) ? 1 : 0;
+}
 const float* crth_map_output(void) { return hostOnly ? nullptr : Renderer::MapOutput(); }
 float crth_last_frame_ms(void) { return hostOnly ? -1.0f : Renderer::LastFrameMs(); }
 

@@ -183,8 +183,43 @@ int crt_sync(void);                                           /* wait for every 
 
 /* Closest-hit query for arbitrary world-space rays (host pointers, n rays) against the first
  * `numInstances` instances: the instance loop + IntersectBVH of kernel_main.cl:198-217 exposed for
- * hit-record parity tests. Also fills the work counters. */
+ * hit-record parity tests. Also fills the work counters. (The counted route over host memory; rays on the device: crt_trace_rays.) */
 int crt_query_hits(const float* origins, const float* dirs, int n, uint32_t numInstances, CrtRayHit* out);
+
+/* Ray queries on device buffers (no reference counterpart: upstream's only rays are the camera's): closest hit or occlusion for a
+ * batch of world-space rays that is already on the device, answered on the device -- visibility between points, light-map and
+ * ambient-occlusion baking, range sensors, collision probes. The instance loop + IntersectBVH of kernel_main.cl:124-160, 189-217 with
+ * its own kernel (CRT_KERNEL forms do not apply, as for crt_query_hits), against the first `numInstances` instances.
+ *   rays    CrtRayBatch (crt_types.h): origins / dirs / tmax are device-accessible; strides in floats, 0 = one value for every ray,
+ *           otherwise >= 3. Directions are not normalised: t and tmax are in units of the given direction's length (hazard H6).
+ *   out     device-accessible: CrtRayHit[n] (20 B each) for CRT_RAYS_CLOSEST, uint8_t[n] (0 or 1) for CRT_RAYS_OCCLUDED.
+ *   stream  a hipStream_t; NULL = HIP's null stream (what torch.cuda.current_stream().cuda_stream is for torch's default stream).
+ * Semantics, one definition for both modes: upstream's loop started with a smaller "closest so far". The bound is
+ * B = !(tmax >= 99999.0f) ? tmax : 99999.0f (no tmax array: 99999.0f); besthit.distance starts at B instead of 99999, nothing else
+ * changes. A NaN tmax stays NaN and makes the ray a miss through the loop's own comparisons (t < out.t, tnear < minSoFar).
+ *   CRT_RAYS_CLOSEST   a hit record is exactly crt_query_hits' CrtRayHit {t, u, v, triIndex, instance}; a miss is always
+ *                      {99999.0f, 0, 0, 0, -1}, whatever B was.
+ *   CRT_RAYS_OCCLUDED  1 where the bounded closest-hit query of the same ray reports a hit, else 0 -- exactly, not approximately: the
+ *                      any-hit traversal (as shadow rays use it) and the bounded closest-hit traversal are in identical states until
+ *                      the first triangle passes, and the any-hit traversal stops there.
+ * What is promised: equality with that bounded loop, always; and equality with "the unbounded record (crt_query_hits) if its
+ * t < tmax, else the miss record" whenever the unbounded record's u and v are finite. (The bound may prune a subtree whose degenerate
+ * triangle would have left a NaN u / v in the unbounded loop's arithmetic blend, kernel_main.cl:101-104.)
+ * The call ENQUEUES AND RETURNS: no ray is read on the host, results are valid once `stream` reaches this point. The host waits only
+ * for the first query's allocations and for an overflow area that has to grow. Queries have a context of their own (instance tables,
+ * overflow area): they neither wait for the frames in flight nor delay them; one query runs at a time -- a query's stream waits, on
+ * the device, for the query before it. Whatever waits for the frames in flight also waits, on the host, for the query in flight -- and
+ * so for everything the caller queued ahead of it on `stream`: scene edits (mesh / node / root / material / texture uploads,
+ * crt_build_bvh, crt_resize, crt_set_row_bands, crt_shutdown, crt_sync), the reads (crt_read_output*, crt_read_rays, crt_read_gbuffer,
+ * crt_pick_pixel, crt_download_*), crt_query_hits, and every frame that is not pipelined (a crt_render without CRT_RENDER_ASYNC, or
+ * with a diagnostic flag). Pipelined frames do not wait. crt_upload_instances waits for nothing, and a query submitted after it sees
+ * the new table. A ray origin beyond the cull's proven range (crt_get_cull_range) costs only its own 64-ray chunk the instance cull.
+ * Work counters, crt_get_counters and noCullFrames are not touched. n == 0: CRT_OK, no pointer is looked at. Errors, all before
+ * anything is enqueued: CRT_E_NOT_INITIALIZED; CRT_E_BAD_ARGUMENT (rays, origins, dirs or out NULL; a stride of 1 or 2; an unknown
+ * mode; numInstances > 401; an invalid scene); CRT_E_OUT_OF_RANGE (n > 2^30); CRT_E_UNSUPPORTED (a session of several devices: the
+ * pointers belong to one GPU). CRT_RAYS_GRID=n in the environment (read by crt_init) caps the launch at n workgroups. */
+enum { CRT_RAYS_CLOSEST = 0, CRT_RAYS_OCCLUDED = 1 };
+int crt_trace_rays(const CrtRayBatch* rays, uint32_t numInstances, int mode, void* out, void* stream);
 
 /* Output: the HDR float4 frame (the reference writes a CL-GL RGBA8 texture, Renderer.cpp:63,192). */
 int crt_read_output(float* dstRGBA, size_t floats);           /* full frame, width*height*4 floats */

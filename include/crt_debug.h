@@ -50,6 +50,10 @@ int crt_debug_build_stats(uint32_t* levels, uint32_t* launches);
  * instances is the one it was built for; a median-split build follows when the set changed, when the inner radii have grown by a quarter, or
  * after 256 refits. *builds = builds of this session so far, *refitsSinceBuild, *nodes = nodes of the current tree. */
 int crt_debug_tlas_stats(uint64_t* builds, uint32_t* refitsSinceBuild, uint32_t* nodes);
+/* Diagnostic: the last crt_trace_rays launch, after waiting for it: out = { 64-ray chunks, chunks traced without the instance cull (an
+ * origin beyond the cull's proven range, or NaN), workgroups launched }. The launch is a persistent grid -- min(chunks, CUs x resident
+ * workgroups per CU, CRT_RAYS_GRID) workgroups claim the chunks from a device counter. Zeros before the first query. */
+int crt_debug_rays_stats(uint64_t out[3]);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,18 @@ typedef struct CrtRayHit {
     int32_t instance;                 /* -1: miss */
 } CrtRayHit;
 
+/* A batch of n world-space rays on the device for crt_trace_rays (include/crt_api.h). Strides are in floats: 0 = every ray shares
+ * element 0 (one origin for all rays; one direction for all rays: sun visibility from many points), otherwise >= 3 (3 = packed
+ * xyz triples, 4 = the xyz of float4 rows). */
+typedef struct CrtRayBatch {
+    const float* origins;             /* device-accessible; ray k starts at origins[k * originStride + 0..2] */
+    const float* dirs;                /* device-accessible; dirs[k * dirStride + 0..2], not normalised (t is in units of its length) */
+    const float* tmax;                /* device-accessible, n floats, or NULL = unbounded */
+    uint32_t originStride;
+    uint32_t dirStride;
+    uint64_t n;
+} CrtRayBatch;
+
 /* One pixel of the three first-hit planes of a CRT_RENDER_GBUFFER frame (crt_pick_pixel; crt_api.h describes the planes):
  * hit: record.normal (kernel_main.cl:236), the hit record as CrtRayHit holds it, 0xFF000000 | b << 16 | g << 8 | r of record.color;
  * miss: normal 0, t = 99999, instance -1, everything else 0. */
@@ -115,6 +127,7 @@ static_assert(sizeof(CrtRGB8) == 3, "RGB8 must be 3 B");
 static_assert(sizeof(CrtMeshInstance) == 80, "MeshInstance must be 80 B");
 static_assert(sizeof(CrtTraceArgs) == 24, "TraceArgs must be 24 B");
 static_assert(sizeof(CrtGBufferPixel) == 36, "GBufferPixel must be 36 B (16 + 16 + 4, the three planes)");
+static_assert(sizeof(CrtRayHit) == 20 && sizeof(CrtRayBatch) == 40, "RayHit must be 20 B, RayBatch 40 B");
 #endif
 #endif
 

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Compile crt_shim.hip for gfx950 with -Rpass-analysis=kernel-resource-usage and print one line per kernel:
-VGPRs, AGPRs, scratch bytes per lane, occupancy, LDS bytes. Runs without a GPU (hipcc cross-compiles).
+"""Compile the translation units of libcrt_hip.so (crt_shim.hip, crt_rays.hip) for gfx950 with -Rpass-analysis=kernel-resource-usage and print one
+line per kernel: VGPRs, AGPRs, scratch bytes per lane, occupancy, LDS bytes. Runs without a GPU (hipcc cross-compiles).
 
     python tools/kernel_resources.py [filter-substring] [-D...]
 
-The tests read the same figures through kernel_resources() / kernel_resource_rows() (tests/util.py imports this file by path): one compile per process.
+The tests read the same figures through kernel_resources() / kernel_resource_rows() (tests/util.py imports this file by path): one compile per unit and process.
 """
 import functools
 import os
@@ -14,19 +14,20 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
+SOURCES = ("crt_shim.hip", "crt_rays.hip")     # the Makefile's units of libcrt_hip.so, in link order
 
 
-def kernel_resource_rows(defs=()):
-    """[(demangled kernel name, {remark field: int})] of crt_shim.hip built with the Makefile's HIPFLAGS (+ defs), one entry per remark block in
-    the compiler's order. (The two kernels in an anonymous namespace both demangle to the empty name here: a list keeps both.)"""
-    return _compile(tuple(defs))
+def kernel_resource_rows(defs=(), source=SOURCES[0]):
+    """[(demangled kernel name, {remark field: int})] of one unit (default: crt_shim.hip) built with the Makefile's HIPFLAGS (+ defs), one entry per
+    remark block in the compiler's order. (The two kernels in an anonymous namespace both demangle to the empty name here: a list keeps both.)"""
+    return _compile(tuple(defs), source)
 
 
 @functools.lru_cache(maxsize=None)
-def _compile(defs):
+def _compile(defs, source):
     flags = re.search(r"^HIPFLAGS = (.*)$", open(os.path.join(ROOT, "Makefile")).read(), re.M).group(1)
     flags = flags.replace("$(ARCH)", "gfx950").split()
-    cmd = [HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "clraytracer_amd/csrc/crt_shim.hip"), "-o", os.devnull] + list(defs)
+    cmd = [HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "clraytracer_amd/csrc", source), "-o", os.devnull] + list(defs)
     p = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True, timeout=900)
     if p.returncode:
         raise RuntimeError(f"hipcc failed ({p.returncode}):\n{p.stderr[-2000:]}")
@@ -45,10 +46,11 @@ def _compile(defs):
 
 
 def kernel_resources(defs=()):
-    """{demangled kernel name: {remark field: int}} over the same (memoised) compile."""
+    """{demangled kernel name: {remark field: int}} of every unit of the library, over the same (memoised) compiles."""
     rows = {}
-    for name, r in kernel_resource_rows(defs):
-        rows.setdefault(name, {}).update(r)
+    for source in SOURCES:
+        for name, r in kernel_resource_rows(defs, source):
+            rows.setdefault(name, {}).update(r)
     return rows
 
 
@@ -61,7 +63,7 @@ def main():
     flt = [a for a in sys.argv[1:] if not a.startswith("-")]
     defs = [a for a in sys.argv[1:] if a.startswith("-")]
     try:
-        rows = kernel_resource_rows(defs)
+        rows = [row for source in SOURCES for row in kernel_resource_rows(defs, source)]
     except RuntimeError as e:
         sys.stderr.write(str(e) + "\n")
         raise SystemExit(1)

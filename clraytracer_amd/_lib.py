@@ -117,6 +117,7 @@ HIP_API = {
     "crt_query_hits": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, _vp]),
     "crt_trace_rays": (C.c_int, [C.POINTER(CrtRayBatch), C.c_uint32, C.c_int, _vp, _vp]),
     "crt_debug_rays_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "crt_debug_live_resources": (C.c_int, [C.POINTER(C.c_uint64)]),
     "crt_read_output": (C.c_int, [_vp, _sz]),
     "crt_read_output_rows": (C.c_int, [_vp, C.c_int, C.c_int]),
     "crt_read_output_rgba8": (C.c_int, [_vp, _sz]),

@@ -1,5 +1,5 @@
 // crt_bvh_driver.h -- host driver of the device BuildBVH (kernels: crt_bvh_build.h; reference: BVH.cpp:218-255)
-// Part of the one translation unit crt_shim.hip (included there, in this order: crt_state.h, crt_instances.h, crt_upload.h,
+// Part of the one translation unit crt_shim.hip (included there, in this order: crt_own.h, crt_state.h, crt_instances.h, crt_upload.h,
 // crt_bvh_driver.h, crt_frame.h, crt_multidev.h); everything here has internal linkage.
 #pragma once
 namespace {
@@ -57,8 +57,8 @@ static int validate(BuildCtx& c)
 // build nodes | rank, holes, backL | 2 x 3 id lists | 2 x BIG-node scratch | 2 x chunk->node + 3 per-chunk counts | mesh counts, roots, scalars, control records
 static int carve_scratch(BuildCtx& c)
 {
-    if (!g.buildTris) HIPCHK(hipMalloc(&g.buildTris, g.triCap * sizeof(CrtTri)));
-    if (!g.buildCtlHost) { HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&g.buildCtlHost), sizeof(CrtBuildCtlHost), hipHostMallocMapped | hipHostMallocCoherent)); g.buildCtlHost->seq = 0; g.buildSeq = 0; }
+    if (!g.buildTris) RCCHK(g.buildTris.alloc(g.triCap));
+    if (!g.buildCtlHost) { RCCHK(g.buildCtlHost.alloc(1, hipHostMallocMapped | hipHostMallocCoherent)); g.buildCtlHost->seq = 0; g.buildSeq = 0; }
     const size_t total = c.total, nm = (size_t)c.numMeshes;
     c.maxNodes = 2 * total + nm;
     const size_t listCap = total + nm;                         // a level never has more nodes than triangles
@@ -72,14 +72,8 @@ static int carve_scratch(BuildCtx& c)
     const size_t offBig = bump(2 * c.maxBig * sizeof(CrtBigScratch));
     const size_t offChunks = bump(5 * c.maxChunks * sizeof(uint32_t));
     const size_t offSmall = bump((2 * nm + 8) * sizeof(uint32_t) + kBuildCtlLevels * sizeof(CrtBuildCtl) + 16);
-    const size_t need = off;
-    if (need > g.buildBytes) {
-        if (g.buildBuf) (void)hipFree(g.buildBuf);
-        g.buildBuf = nullptr; g.buildBytes = 0;
-        HIPCHK(hipMalloc(&g.buildBuf, need));
-        g.buildBytes = need;
-    }
-    char* base = static_cast<char*>(g.buildBuf);
+    RCCHK(g.buildBuf.grow(off, g.stream));                     // (the stream is idle: crt1_build_bvh has just waited for it in sync_all)
+    char* base = g.buildBuf;
     c.bn = reinterpret_cast<CrtBuildNode*>(base + offNodes);
     c.rank = reinterpret_cast<uint32_t*>(base + offRank); c.holes = c.rank + total; c.backL = c.holes + total;
     uint32_t* listMem = reinterpret_cast<uint32_t*>(base + offLists);

@@ -1,5 +1,5 @@
 // crt_frame.h -- one frame: feedback launch lists, the Trace launch by kernel structure, frame slots and events (Renderer.cpp:305-375), queries, reads, statistics
-// Part of the one translation unit crt_shim.hip (included there, in this order: crt_state.h, crt_instances.h, crt_upload.h,
+// Part of the one translation unit crt_shim.hip (included there, in this order: crt_own.h, crt_state.h, crt_instances.h, crt_upload.h,
 // crt_bvh_driver.h, crt_frame.h, crt_multidev.h); everything here has internal linkage.
 #pragma once
 namespace {
@@ -18,7 +18,7 @@ static void unpack_counters(const unsigned long long c[CRT_NUM_COUNTERS])
 int collect_set(EventSet& es)
 {
     if (!es.pending) return CRT_OK;
-    hipEvent_t* ev = es.ev;
+    const Event* ev = es.ev;
     hipEvent_t traceStart = es.evRaygen ? ev[1] : ev[0], frameEnd = es.evPost ? ev[3] : ev[2];
     HIPCHK(hipEventSynchronize(frameEnd));
     float ms[4] = { 0, 0, 0, 0 };
@@ -89,8 +89,8 @@ static int prepare_launch_lists(CrtFrame& F, unsigned& grid, FrameSlot& fs, bool
     const int key[7] = { g.width, g.height, g.bandRows, g.rank, g.nRanks, F.slotsPerXcd, F.ss };   // ss: another factor is another tile grid
     F.listCap = F.slotsPerXcd + 3 * CRT_MAX_SPLIT;
     const size_t n = (size_t)8 * (size_t)F.listCap;
-    if (3 * n + 8 > fs.listsCap) fs.orderSlots = -1;     // new memory: start from the identity order
-    RCCHK(grow(fs.lists, fs.listsCap, 3 * n + 8, fs.stream));
+    if (3 * n + 8 > fs.lists.capacity()) fs.orderSlots = -1;     // new memory: start from the identity order
+    RCCHK(fs.lists.grow(3 * n + 8, fs.stream));
     if (fs.orderSlots != F.slotsPerXcd || memcmp(key, fs.orderKey, sizeof key) != 0) {
         HIPCHK(hipMemsetAsync(fs.lists + n, 0, sizeof(uint32_t) * n, fs.stream));
         crt_identity_order_kernel<<<(8 * F.slotsPerXcd + 255) / 256, 256, 0, fs.stream>>>(fs.lists, fs.lists + 3 * n, F.slotsPerXcd, F.listCap);
@@ -121,8 +121,8 @@ static int prepare_mix3_lists(CrtFrame& F, unsigned& grid, FrameSlot& fs)
 {
     const int S = F.slotsPerXcd, S3 = 3 * S;
     const size_t entries = (size_t)8 * S3;
-    if (entries + 8 > fs.mixCap) fs.mixSlots = -1;       // new memory: write the lists
-    RCCHK(grow(fs.mixOrder, fs.mixCap, entries + 8, fs.stream));
+    if (entries + 8 > fs.mixOrder.capacity()) fs.mixSlots = -1;       // new memory: write the lists
+    RCCHK(fs.mixOrder.grow(entries + 8, fs.stream));
     if (fs.mixSlots != S) {
         std::vector<uint32_t> h(entries + 8, (uint32_t)S3);
         for (int x = 0; x < 8; ++x)
@@ -205,7 +205,7 @@ static int launch_trace(FrameCtx& c, float4* out)
     c.fused = true;
     if (c.flags & CRT_RENDER_STAMPS) {   // diagnostic launch with per-wave stamps (megakernel, refill, block): the stamped instantiation applies T.epilogue too
         const size_t words = 16 + (size_t)grid * 8;
-        RCCHK(grow(g.stamps, g.stampCap, words, fs.stream));
+        RCCHK(g.stamps.grow(words, fs.stream));
         g.stampWaves = grid;
         HIPCHK(hipMemsetAsync(g.stamps, 0, words * sizeof(unsigned long long), fs.stream));
         if (g.form == Form::Block) crt_trace_block_kernel<false, true><<<grid, CRT_BLOCK, 0, fs.stream>>>(S, T, out, g.stamps, fs.blockQueue);
@@ -288,12 +288,12 @@ static int prepare_lists(FrameCtx& c)
         set_tile_grid(c.T, c.F.ownedTileRows, (c.F.tilesX + tiles - 1) / tiles);
         c.gridT = (unsigned)c.T.gridBlocks;
         if (feedback) RCCHK(prepare_launch_lists(c.T, c.gridT, fs, c.pipelined, true));
-        if (g.form == Form::Block) RCCHK(grow(fs.blockQueue, fs.blockQueueCap, (size_t)c.T.gridBlocks * CRT_BLOCK_PIXELS, fs.stream));
+        if (g.form == Form::Block) RCCHK(fs.blockQueue.grow((size_t)c.T.gridBlocks * CRT_BLOCK_PIXELS, fs.stream));
         break;
     }
     case Form::Wavefront:                // this slot's queue (64 records per primary wave), counts + offsets + per-XCD totals
-        RCCHK(grow(fs.blockQueue, fs.blockQueueCap, (size_t)c.grid * 64, fs.stream));
-        RCCHK(grow(fs.wfCount, fs.wfCap, (size_t)c.grid * 2 + 8, fs.stream));
+        RCCHK(fs.blockQueue.grow((size_t)c.grid * 64, fs.stream));
+        RCCHK(fs.wfCount.grow((size_t)c.grid * 2 + 8, fs.stream));
         break;
     case Form::LdsTop: ovfBlocks = (size_t)ldstop_grid(c.F) * CRT_TOP_WAVES; break;   // one block per WAVE of the four-wave workgroups
     }
@@ -309,7 +309,7 @@ static bool frame_gathers_rgba8(int flags) { return g.groupSize > 1 && g.gather8
 int crt1_prepare_gather8(void)
 {
     if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    for (int i = 0; i < g.nSlots; ++i) RCCHK(grow(g.slot[i].packBuf, g.slot[i].packCap, (size_t)g.width * (size_t)g.height, g.slot[i].stream));
+    for (int i = 0; i < g.nSlots; ++i) RCCHK(g.slot[i].packBuf.grow((size_t)g.width * (size_t)g.height, g.slot[i].stream));
     return CRT_OK;
 }
 // the float frame of slot `fs` from its byte frame, if the last frame on it was gathered as RGBA8 (the caller has drained the streams)
@@ -464,8 +464,8 @@ static int launch_passes(FrameCtx& c)
     const bool unorm = (c.flags & CRT_RENDER_UNORM8) != 0, post = (c.flags & CRT_RENDER_POSTPROCESS) != 0, fxaa = (c.flags & CRT_RENDER_FXAA) != 0;
     const bool fxaaLocal = fxaa && g.groupSize <= 1;
     const size_t framePixels = (size_t)g.width * (size_t)g.height;
-    if (fxaa && !is_secondary()) RCCHK(grow(fs.aux, fs.auxPixels, framePixels, fs.stream));
-    if (c.flags & CRT_RENDER_GBUFFER) RCCHK(grow(fs.gbuf, fs.gbufBytes, framePixels * CRT_GBUFFER_PIXEL_BYTES, fs.stream));
+    if (fxaa && !is_secondary()) RCCHK(fs.aux.grow(framePixels, fs.stream));
+    if (c.flags & CRT_RENDER_GBUFFER) RCCHK(fs.gbuf.grow(framePixels * CRT_GBUFFER_PIXEL_BYTES, fs.stream));
     if (!fxaa) F.epilogue = (unorm ? CRT_EPILOGUE_QUANTIZE : 0u) | (post ? CRT_EPILOGUE_POST : 0u);
     else if (fxaaLocal) F.epilogue = unorm ? CRT_EPILOGUE_QUANTIZE : 0u;
     // the kernel that stores the final pixel stores its four bytes too: for a read-back of the RGBA8 frame on one device (a
@@ -473,7 +473,7 @@ static int launch_passes(FrameCtx& c)
     // are gathered as bytes
     c.gather8 = frame_gathers_rgba8(c.flags);
     c.packInKernel = unorm && (((c.flags & CRT_RENDER_READBACK) && g.groupSize <= 1) || c.gather8);
-    if (c.packInKernel) RCCHK(grow(fs.packBuf, fs.packCap, framePixels, fs.stream));
+    if (c.packInKernel) RCCHK(fs.packBuf.grow(framePixels, fs.stream));
     if (c.packInKernel && !fxaa) F.packOut = fs.packBuf;
     c.T.epilogue = F.epilogue; c.T.packOut = F.packOut;
     RCCHK(launch_trace(c, fxaaLocal ? fs.aux : fs.out));
@@ -547,16 +547,11 @@ static int finish_frame(const FrameCtx& c)
         const size_t pixels = (size_t)g.width * (size_t)g.height;
         const bool bytes8 = (c.flags & CRT_RENDER_UNORM8) != 0;
         const size_t bytes = pixels * (bytes8 ? 4 : 16);
-        if (bytes > fs.hostCap) {
-            if (fs.hostBuf) (void)hipHostFree(fs.hostBuf);
-            fs.hostBuf = nullptr; fs.hostCap = 0;
-            HIPCHK(hipHostMalloc(&fs.hostBuf, bytes, hipHostMallocDefault));
-            fs.hostCap = bytes;
-        }
-        if (!fs.copied) HIPCHK(hipEventCreateWithFlags(&fs.copied, hipEventDisableTiming));
+        RCCHK(fs.hostBuf.grow(bytes, hipHostMallocDefault));
+        if (!fs.copied) RCCHK(fs.copied.create(hipEventDisableTiming));
         const void* src = fs.out;
         if (bytes8) {
-            RCCHK(grow(fs.packBuf, fs.packCap, pixels, fs.stream));
+            RCCHK(fs.packBuf.grow(pixels, fs.stream));
             // the Trace (or FXAA) kernel stored the bytes already / the byte frame was gathered
             const bool packed = (c.packInKernel && ((c.flags & CRT_RENDER_FXAA) || c.fused)) || c.gather8;
             if (!packed) crt_pack_unorm8_kernel<<<(unsigned)((pixels + 255) / 256), 256, 0, fs.stream>>>(fs.out, fs.packBuf, pixels);
@@ -611,19 +606,14 @@ int crt1_debug_measure_clock(int micros, double* ghz)
 {
     if (!g.initialized) return CRT_E_NOT_INITIALIZED;
     if (!ghz || micros < 1 || micros > 100000) return CRT_E_BAD_ARGUMENT;
-    double* d = nullptr; hipStream_t st = nullptr;
-    HIPCHK(hipMalloc(&d, 8 * sizeof(double)));
-    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    DevBuf<double> d; Stream st;
+    RCCHK(d.alloc(8));
+    RCCHK(st.create(hipStreamNonBlocking));
     double h[8] = { 0 };
-    if (e == hipSuccess) {
-        crt_clock_probe_kernel<<<8, 64, 0, st>>>((unsigned long long)micros * 100ull, d);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (st) (void)hipStreamDestroy(st);
-    (void)hipFree(d);
-    if (e != hipSuccess) return (int)e;
+    crt_clock_probe_kernel<<<8, 64, 0, st>>>((unsigned long long)micros * 100ull, d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     double sum = 0; int n = 0;
     for (double v : h) if (v > 0.0) { sum += v; ++n; }
     *ghz = n ? sum / n : 0.0;
@@ -645,8 +635,8 @@ int crt1_query_hits(const float* origins, const float* dirs, int n, uint32_t num
     RCCHK(collect_timing());
     RCCHK(quiesce());
     const size_t rayBytes = sizeof(float) * 3 * (size_t)n, need = rayBytes * 2 + sizeof(CrtRayHit) * (size_t)n;
-    RCCHK(grow(g.queryBuf, g.queryBytes, need, g.stream));
-    float* dO = reinterpret_cast<float*>(g.queryBuf);
+    RCCHK(g.queryBuf.grow(need, g.stream));
+    float* dO = reinterpret_cast<float*>(static_cast<char*>(g.queryBuf));
     float* dD = dO + 3 * (size_t)n;
     CrtRayHit* dH = reinterpret_cast<CrtRayHit*>(dD + 3 * (size_t)n);
     HIPCHK(hipMemcpyAsync(dO, origins, rayBytes, hipMemcpyHostToDevice, g.stream));
@@ -680,10 +670,10 @@ static int ensure_ray_query_context()
 {
     QueryContext& q = g.rayQuery;
     if (q.ready) return CRT_OK;
-    if (!q.fs.stream) HIPCHK(hipStreamCreateWithFlags(&q.fs.stream, hipStreamNonBlocking));
-    if (!q.fs.instBlock) RCCHK(create_slot_tables(q.fs));
-    if (!q.ctl) HIPCHK(hipMalloc(&q.ctl, 2 * sizeof(uint32_t)));
-    if (!q.raysDone) HIPCHK(hipEventCreateWithFlags(&q.raysDone, hipEventDisableTiming));
+    if (!q.tables.stream) RCCHK(q.tables.stream.create(hipStreamNonBlocking));
+    if (!q.tables.instBlock) RCCHK(create_slot_tables(q.tables));
+    if (!q.ctl) RCCHK(q.ctl.alloc(2));
+    if (!q.raysDone) RCCHK(q.raysDone.create(hipEventDisableTiming));
     q.ready = true;
     return CRT_OK;
 }
@@ -719,7 +709,7 @@ int crt1_trace_rays(const CrtRayBatch* rays, uint32_t numInstances, int mode, vo
     if (rays->n > CRT_RAYS_MAX) return CRT_E_OUT_OF_RANGE;
     RCCHK(ensure_ray_query_context());
     QueryContext& q = g.rayQuery;
-    FrameSlot& fs = q.fs;
+    SlotTables& fs = q.tables;
     const bool anyHit = mode == CRT_RAYS_OCCLUDED;
     if (fs.instVersion != g.instVersion) {      // an instance upload since the last query: refresh behind the query that may still read the old tables
         if (q.inFlight) HIPCHK(hipStreamWaitEvent(fs.stream, q.raysDone, 0));
@@ -734,7 +724,7 @@ int crt1_trace_rays(const CrtRayBatch* rays, uint32_t numInstances, int mode, vo
     uint64_t grid = (uint64_t)g.numCUs * (uint64_t)perCU;
     if (g.raysGridCap > 0 && grid > (uint64_t)g.raysGridCap) grid = (uint64_t)g.raysGridCap;
     if (grid > chunks) grid = chunks;
-    if (grid * CRT_OVF_WORDS_PER_BLOCK > fs.ovfWords) {
+    if (grid * CRT_OVF_WORDS_PER_BLOCK > fs.ovf.capacity()) {
         if (q.inFlight) { HIPCHK(hipEventSynchronize(q.raysDone)); q.inFlight = false; }      // the query before still owns the old area (grow() frees it)
         RCCHK(ensure_overflow(fs, (size_t)grid));
     }
@@ -799,8 +789,8 @@ int crt1_read_output_rgba8(uint8_t* dst, size_t bytes)
         HIPCHK(hipMemcpy(dst, g.slot[g.cur].packBuf, pixels * 4, hipMemcpyDeviceToHost));
         return CRT_OK;
     }
-    RCCHK(grow(g.queryBuf, g.queryBytes, pixels * 4, g.stream));   // shares the query scratch buffer
-    crt_pack_unorm8_kernel<<<(unsigned)((pixels + 255) / 256), 256, 0, g.stream>>>(g.slot[g.cur].out, reinterpret_cast<uint32_t*>(g.queryBuf), pixels);
+    RCCHK(g.queryBuf.grow(pixels * 4, g.stream));   // shares the query scratch buffer
+    crt_pack_unorm8_kernel<<<(unsigned)((pixels + 255) / 256), 256, 0, g.stream>>>(g.slot[g.cur].out, reinterpret_cast<uint32_t*>(static_cast<char*>(g.queryBuf)), pixels);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(dst, g.queryBuf, pixels * 4, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));

@@ -1,5 +1,5 @@
 // crt_instances.h -- everything derived from the instance table and the root nodes: device records, bounding spheres and the cull range, the instance tree, per-slot copies
-// Part of the one translation unit crt_shim.hip (included there, in this order: crt_state.h, crt_instances.h, crt_upload.h,
+// Part of the one translation unit crt_shim.hip (included there, in this order: crt_own.h, crt_state.h, crt_instances.h, crt_upload.h,
 // crt_bvh_driver.h, crt_frame.h, crt_multidev.h); everything here has internal linkage.
 #pragma once
 namespace {
@@ -324,7 +324,7 @@ constexpr size_t kStageTlas = (kStageAlways + CRT_MAX_INSTANCES * sizeof(uint32_
 constexpr size_t kStageBytes = kStageTlas + 2 * CRT_MAX_INSTANCES * sizeof(CrtTlasNode);
 
 // Brings a slot's instance tables up to the host master, on the slot's own stream, before a frame (or query) uses them.
-int ensure_slot_instances(FrameSlot& fs)
+int ensure_slot_instances(SlotTables& fs)
 {
     if (fs.instVersion == g.instVersion) return CRT_OK;
     HIPCHK(hipEventSynchronize(fs.staged));                        // the previous refresh no longer reads the staging block
@@ -336,7 +336,7 @@ int ensure_slot_instances(FrameSlot& fs)
     // reads the pinned block over the link, fills the device block and builds the device records (crt_refresh_instances_kernel)
     static_assert(kStageInst == 0 && kStageBytes % 16 == 0 && kStageTlas % 16 == 0 && sizeof(CrtTlasNode) % 16 == 0, "copied as 16-byte words");
     const uint32_t words16 = (uint32_t)((kStageTlas + g.hTlasNodes * sizeof(CrtTlasNode)) / 16);
-    crt_refresh_instances_kernel<<<16, 256, 0, fs.stream>>>(reinterpret_cast<const uint4*>(fs.stagingDev), reinterpret_cast<uint4*>(fs.instBlock), words16,
+    crt_refresh_instances_kernel<<<16, 256, 0, fs.stream>>>(reinterpret_cast<const uint4*>(fs.stagingDev), reinterpret_cast<uint4*>(static_cast<char*>(fs.instBlock)), words16,
                                                              g.rootRefs, g.topRootRefs, CRT_MAX_INSTANCES, fs.devInstances);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(fs.staged, fs.stream));

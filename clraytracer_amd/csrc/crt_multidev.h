@@ -1,5 +1,5 @@
 // crt_multidev.h -- several devices behind the one C-ABI (crt_init_devices): per-device worker threads, device selection, the dispatch macros
-// Part of the one translation unit crt_shim.hip (included there, in this order: crt_state.h, crt_instances.h, crt_upload.h,
+// Part of the one translation unit crt_shim.hip (included there, in this order: crt_own.h, crt_state.h, crt_instances.h, crt_upload.h,
 // crt_bvh_driver.h, crt_frame.h, crt_multidev.h); everything here has internal linkage.
 #pragma once
 namespace {
@@ -99,6 +99,8 @@ struct Use {
 #define ON_ALL(expr) do { NEED_SESSION(); int rc_ = CRT_OK; for (int d_ = 0; d_ < M.n; ++d_) { Use u_(d_); const int r_ = (expr); if (r_ != CRT_OK && rc_ == CRT_OK) rc_ = r_; } return rc_; } while (0)
 #define ON_PRIMARY(expr) do { NEED_SESSION(); Use u_(0); return (expr); } while (0)
 
+// The only place a State dies. Its owners (crt_own.h) call HIP from their destructors, so the device is selected first; M.dev[] stays a
+// raw pointer so that a process that exits without crt_shutdown runs no HIP call from a static destructor.
 static void destroy_group()
 {
     for (int d = 1; d < M.n; ++d) if (M.worker[d]) { M.worker[d]->stop(); delete M.worker[d]; M.worker[d] = nullptr; }

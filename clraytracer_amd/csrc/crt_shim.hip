@@ -6,7 +6,7 @@
 // One translation unit (and crt_rays.hip, the ray-query kernel, beside it); the parts (round 5 split what used to be one 2,000-line file):
 //   kernels     crt_device.h (traversal + shading), crt_kernels.h (launches), crt_refill.h (opt-in in-wave compaction forms), crt_ldstop.h (opt-in: tree tops staged in LDS),
 //               crt_relayout.h (upload-time layouts), crt_bvh_build.h (device BuildBVH); crt_rays.h declares the ray-query kernel of the second unit, crt_rays.hip
-//   host state  crt_state.h (State / FrameSlot, helpers), crt_instances.h (instance tables, cull bounds, instance tree)
+//   host state  crt_own.h (the owners of device / pinned buffers, events and streams), crt_state.h (State / FrameSlot, helpers), crt_instances.h (instance tables, cull bounds, instance tree)
 //   entry impl  crt_upload.h (init, uploads, read-backs), crt_bvh_driver.h (crt_build_bvh), crt_frame.h (crt_render and what a frame
 //               needs), crt_multidev.h (several devices behind the same calls)
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared crt_shim.hip crt_rays.hip (the Makefile's rule; a library of this unit alone links
@@ -32,6 +32,7 @@
 #include <condition_variable>
 #include <functional>
 #include <atomic>
+#include "crt_own.h"
 #include "crt_state.h"
 #include "crt_instances.h"
 #include "crt_upload.h"
@@ -187,6 +188,7 @@ int crt_debug_last_kernel(char* dst, size_t cap)
     return CRT_OK;
 }
 int crt_debug_measure_clock(int micros, double* ghz) { ON_PRIMARY(crt1_debug_measure_clock(micros, ghz)); }
+int crt_debug_live_resources(uint64_t* out) { if (!out) return CRT_E_BAD_ARGUMENT; *out = (uint64_t)gLiveOwned.load(); return CRT_OK; }
 
 int crt_shutdown(void)
 {

@@ -1,5 +1,5 @@
 // crt_state.h -- host state of one device session: frame slots, pools, the helpers every other part uses
-// Part of the one translation unit crt_shim.hip (included there, in this order: crt_state.h, crt_instances.h, crt_upload.h,
+// Part of the one translation unit crt_shim.hip (included there, in this order: crt_own.h, crt_state.h, crt_instances.h, crt_upload.h,
 // crt_bvh_driver.h, crt_frame.h, crt_multidev.h); everything here has internal linkage.
 #pragma once
 // ------------------------------------------------------------------------------------------------
@@ -17,42 +17,48 @@ namespace {
 enum class Form { Mega, Wavefront, Refill, Block, LdsTop };
 
 struct EventSet {
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    Event ev[4];
     bool pending = false; int flags = 0; bool evRaygen = false, evPost = false;   // timing not yet read back
     unsigned long long seq = 0;
 };
 
-struct FrameSlot {
-    hipStream_t stream = nullptr;
-    EventSet es[2];                            // two sets, so the host may queue a slot's next frame before reading the last one's timing
-    unsigned frames = 0;
-    float4* out = nullptr;
-    float4* aux = nullptr; size_t auxPixels = 0;   // CRT_RENDER_FXAA: the unfiltered frame the filter reads (allocated on first use)
-    CrtBounceRay* blockQueue = nullptr; size_t blockQueueCap = 0;   // CRT_KERNEL=block / wavefront: bounce-ray queue, one 64- or 128-record range per workgroup of the primary launch
-    uint32_t* wfCount = nullptr; size_t wfCap = 0;                  // CRT_KERNEL=wavefront: per primary wave {continuing rays}, {offset within its XCD}, then the 8 per-XCD totals
-    // CRT_RENDER_GBUFFER: this slot's first-hit planes, one allocation of 36 B per pixel (geometry, ids, albedo back to back), made on
-    // the slot's first G-buffer frame (slot_gbuffer)
-    char* gbuf = nullptr; size_t gbufBytes = 0;
-    uint32_t* ovf = nullptr; size_t ovfWords = 0;   // traversal-stack overflow area of this slot's launches (CrtStack), one block per workgroup
-    uint32_t* lists = nullptr; size_t listsCap = 0;   // feedback launch lists: order, costs, sort keys, lengths (prepare_launch_lists)
-    int orderSlots = -1; int orderKey[7] = { 0, 0, 0, 0, 0, 0, 0 };
-    bool listsReady = false;                   // the lists for the next frame were already sorted at the end of the last one
-    // CRT_RENDER_READBACK: pinned host copy of this slot's frame, queued behind the frame on the slot's stream; packBuf: the
-    // frame's RGBA8 bytes, packCap pixels
-    void* hostBuf = nullptr; size_t hostCap = 0, hostBytes = 0; uint32_t* packBuf = nullptr; size_t packCap = 0; hipEvent_t copied = nullptr;
+// A stream with its own copy of the instance tables and its traversal-stack overflow area: what every frame slot has, and all the ray
+// queries' context borrows of one (create_slot_tables, ensure_slot_instances, fill_scene, ensure_overflow).
+struct SlotTables {
+    Stream stream;
     // This slot's copy of the instance tables (reference-layout records, device records, bounding spheres, instance tree,
     // never-culled list), refreshed on the slot's own stream from the host master when it is stale (ensure_slot_instances):
     // an instance upload never has to wait for the frames in flight, and those frames never see it.
-    char* instBlock = nullptr;                 // one device allocation; the four pointers below point into it
-    CrtMeshInstance* instances = nullptr; CrtDevInstance* devInstances = nullptr; float4* instBounds = nullptr;
-    CrtTlasNode* tlas = nullptr; uint32_t* alwaysList = nullptr; uint32_t tlasNodes = 0, numAlways = 0;
+    DevBuf<char> instBlock;                    // one device allocation; the four pointers below point into it
+    CrtMeshInstance* instances = nullptr; float4* instBounds = nullptr; CrtTlasNode* tlas = nullptr; uint32_t* alwaysList = nullptr;
+    DevBuf<CrtDevInstance> devInstances;
+    uint32_t tlasNodes = 0, numAlways = 0;
     unsigned long long instVersion = 0;        // 0 = never filled (the master starts at 1)
-    uint32_t* mixOrder = nullptr; size_t mixCap = 0; int mixSlots = -1;   // CRT_RENDER_DIAG_MIX3 launch lists, then their 8 lengths
+    PinnedBuf<char> staging; Event staged;     // pinned staging block and "its copies have been issued and done" event
     char* stagingDev = nullptr;                // the staging block as the device sees it
-    char* staging = nullptr; hipEvent_t staged = nullptr;   // pinned staging block and "its copies have been issued and done" event
+    DevBuf<uint32_t> ovf;                      // traversal-stack overflow area of this slot's launches (CrtStack), one block per workgroup
+};
+
+struct FrameSlot : SlotTables {
+    EventSet es[2];                            // two sets, so the host may queue a slot's next frame before reading the last one's timing
+    unsigned frames = 0;
+    DevBuf<float4> out;
+    DevBuf<float4> aux;                        // CRT_RENDER_FXAA: the unfiltered frame the filter reads (allocated on first use)
+    DevBuf<CrtBounceRay> blockQueue;           // CRT_KERNEL=block / wavefront: bounce-ray queue, one 64- or 128-record range per workgroup of the primary launch
+    DevBuf<uint32_t> wfCount;                  // CRT_KERNEL=wavefront: per primary wave {continuing rays}, {offset within its XCD}, then the 8 per-XCD totals
+    // CRT_RENDER_GBUFFER: this slot's first-hit planes, one allocation of 36 B per pixel (geometry, ids, albedo back to back), made on
+    // the slot's first G-buffer frame (slot_gbuffer)
+    DevBuf<char> gbuf;
+    DevBuf<uint32_t> lists;                    // feedback launch lists: order, costs, sort keys, lengths (prepare_launch_lists)
+    int orderSlots = -1; int orderKey[7] = { 0, 0, 0, 0, 0, 0, 0 };
+    bool listsReady = false;                   // the lists for the next frame were already sorted at the end of the last one
+    // CRT_RENDER_READBACK: pinned host copy of this slot's frame (hostBytes of it), queued behind the frame on the slot's stream;
+    // packBuf: the frame's RGBA8 bytes, one word per pixel
+    PinnedBuf<char> hostBuf; size_t hostBytes = 0; DevBuf<uint32_t> packBuf; Event copied;
+    DevBuf<uint32_t> mixOrder; int mixSlots = -1;   // CRT_RENDER_DIAG_MIX3 launch lists, then their 8 lengths
     // in-process multi-GPU (crt_init_devices): a secondary device records `partDone` behind the copy of its bands into the
     // primary's frame; the primary records `slotDone` behind everything a frame queues on this slot (incl. a read-back)
-    hipEvent_t partDone = nullptr, slotDone = nullptr;
+    Event partDone, slotDone;
     // RGBA8 gather (a multi-device session's CRT_RENDER_UNORM8 frames without FXAA): the WHOLE frame is in packBuf (every device's Trace
     // epilogue stores its pixels' four bytes, the secondaries copy 4 B per pixel into the primary's packBuf); `out` holds only this
     // device's bands until somebody asks for the float frame (expand_rgba8_frame: x = byte / 255, exactly what the epilogue stored)
@@ -60,20 +66,21 @@ struct FrameSlot {
 };
 
 // The context of the ray queries on device buffers (crt_trace_rays, crt_frame.h): queries never touch a frame slot, so they neither wait
-// for the frames in flight nor make them wait. `fs` is used as a frame slot without a frame: its stream (the instance-table refresh
-// runs there), its copy of the instance tables with the staging block and `staged` event (ensure_slot_instances), and its overflow
-// area, one block per workgroup of the persistent grid. One query at a time: every launch makes the caller's stream wait for
-// `raysDone` of the one before (no host wait), and whatever edits shared device state waits for it on the host (quiesce).
+// for the frames in flight nor make them wait. `tables`: the context's own stream (the instance-table refresh runs there), its copy of
+// the instance tables with the staging block and `staged` event (ensure_slot_instances), and its overflow area, one block per workgroup
+// of the persistent grid. One query at a time: every launch makes the caller's stream wait for `raysDone` of the one before (no host
+// wait), and whatever edits shared device state waits for it on the host (quiesce).
 struct QueryContext {
-    FrameSlot fs;
+    SlotTables tables;
     bool ready = false;                        // allocated (by the first query)
-    uint32_t* ctl = nullptr;                   // device: [0] chunk counter, [1] chunks traced without the cull (CrtRaysArgs::ctl)
-    hipEvent_t raysDone = nullptr; bool inFlight = false;   // recorded behind the last query on the caller's stream; inFlight: not yet known to be over
-    bool refreshPending = false;               // a table refresh was queued on fs.stream and no raysDone covers it yet (a query that failed behind it): quiesce waits for fs.staged
+    DevBuf<uint32_t> ctl;                      // device: [0] chunk counter, [1] chunks traced without the cull (CrtRaysArgs::ctl)
+    Event raysDone; bool inFlight = false;     // recorded behind the last query on the caller's stream; inFlight: not yet known to be over
+    bool refreshPending = false;               // a table refresh was queued on tables.stream and no raysDone covers it yet (a query that failed behind it): quiesce waits for tables.staged
     unsigned long long chunks = 0, grid = 0;   // of the last query (crt_debug_rays_stats)
     int residentPerCU[4] = { 0, 0, 0, 0 };     // hipOccupancyMaxActiveBlocksPerMultiprocessor of crt_rays_kernel<ANYHIT, TLAS>, [2 * ANYHIT + TLAS]; 0 = not asked yet
 };
 
+// Whatever a State holds is released when it is deleted, with its device current: destroy_group (crt_multidev.h) is the only place.
 struct State {
     bool initialized = false;
     int device = -1;
@@ -98,11 +105,11 @@ struct State {
     int width = 0, height = 0;
     int bandRows = 16, rank = 0, nRanks = 1;
     // raw (reference-layout) device copies
-    CrtTri* rawTris = nullptr; CrtBVHNode* rawNodes = nullptr; uint32_t* roots = nullptr; uint8_t* rawTexels = nullptr;
+    DevBuf<CrtTri> rawTris; DevBuf<CrtBVHNode> rawNodes; DevBuf<uint32_t> roots; DevBuf<uint8_t> rawTexels;
     // CDNA4 layouts
-    float4* pairs = nullptr; float* triHot = nullptr; uint4* triCold = nullptr; uint32_t* bigLeaf = nullptr;
-    uint32_t* rootRefs = nullptr; uint32_t* texels = nullptr;
-    CrtMaterial* materials = nullptr; CrtTexture* textures = nullptr;
+    DevBuf<float4> pairs; DevBuf<float> triHot; DevBuf<uint4> triCold; DevBuf<uint32_t> bigLeaf;
+    DevBuf<uint32_t> rootRefs; DevBuf<uint32_t> texels;
+    DevBuf<CrtMaterial> materials; DevBuf<CrtTexture> textures;
     // host master of everything derived from the instance table (rebuild_instance_master); slots copy it when stale
     float4 hBounds[CRT_MAX_INSTANCES]; CrtTlasNode hTlas[2 * CRT_MAX_INSTANCES]; uint32_t hAlways[CRT_MAX_INSTANCES];
     uint32_t hTlasNodes = 0, hNumAlways = 0; unsigned long long instVersion = 1;
@@ -116,13 +123,13 @@ struct State {
     // per instance and the smallest over the cullable ones; a frame / query whose origins lie beyond it runs with `noCullBounds`.
     float hCullOriginLimit[CRT_MAX_INSTANCES]; float cullOriginLimit = 0.0f; float bounceOriginReach = 0.0f;
     double triReach2 = 0.0;                    // largest squared distance of a vertex in the triangle pool from its object-space origin (crt1_upload_triangles)
-    uint32_t* triReachBits = nullptr;          // device: that maximum as float bits (crt_tri_reach_kernel)
-    float4* noCullBounds = nullptr;            // device: CRT_MAX_INSTANCES x (0, 0, 0, -1) = "never cull"
+    DevBuf<uint32_t> triReachBits;             // device: that maximum as float bits (crt_tri_reach_kernel)
+    DevBuf<float4> noCullBounds;               // device: CRT_MAX_INSTANCES x (0, 0, 0, -1) = "never cull"
     unsigned long long noCullFrames = 0;       // frames and queries that ran without the cull for that reason
     CrtMeshInstance hInstances[CRT_MAX_INSTANCES]; uint32_t hRoots[CRT_MAX_MESHES]; uint32_t instHigh = 0;
-    float* rays = nullptr;
-    unsigned long long* counters = nullptr; int* err = nullptr;
-    unsigned long long* stamps = nullptr; size_t stampCap = 0, stampWaves = 0;
+    DevBuf<float> rays;
+    DevBuf<unsigned long long> counters; DevBuf<int> err;
+    DevBuf<unsigned long long> stamps; size_t stampWaves = 0;
     int numCUs = 0;
     int forceTlas = -1;   // CRT_TLAS=0/1: force the linear / tree candidate search (tests); default: by instance count
     int feedbackAsync = 0; int feedback = 1; int maxSplit = CRT_MAX_SPLIT, maxSplitPipelined = CRT_MAX_SPLIT_PIPELINED;
@@ -132,23 +139,23 @@ struct State {
     float lastView[35] = { 0 }; unsigned long long lastViewInst = 0; bool viewMoved = false;   // camera matrices + position / instance version of the last sorted frame
     float splitBeta = CRT_SPLIT_BETA, splitBetaAsync = CRT_SPLIT_BETA_ASYNC;   // split a tile whose wave would run longer than beta x the XCD's time for the frame
     Form form = Form::Mega;                    // CRT_KERNEL: the Trace kernel structure of every frame (one the form cannot render is refused)
-    float4* topPairs = nullptr; uint32_t* topRootRefs = nullptr;   // the tree-top table (CRT_TOP_PAIRS records) and every mesh's entry into it, rebuilt with the BVH layout
+    DevBuf<float4> topPairs; DevBuf<uint32_t> topRootRefs;   // the tree-top table (CRT_TOP_PAIRS records) and every mesh's entry into it, rebuilt with the BVH layout
     char lastKernel[128] = { 0 };              // crt_debug_last_kernel: the Trace launch(es) of the most recently submitted frame
-    char* queryBuf = nullptr; size_t queryBytes = 0;
+    DevBuf<char> queryBuf;                     // scratch of crt_query_hits and crt_read_output_rgba8
     QueryContext rayQuery;                     // crt_trace_rays
     int raysGridCap = 0;                       // CRT_RAYS_GRID=n: at most n workgroups per query (tests: few waves walking many chunks); 0 = as many as are resident
-    void* buildBuf = nullptr; size_t buildBytes = 0;          // crt_build_bvh scratch
+    DevBuf<char> buildBuf;                                    // crt_build_bvh scratch
     std::vector<CrtBuildCtl> buildReplay; unsigned long long buildReplayKey = 0;   // CRT_DEBUG_BVH_REPLAY (crt_bvh_driver.h): the level records of the last build
     unsigned buildLaunches = 0, buildLevels = 0;   // crt_debug_build_stats: kernel launches and levels of the last crt_build_bvh (before the re-layout)
     bool buildNoSpin = false;                                   // the spin on buildCtlHost timed out once: synchronise the stream per level instead
-    CrtBuildCtlHost* buildCtlHost = nullptr; uint32_t buildSeq = 0;   // pinned: the per-level control record the builder publishes (crt_bvh_publish)
-    CrtTri* buildTris = nullptr;                               // crt_build_bvh: second triangle pool (same indexing as rawTris)
+    PinnedBuf<CrtBuildCtlHost> buildCtlHost; uint32_t buildSeq = 0;   // pinned: the per-level control record the builder publishes (crt_bvh_publish)
+    DevBuf<CrtTri> buildTris;                                  // crt_build_bvh: second triangle pool (same indexing as rawTris)
     size_t triCap = 0, nodeCap = 0, texelByteCap = 0;
     uint32_t nodeCount = 0, numRoots = 0; size_t texelBytesHigh = 0; size_t trisHigh = 0;
     bool sceneValid = true;
     double msSum[4] = { 0, 0, 0, 0 }; unsigned long long framesTimed = 0;   // crt_frame_time_stats
     float ms[4] = { 0, 0, 0, 0 }; unsigned long long msSeq = 0, frameSeq = 0;   // timing of the newest frame read back so far
-    hipEvent_t statStart = nullptr; bool statStartArmed = true, statStartValid = false; unsigned long long statStartSeq = 0; double statExtent = 0, statFirstMs = 0;
+    Event statStart; bool statStartArmed = true, statStartValid = false; unsigned long long statStartSeq = 0; double statExtent = 0, statFirstMs = 0;
     CrtCounters lastCounters; unsigned long long lastCulled = 0;
     double frameLog[512]; unsigned frameLogN = 0;      // crt_debug_read_frame_times: {start, end} ms after statStart of the frames since the last reset
     // in-process multi-GPU: this device renders band `rank` of `nRanks`; `primary` (rank 0) owns the frame that is read
@@ -172,28 +179,13 @@ static inline void crt_cpu_relax()
 }
 
 #define CRT_NUM_COUNTERS 15
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { return (int)e_; } } while (0)
-#define RCCHK(x) do { int r_ = (x); if (r_ != CRT_OK) { return r_; } } while (0)
-
-// Grows device buffer `p` to hold `count` elements (no-op when `cap` already does): waits for `s`, the stream that last used it,
-// frees it and allocates anew. Contents are not kept. On failure p == nullptr, cap == 0.
-template <class T> int grow(T*& p, size_t& cap, size_t count, hipStream_t s)
-{
-    if (count <= cap) return CRT_OK;
-    HIPCHK(hipStreamSynchronize(s));
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    HIPCHK(hipMalloc(&p, count * sizeof(T)));
-    cap = count;
-    return CRT_OK;
-}
 
 // Wait for frames still running on the second slot, and for the ray query in flight (it runs on the caller's stream), before anything
 // touches shared device state.
 int quiesce()
 {
     if (g.rayQuery.inFlight) { HIPCHK(hipEventSynchronize(g.rayQuery.raysDone)); g.rayQuery.inFlight = false; }
-    if (g.rayQuery.refreshPending) { HIPCHK(hipEventSynchronize(g.rayQuery.fs.staged)); g.rayQuery.refreshPending = false; }   // it reads g.rootRefs
+    if (g.rayQuery.refreshPending) { HIPCHK(hipEventSynchronize(g.rayQuery.tables.staged)); g.rayQuery.refreshPending = false; }   // it reads g.rootRefs
     if (g.othersBusy) {
         for (int i = 1; i < g.nSlots; ++i) HIPCHK(hipStreamSynchronize(g.slot[i].stream));
         g.othersBusy = false;
@@ -249,7 +241,7 @@ void fill_frame(CrtFrame& F, const CrtTraceArgs* args, const float* invView, con
 
 // noCull: the rays of this launch may start beyond the range the instance cull is proven for (State::cullOriginLimit): every
 // instance is a candidate for every ray (all-never bounds table, no instance tree)
-void fill_scene(CrtDevScene& S, uint32_t numInstances, const FrameSlot& fs, bool noCull = false)
+void fill_scene(CrtDevScene& S, uint32_t numInstances, const SlotTables& fs, bool noCull = false)
 {
     S.pairs = g.pairs; S.triHot = g.triHot; S.triCold = g.triCold; S.bigLeaf = g.bigLeaf; S.rootRefs = g.rootRefs; S.stackOverflow = fs.ovf;
     S.instances = fs.instances; S.devInstances = fs.devInstances; S.instBounds = fs.instBounds; S.materials = g.materials; S.textures = g.textures; S.texels = g.texels;
@@ -265,33 +257,25 @@ bool beyond_cull_range(double originNorm) { return !(originNorm <= (double)g.cul
 
 // The traversal-stack overflow area of a slot must hold one block per workgroup of its largest launch. It is never
 // initialised: entries are written before they are read.
-int ensure_overflow(FrameSlot& fs, size_t blocks) { return grow(fs.ovf, fs.ovfWords, blocks * CRT_OVF_WORDS_PER_BLOCK, fs.stream); }
+int ensure_overflow(SlotTables& fs, size_t blocks) { return fs.ovf.grow(blocks * CRT_OVF_WORDS_PER_BLOCK, fs.stream); }
 
-// New frame buffers are allocated first and swapped in only when every allocation succeeded: a failed resize leaves
-// the old frame size fully usable (crt_resize returns the error).
+// New frame buffers are allocated first and moved in only when every allocation succeeded: a failed resize leaves
+// the old frame size fully usable (crt_resize returns the error; the new buffers free themselves).
 int alloc_frame_buffers(int w, int h)
 {
     const size_t pixels = (size_t)w * (size_t)h;
-    float* rays = nullptr; float4* outs[CRT_MAX_FRAMES_IN_FLIGHT] = {};
-    hipError_t e = hipMalloc(&rays, sizeof(float) * 3 * pixels);
-    for (int i = 0; i < g.nSlots && e == hipSuccess; ++i) {   // slots past nSlots are never rendered into
-        e = hipMalloc(&outs[i], sizeof(float4) * pixels);
-        if (e == hipSuccess) e = hipMemsetAsync(outs[i], 0, sizeof(float4) * pixels, g.stream);
+    DevBuf<float> rays; DevBuf<float4> outs[CRT_MAX_FRAMES_IN_FLIGHT];
+    RCCHK(rays.alloc(3 * pixels));
+    for (int i = 0; i < g.nSlots; ++i) {   // slots past nSlots are never rendered into
+        RCCHK(outs[i].alloc(pixels));
+        HIPCHK(hipMemsetAsync(outs[i], 0, sizeof(float4) * pixels, g.stream));
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    if (e != hipSuccess) {
-        if (rays) (void)hipFree(rays);
-        for (float4* o : outs) if (o) (void)hipFree(o);
-        return (int)e;
-    }
-    if (g.rays) (void)hipFree(g.rays);
-    g.rays = rays;
+    HIPCHK(hipStreamSynchronize(g.stream));
+    g.rays = std::move(rays);
     for (int i = 0; i < CRT_MAX_FRAMES_IN_FLIGHT; ++i) {
         FrameSlot& fs = g.slot[i];
-        if (fs.out) (void)hipFree(fs.out);
-        fs.out = outs[i];
-        if (fs.aux) { (void)hipFree(fs.aux); fs.aux = nullptr; fs.auxPixels = 0; }
-        if (fs.gbuf) { (void)hipFree(fs.gbuf); fs.gbuf = nullptr; fs.gbufBytes = 0; }
+        fs.out = std::move(outs[i]);
+        fs.aux = DevBuf<float4>(); fs.gbuf = DevBuf<char>();
     }
     g.width = w; g.height = h; g.readbackCount = 0; g.pipelinedLatencyMs = 0.0f; g.gbufSlot = -1;
     return CRT_OK;

@@ -1,5 +1,5 @@
 // crt_upload.h -- session set-up / tear-down, uploads in the reference layouts (Renderer.cpp:122-193, ResourceManager.cpp:145-300) and read-backs of the pools
-// Part of the one translation unit crt_shim.hip (included there, in this order: crt_state.h, crt_instances.h, crt_upload.h,
+// Part of the one translation unit crt_shim.hip (included there, in this order: crt_own.h, crt_state.h, crt_instances.h, crt_upload.h,
 // crt_bvh_driver.h, crt_frame.h, crt_multidev.h); everything here has internal linkage.
 #pragma once
 namespace {
@@ -19,7 +19,7 @@ bool env_on(const char* name, bool dflt) { const char* e = getenv(name); return 
 const struct { const char* name; Form form; } kKernelForms[] = {
     { "default", Form::Mega }, { "wavefront", Form::Wavefront }, { "refill", Form::Refill }, { "block", Form::Block }, { "ldstop", Form::LdsTop } };
 
-// ---- the steps of init_impl; a failure leaves a half-built State for the caller's destroy_group / release_all ----
+// ---- the steps of init_impl; a failure leaves a half-built State for the caller's destroy_group ----
 
 int open_device(int device)
 {
@@ -36,15 +36,15 @@ int open_device(int device)
 }
 
 // a slot's copy of the instance tables, its staging block and `staged` event, on the slot's stream (a frame slot, or the ray queries' context)
-int create_slot_tables(FrameSlot& fs)
+int create_slot_tables(SlotTables& fs)
 {
-    HIPCHK(hipMalloc(&fs.instBlock, kStageBytes));         // the slot's instance tables in the staging block's layout (crt_instances.h)
+    RCCHK(fs.instBlock.alloc(kStageBytes));                // the slot's instance tables in the staging block's layout (crt_instances.h)
     fs.instances = reinterpret_cast<CrtMeshInstance*>(fs.instBlock + kStageInst); fs.instBounds = reinterpret_cast<float4*>(fs.instBlock + kStageBounds);
     fs.alwaysList = reinterpret_cast<uint32_t*>(fs.instBlock + kStageAlways); fs.tlas = reinterpret_cast<CrtTlasNode*>(fs.instBlock + kStageTlas);
-    HIPCHK(hipMalloc(&fs.devInstances, CRT_MAX_INSTANCES * sizeof(CrtDevInstance)));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&fs.staging), kStageBytes, hipHostMallocDefault));
+    RCCHK(fs.devInstances.alloc(CRT_MAX_INSTANCES));
+    RCCHK(fs.staging.alloc(kStageBytes, hipHostMallocDefault));
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&fs.stagingDev), fs.staging, 0));     // the refresh kernel reads the pinned block itself
-    HIPCHK(hipEventCreateWithFlags(&fs.staged, hipEventDisableTiming));
+    RCCHK(fs.staged.create(hipEventDisableTiming));
     HIPCHK(hipEventRecord(fs.staged, fs.stream));
     fs.instVersion = 0;
     return CRT_OK;
@@ -58,13 +58,13 @@ int create_frame_slots()
     g.nSlots = std::min(std::max(env_int("CRT_FRAMES_IN_FLIGHT", 3), 1), CRT_MAX_FRAMES_IN_FLIGHT);
     for (int si = 0; si < g.nSlots; ++si) {
         FrameSlot& fs = g.slot[si];
-        HIPCHK(hipStreamCreateWithFlags(&fs.stream, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&fs.partDone, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&fs.slotDone, hipEventDisableTiming));
-        for (EventSet& es : fs.es) for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&es.ev[i]));
+        RCCHK(fs.stream.create(hipStreamNonBlocking));
+        RCCHK(fs.partDone.create(hipEventDisableTiming));
+        RCCHK(fs.slotDone.create(hipEventDisableTiming));
+        for (EventSet& es : fs.es) for (Event& ev : es.ev) RCCHK(ev.create());
         RCCHK(create_slot_tables(fs));
     }
-    HIPCHK(hipEventCreate(&g.statStart));
+    RCCHK(g.statStart.create());
     g.stream = g.slot[0].stream; g.cur = 0; g.asyncSeq = 0; g.othersBusy = false;
     return CRT_OK;
 }
@@ -74,31 +74,31 @@ int alloc_pools()
     g.triCap = (size_t)CRT_MAX_TRIANGLES * 2;           // ResourceManager.cpp:158
     g.nodeCap = (size_t)CRT_MAX_TRIANGLES * 2;          // ResourceManager.cpp:159 (MAX_BVHMEMORY * 2)
     g.texelByteCap = CRT_MAX_TEXTURE_BYTES * 2;         // ResourceManager.cpp:163
-    HIPCHK(hipMalloc(&g.rawTris, g.triCap * sizeof(CrtTri)));
+    RCCHK(g.rawTris.alloc(g.triCap));
     HIPCHK(hipMemsetAsync(g.rawTris, 0, g.triCap * sizeof(CrtTri), g.stream));   // crt_tri_reach_kernel may scan slots nobody has uploaded yet (an upload that leaves a gap)
-    HIPCHK(hipMalloc(&g.rawNodes, g.nodeCap * sizeof(CrtBVHNode)));
-    HIPCHK(hipMalloc(&g.roots, CRT_MAX_MESHES * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&g.rawTexels, g.texelByteCap + 16));
-    HIPCHK(hipMalloc(&g.pairs, (g.nodeCap / 2 + 1) * 4 * sizeof(float4)));
-    HIPCHK(hipMalloc(&g.triHot, g.triCap * 9 * sizeof(float)));
-    HIPCHK(hipMalloc(&g.triCold, g.triCap * 2 * sizeof(uint4)));
-    HIPCHK(hipMalloc(&g.bigLeaf, (g.triCap + 1) * sizeof(uint32_t)));
+    RCCHK(g.rawNodes.alloc(g.nodeCap));
+    RCCHK(g.roots.alloc(CRT_MAX_MESHES));
+    RCCHK(g.rawTexels.alloc(g.texelByteCap + 16));
+    RCCHK(g.pairs.alloc((g.nodeCap / 2 + 1) * 4));
+    RCCHK(g.triHot.alloc(g.triCap * 9));
+    RCCHK(g.triCold.alloc(g.triCap * 2));
+    RCCHK(g.bigLeaf.alloc(g.triCap + 1));
     HIPCHK(hipMemset(g.bigLeaf + g.triCap, 0, sizeof(uint32_t)));      // crt_empty_ref: a leaf of zero triangles
-    HIPCHK(hipMalloc(&g.rootRefs, CRT_MAX_MESHES * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&g.topRootRefs, CRT_MAX_MESHES * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&g.topPairs, CRT_TOP_PAIRS * 4 * sizeof(float4)));
+    RCCHK(g.rootRefs.alloc(CRT_MAX_MESHES));
+    RCCHK(g.topRootRefs.alloc(CRT_MAX_MESHES));
+    RCCHK(g.topPairs.alloc(CRT_TOP_PAIRS * 4));
     HIPCHK(hipMemset(g.topPairs, 0, CRT_TOP_PAIRS * 4 * sizeof(float4)));
-    HIPCHK(hipMalloc(&g.texels, (g.texelByteCap / 3 + 2) * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&g.materials, CRT_MAX_MATERIALS * sizeof(CrtMaterial)));
-    HIPCHK(hipMalloc(&g.textures, CRT_MAX_TEXTURES * sizeof(CrtTexture)));
-    HIPCHK(hipMalloc(&g.counters, CRT_NUM_COUNTERS * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&g.err, sizeof(int)));
-    HIPCHK(hipMalloc(&g.triReachBits, sizeof(uint32_t)));
+    RCCHK(g.texels.alloc(g.texelByteCap / 3 + 2));
+    RCCHK(g.materials.alloc(CRT_MAX_MATERIALS));
+    RCCHK(g.textures.alloc(CRT_MAX_TEXTURES));
+    RCCHK(g.counters.alloc(CRT_NUM_COUNTERS));
+    RCCHK(g.err.alloc(1));
+    RCCHK(g.triReachBits.alloc(1));
     HIPCHK(hipMemset(g.triReachBits, 0, sizeof(uint32_t)));
     // the "never cull" bounds table of frames whose rays start beyond the cull's proven range
     static float4 never[CRT_MAX_INSTANCES];
     for (float4& b : never) b = make_float4(0.f, 0.f, 0.f, -1.0f);
-    HIPCHK(hipMalloc(&g.noCullBounds, sizeof never));
+    RCCHK(g.noCullBounds.alloc(CRT_MAX_INSTANCES));
     HIPCHK(hipMemcpy(g.noCullBounds, never, sizeof never, hipMemcpyHostToDevice));
     return CRT_OK;
 }
@@ -164,39 +164,13 @@ static int init_impl(int device, int width, int height)
     return crt1_upload_texels(def, 0, 6);
 }
 
-// frees everything State holds (also after an init that failed half way) and resets it
+// Waits for everything the session may still have running, also after an init that failed half way. Freeing is not done here: the
+// owners in State release what they hold when destroy_group deletes it.
 static void release_all()
 {
     for (FrameSlot& fs : g.slot) if (fs.stream) (void)hipStreamSynchronize(fs.stream);
     if (g.rayQuery.raysDone) (void)hipEventSynchronize(g.rayQuery.raysDone);      // the last ray query runs on its caller's stream
-    if (g.rayQuery.fs.stream) (void)hipStreamSynchronize(g.rayQuery.fs.stream);
-    void* ptrs[] = { g.rawTris, g.rawNodes, g.roots, g.rawTexels, g.pairs, g.triHot, g.triCold, g.bigLeaf, g.rootRefs,
-                     g.texels, g.materials, g.textures, g.rays, g.counters, g.err, g.triReachBits, g.topPairs, g.topRootRefs,
-                     g.queryBuf, g.buildBuf, g.buildTris, g.stamps, g.noCullBounds, g.rayQuery.ctl };
-    FrameSlot* slots[CRT_MAX_FRAMES_IN_FLIGHT + 1];
-    for (int i = 0; i < CRT_MAX_FRAMES_IN_FLIGHT; ++i) slots[i] = &g.slot[i];
-    slots[CRT_MAX_FRAMES_IN_FLIGHT] = &g.rayQuery.fs;                      // the ray queries' context owns a slot's tables, overflow area and stream
-    for (FrameSlot* sl : slots) {
-        FrameSlot& fs = *sl;
-        void* q[] = { fs.out, fs.aux, fs.blockQueue, fs.wfCount, fs.ovf, fs.lists, fs.mixOrder, fs.packBuf, fs.instBlock, fs.devInstances, fs.gbuf };
-        for (void* p : q) if (p) (void)hipFree(p);
-        if (fs.staging) (void)hipHostFree(fs.staging);
-        if (fs.staged) (void)hipEventDestroy(fs.staged);
-        if (fs.partDone) (void)hipEventDestroy(fs.partDone);
-        if (fs.slotDone) (void)hipEventDestroy(fs.slotDone);
-        if (fs.hostBuf) (void)hipHostFree(fs.hostBuf);
-        if (fs.copied) (void)hipEventDestroy(fs.copied);
-    }
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (g.statStart) (void)hipEventDestroy(g.statStart);
-    if (g.buildCtlHost) (void)hipHostFree(g.buildCtlHost);
-    if (g.rayQuery.raysDone) (void)hipEventDestroy(g.rayQuery.raysDone);
-    for (FrameSlot* sl : slots) {
-        FrameSlot& fs = *sl;
-        for (EventSet& es : fs.es) for (int i = 0; i < 4; ++i) if (es.ev[i]) (void)hipEventDestroy(es.ev[i]);
-        if (fs.stream) (void)hipStreamDestroy(fs.stream);
-    }
-    { State* me = G; *me = State(); }
+    if (g.rayQuery.tables.stream) (void)hipStreamSynchronize(g.rayQuery.tables.stream);
 }
 
 int crt1_resize(int width, int height)
@@ -235,7 +209,7 @@ int crt1_upload_triangles(const void* tris, size_t byteOffset, size_t bytes)
 {
     SPANCHK(tris, byteOffset, bytes, sizeof(CrtTri), g.triCap * sizeof(CrtTri));
     RCCHK(quiesce());
-    HIPCHK(hipMemcpyAsync(reinterpret_cast<char*>(g.rawTris) + byteOffset, tris, bytes, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(g.rawTris + byteOffset / sizeof(CrtTri), tris, bytes, hipMemcpyHostToDevice, g.stream));
     const size_t first = byteOffset / sizeof(CrtTri), count = bytes / sizeof(CrtTri);
     crt_relayout_tris<<<(unsigned)((count + 255) / 256), 256, 0, g.stream>>>(g.rawTris, first, count, g.triHot, g.triCold);
     HIPCHK(hipGetLastError());
@@ -268,7 +242,7 @@ int crt1_upload_bvh_nodes(const void* nodes, size_t byteOffset, size_t bytes)
 {
     SPANCHK(nodes, byteOffset, bytes, sizeof(CrtBVHNode), g.nodeCap * sizeof(CrtBVHNode));
     RCCHK(quiesce());
-    HIPCHK(hipMemcpyAsync(reinterpret_cast<char*>(g.rawNodes) + byteOffset, nodes, bytes, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(g.rawNodes + byteOffset / sizeof(CrtBVHNode), nodes, bytes, hipMemcpyHostToDevice, g.stream));
     const uint32_t high = (uint32_t)((byteOffset + bytes) / sizeof(CrtBVHNode));
     if (high > g.nodeCount) g.nodeCount = high;
     return rebuild_bvh_layout();

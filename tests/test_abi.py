@@ -72,3 +72,27 @@ def test_render_in_host_only_session_is_an_error():
         s.load_scene(scenes.get("tiny"))
         with pytest.raises(_lib.CrtError):
             s.render()
+
+
+HIP_OWNING_CALLS = r"\b(hipMalloc|hipFree|hipHostMalloc|hipHostFree|hipEventCreate\w*|hipEventDestroy|hipStreamCreate\w*|hipStreamDestroy)\s*\("
+
+
+def test_only_the_owners_create_and_destroy_hip_objects():
+    """Device and pinned buffers, events and streams are made and released by the four owner types of csrc/crt_own.h and nowhere else
+    in the library's sources; a process that has made no session holds none."""
+    csrc = os.path.join(ROOT, "clraytracer_amd", "csrc")
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".h", ".hip")))
+    assert "crt_own.h" in sources and "crt_shim.hip" in sources and len(sources) >= 16
+    found = {}
+    for f in sources:
+        text = open(os.path.join(csrc, f)).read()
+        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+        text = re.sub(r"//[^\n]*", "", text)
+        calls = re.findall(HIP_OWNING_CALLS, text)
+        if calls:
+            found[f] = sorted(set(calls))
+    assert set(found) == {"crt_own.h"}, found
+    assert len(found["crt_own.h"]) == 8, found                 # all eight live there: the scan sees what it looks for
+    n = C.c_uint64(99)
+    assert _lib.hip().crt_debug_live_resources(C.byref(n)) == 0 and n.value == 0
+    assert _lib.hip().crt_debug_live_resources(None) == _lib.CRT_E_BAD_ARGUMENT

@@ -12,7 +12,7 @@ import pytest
 
 from clraytracer_amd import _lib, driver, scenes
 import oracle_lib
-from util import bits
+from util import bits, live_resources
 
 pytestmark = pytest.mark.gpu
 
@@ -196,6 +196,7 @@ def test_failed_resize_rolls_every_device_back(monkeypatch):
         s.resize(640, 360)                                     # a later resize goes through
         assert _render(s, 0) == 0
         got = s.read_output()
+    assert live_resources() == 0                               # the refused resize and the roll-back left nothing behind on any device
     ref2, _ = single_frame(sc, 640, 360, flags=0)
     assert np.array_equal(bits(got), bits(ref2))
 

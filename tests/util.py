@@ -39,3 +39,12 @@ def bits(a):
 def rmse(a, b):
     d = a[..., :3].astype(np.float64) - b[..., :3].astype(np.float64)
     return float(np.sqrt(np.mean(d * d)))
+
+
+def live_resources():
+    """Device buffers, pinned buffers, events and streams libcrt_hip.so holds right now (crt_debug_live_resources; needs no session)."""
+    import ctypes as C
+    from clraytracer_amd import _lib
+    n = C.c_uint64(0)
+    _lib.check(_lib.hip().crt_debug_live_resources(C.byref(n)), "crt_debug_live_resources")
+    return int(n.value)

@@ -36,9 +36,10 @@ tools/ubench/cumask: tools/ubench/cumask.hip
 $(EXAMPLE): examples/headless_main.cpp $(HOST_SO)
 	$(CXX) $(CXXFLAGS) -o $@ examples/headless_main.cpp -Lclraytracer_amd/host -lcrt_host -Lclraytracer_amd/csrc -lcrt_hip -Wl,-rpath,'$$ORIGIN/../clraytracer_amd/host' -Wl,-rpath,'$$ORIGIN/../clraytracer_amd/csrc'
 
-# two translation units: crt_shim.hip (the C-ABI and every frame kernel) and crt_rays.hip (the kernel of crt_trace_rays)
-$(HIP_SO): $(wildcard clraytracer_amd/csrc/*.h) clraytracer_amd/csrc/crt_shim.hip clraytracer_amd/csrc/crt_rays.hip include/crt_api.h include/crt_debug.h include/crt_types.h
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ clraytracer_amd/csrc/crt_shim.hip clraytracer_amd/csrc/crt_rays.hip
+# three translation units: crt_shim.hip (the C-ABI and every frame kernel), crt_rays.hip (the kernel of crt_trace_rays) and crt_ao.hip (the
+# kernels of crt_trace_ao / crt_frame_ao; its direction table crt_ao_table.h is written by tools/make_ao_table.py and committed)
+$(HIP_SO): $(wildcard clraytracer_amd/csrc/*.h) clraytracer_amd/csrc/crt_shim.hip clraytracer_amd/csrc/crt_rays.hip clraytracer_amd/csrc/crt_ao.hip include/crt_api.h include/crt_debug.h include/crt_types.h
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ clraytracer_amd/csrc/crt_shim.hip clraytracer_amd/csrc/crt_rays.hip clraytracer_amd/csrc/crt_ao.hip
 
 $(HOST_SO): $(HOST_SRC) $(HOST_HDR) $(HIP_SO)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRC) -Lclraytracer_amd/csrc -lcrt_hip -lrt -Wl,-rpath,'$$ORIGIN/../csrc'

@@ -37,6 +37,20 @@ class CrtRayBatch(C.Structure):
 CRT_RAYS_CLOSEST, CRT_RAYS_OCCLUDED = 0, 1      # crt_trace_rays modes
 
 
+class CrtAoParams(C.Structure):
+    """Parameters of crt_trace_ao / crt_frame_ao (include/crt_types.h): samples in {1, 2, 4, ..., 64}, radius > 0, a finite bias."""
+    _fields_ = [("samples", C.c_uint32), ("radius", C.c_float), ("bias", C.c_float), ("seed", C.c_uint32), ("flags", C.c_uint32),
+                ("filterDepthTol", C.c_float), ("filterNormalCos", C.c_float)]
+
+
+class CrtAoPoints(C.Structure):
+    """Points on the device for crt_trace_ao: pointers as integers, strides in floats (0 = one value for every point)."""
+    _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p), ("positionStride", C.c_uint32), ("normalStride", C.c_uint32), ("n", C.c_uint64)]
+
+
+CRT_AO_FILTER = 1                               # CrtAoParams.flags
+
+
 class CrtFrameStats(C.Structure):
     _fields_ = [("frames", C.c_uint64), ("sumMs", C.c_double * 4), ("extentMs", C.c_double), ("firstFrameMs", C.c_double)]
 
@@ -62,7 +76,7 @@ RAYHIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<u4"
 HITRECORD_DTYPE = np.dtype([("normal", "<f4", 3), ("uv", "<f4", 2), ("distance", "<f4"), ("color", "<u4"), ("index", "<u4")])
 assert TRI_DTYPE.itemsize == 80 and NODE_DTYPE.itemsize == 32 and MATERIAL_DTYPE.itemsize == 16
 assert TEXTURE_DTYPE.itemsize == 16 and INSTANCE_DTYPE.itemsize == 80 and RAYHIT_DTYPE.itemsize == 20
-assert HITRECORD_DTYPE.itemsize == 32 and C.sizeof(CrtRayBatch) == 40
+assert HITRECORD_DTYPE.itemsize == 32 and C.sizeof(CrtRayBatch) == 40 and C.sizeof(CrtAoParams) == 28 and C.sizeof(CrtAoPoints) == 32
 # the first-hit planes of a CRT_RENDER_GBUFFER frame (include/crt_api.h) and one pixel of all three (CrtGBufferPixel, crt_pick_pixel)
 CRT_RENDER_GBUFFER = 8192        # the crt_render flag
 CRT_GBUFFER_GEOMETRY, CRT_GBUFFER_IDS, CRT_GBUFFER_ALBEDO = 0, 1, 2
@@ -117,6 +131,12 @@ HIP_API = {
     "crt_query_hits": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, _vp]),
     "crt_trace_rays": (C.c_int, [C.POINTER(CrtRayBatch), C.c_uint32, C.c_int, _vp, _vp]),
     "crt_debug_rays_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "crt_ao_directions": (C.c_int, [_fp]),
+    "crt_trace_ao": (C.c_int, [C.POINTER(CrtAoPoints), C.POINTER(CrtAoParams), C.c_uint32, _vp, _vp]),
+    "crt_frame_ao": (C.c_int, [C.POINTER(CrtAoParams), _vp]),
+    "crt_read_ao": (C.c_int, [_vp, _sz]),
+    "crt_ao_device_ptr": (_vp, []),
+    "crt_debug_ao_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "crt_debug_live_resources": (C.c_int, [C.POINTER(C.c_uint64)]),
     "crt_read_output": (C.c_int, [_vp, _sz]),
     "crt_read_output_rows": (C.c_int, [_vp, C.c_int, C.c_int]),
@@ -187,6 +207,9 @@ HOST_API = {
     "crth_render": (C.c_uint, [_f]),
     "crth_map_output": (_vp, []),
     "crth_trace_rays": (C.c_int, [C.POINTER(CrtRayBatch), C.c_int, _vp, _vp]),
+    "crth_trace_ao": (C.c_int, [C.POINTER(CrtAoPoints), C.POINTER(CrtAoParams), _vp, _vp]),
+    "crth_compute_ao": (C.c_int, [C.POINTER(CrtAoParams), _vp]),
+    "crth_map_ao": (_vp, []),
     "crth_last_frame_ms": (C.c_float, []),
     "crth_cpu_raycast": (None, [_vp, _vp, C.c_int, _vp, C.c_int]),
     "crth_cpu_raycast_sse": (None, [_vp, _vp, C.c_int, _vp, C.c_int]),

@@ -465,7 +465,12 @@ static int launch_passes(FrameCtx& c)
     const bool fxaaLocal = fxaa && g.groupSize <= 1;
     const size_t framePixels = (size_t)g.width * (size_t)g.height;
     if (fxaa && !is_secondary()) RCCHK(fs.aux.grow(framePixels, fs.stream));
-    if (c.flags & CRT_RENDER_GBUFFER) RCCHK(fs.gbuf.grow(framePixels * CRT_GBUFFER_PIXEL_BYTES, fs.stream));
+    if (c.flags & CRT_RENDER_GBUFFER) {
+        RCCHK(fs.gbuf.grow(framePixels * CRT_GBUFFER_PIXEL_BYTES, fs.stream));
+        // an AO query may still read this slot's planes (crt_frame_ao): the frame waits for it on the device, the host does not
+        if (fs.aoPending && g.rayQuery.inFlight) HIPCHK(hipStreamWaitEvent(fs.stream, g.rayQuery.raysDone, 0));
+        fs.aoPending = false;
+    }
     if (!fxaa) F.epilogue = (unorm ? CRT_EPILOGUE_QUANTIZE : 0u) | (post ? CRT_EPILOGUE_POST : 0u);
     else if (fxaaLocal) F.epilogue = unorm ? CRT_EPILOGUE_QUANTIZE : 0u;
     // the kernel that stores the final pixel stores its four bytes too: for a read-back of the RGBA8 frame on one device (a
@@ -532,7 +537,13 @@ static int finish_frame(const FrameCtx& c)
     FrameSlot& fs = *c.fs; EventSet& es = *c.es;
     fs.frameIs8 = c.gather8;
     g.cur = c.slot;
-    if (c.flags & CRT_RENDER_GBUFFER) g.gbufSlot = c.slot;
+    if (c.flags & CRT_RENDER_GBUFFER) {         // what crt_frame_ao needs of this frame: its camera, and an event behind its kernels
+        g.gbufSlot = c.slot;
+        memcpy(fs.gbufInvView, c.F.invView, 64); memcpy(fs.gbufInvProj, c.F.invProj, 64);
+        memcpy(fs.gbufArgs.cameraPos, c.F.camPos, 12); fs.gbufArgs.numMeshes = c.S.numInstances;
+        if (!fs.gbufDone) RCCHK(fs.gbufDone.create(hipEventDisableTiming));
+        HIPCHK(hipEventRecord(fs.gbufDone, fs.stream));
+    }
     es.pending = true; es.flags = c.flags; es.seq = ++g.frameSeq; fs.frames++;
     if (c.T.order != nullptr && !(c.flags & CRT_RENDER_DIAG_MIX3)) {
         // did the view change since the last sorted frame? (camera matrices and position, instance tables)
@@ -672,9 +683,52 @@ static int ensure_ray_query_context()
     if (q.ready) return CRT_OK;
     if (!q.tables.stream) RCCHK(q.tables.stream.create(hipStreamNonBlocking));
     if (!q.tables.instBlock) RCCHK(create_slot_tables(q.tables));
-    if (!q.ctl) RCCHK(q.ctl.alloc(2));
+    if (!q.ctl) RCCHK(q.ctl.alloc(4));
     if (!q.raysDone) RCCHK(q.raysDone.create(hipEventDisableTiming));
     q.ready = true;
+    return CRT_OK;
+}
+
+// The three steps every query on the context shares (crt_trace_rays, crt_trace_ao, crt_frame_ao); all of the caller's checks come first.
+// 1. The scene as the query sees it: the context exists, its instance tables are current -- an instance upload since the last query is
+//    refreshed on the context's own stream behind the query that may still read the old tables.
+static int query_scene(uint32_t numInstances, CrtDevScene& S)
+{
+    RCCHK(ensure_ray_query_context());
+    QueryContext& q = g.rayQuery;
+    SlotTables& fs = q.tables;
+    if (fs.instVersion != g.instVersion) {
+        if (q.inFlight) HIPCHK(hipStreamWaitEvent(fs.stream, q.raysDone, 0));
+        q.refreshPending = true;               // until a raysDone lies behind it: a step that fails below must not leave it unseen by quiesce()
+        RCCHK(ensure_slot_instances(fs));
+    }
+    fill_scene(S, numInstances, fs);
+    return CRT_OK;
+}
+// 2. The persistent grid -- min(chunks, CUs x resident workgroups, CRT_RAYS_GRID) -- with an overflow block per workgroup (the host waits
+//    only when the area has to grow), and the caller's stream ordered, on the device, behind the query before and the table refresh.
+static int query_grid(uint64_t chunks, int perCU, hipStream_t stream, CrtDevScene& S, uint64_t& grid)
+{
+    QueryContext& q = g.rayQuery;
+    SlotTables& fs = q.tables;
+    grid = (uint64_t)g.numCUs * (uint64_t)perCU;
+    if (g.raysGridCap > 0 && grid > (uint64_t)g.raysGridCap) grid = (uint64_t)g.raysGridCap;
+    if (grid > chunks) grid = chunks;
+    if (grid * CRT_OVF_WORDS_PER_BLOCK > fs.ovf.capacity()) {
+        if (q.inFlight) { HIPCHK(hipEventSynchronize(q.raysDone)); q.inFlight = false; }      // the query before still owns the old area (grow() frees it)
+        RCCHK(ensure_overflow(fs, (size_t)grid));
+    }
+    S.stackOverflow = fs.ovf;
+    if (q.inFlight) HIPCHK(hipStreamWaitEvent(stream, q.raysDone, 0));
+    HIPCHK(hipStreamWaitEvent(stream, fs.staged, 0));
+    return CRT_OK;
+}
+// 3. Behind the query's last launch: the event the next query, and whatever edits shared device state (quiesce), waits for.
+static int end_query(hipStream_t stream)
+{
+    QueryContext& q = g.rayQuery;
+    HIPCHK(hipEventRecord(q.raysDone, stream));
+    q.inFlight = true; q.refreshPending = false;      // (raysDone lies behind `staged`: the stream waited for it)
     return CRT_OK;
 }
 
@@ -707,30 +761,16 @@ int crt1_trace_rays(const CrtRayBatch* rays, uint32_t numInstances, int mode, vo
     if (mode != CRT_RAYS_CLOSEST && mode != CRT_RAYS_OCCLUDED) return CRT_E_BAD_ARGUMENT;
     if (numInstances > CRT_MAX_INSTANCES || !g.sceneValid) return CRT_E_BAD_ARGUMENT;
     if (rays->n > CRT_RAYS_MAX) return CRT_E_OUT_OF_RANGE;
-    RCCHK(ensure_ray_query_context());
-    QueryContext& q = g.rayQuery;
-    SlotTables& fs = q.tables;
     const bool anyHit = mode == CRT_RAYS_OCCLUDED;
-    if (fs.instVersion != g.instVersion) {      // an instance upload since the last query: refresh behind the query that may still read the old tables
-        if (q.inFlight) HIPCHK(hipStreamWaitEvent(fs.stream, q.raysDone, 0));
-        q.refreshPending = true;               // until a raysDone lies behind it: a step that fails below must not leave it unseen by quiesce()
-        RCCHK(ensure_slot_instances(fs));
-    }
-    CrtDevScene S; fill_scene(S, numInstances, fs);
+    CrtDevScene S;
+    RCCHK(query_scene(numInstances, S));
     const bool tlas = use_tlas(S);
     const uint64_t chunks = (rays->n + CRT_BLOCK - 1) / CRT_BLOCK;
     int perCU = 1;
     RCCHK(rays_resident_per_cu(anyHit, tlas, perCU));
-    uint64_t grid = (uint64_t)g.numCUs * (uint64_t)perCU;
-    if (g.raysGridCap > 0 && grid > (uint64_t)g.raysGridCap) grid = (uint64_t)g.raysGridCap;
-    if (grid > chunks) grid = chunks;
-    if (grid * CRT_OVF_WORDS_PER_BLOCK > fs.ovf.capacity()) {
-        if (q.inFlight) { HIPCHK(hipEventSynchronize(q.raysDone)); q.inFlight = false; }      // the query before still owns the old area (grow() frees it)
-        RCCHK(ensure_overflow(fs, (size_t)grid));
-    }
-    S.stackOverflow = fs.ovf;
-    if (q.inFlight) HIPCHK(hipStreamWaitEvent(stream, q.raysDone, 0));
-    HIPCHK(hipStreamWaitEvent(stream, fs.staged, 0));
+    uint64_t grid = 0;
+    RCCHK(query_grid(chunks, perCU, stream, S, grid));
+    QueryContext& q = g.rayQuery;
     HIPCHK(hipMemsetAsync(q.ctl, 0, 2 * sizeof(uint32_t), stream));
     CrtRaysArgs A;
     A.origins = rays->origins; A.dirs = rays->dirs; A.tmax = rays->tmax; A.out = out; A.ctl = q.ctl; A.noCullBounds = g.noCullBounds;
@@ -738,8 +778,8 @@ int crt1_trace_rays(const CrtRayBatch* rays, uint32_t numInstances, int mode, vo
     A.cullOriginLimit = (double)g.cullOriginLimit;
     with_bools([&](auto An, auto Tl) { crt_rays_kernel<decltype(An)::value, decltype(Tl)::value><<<(unsigned)grid, CRT_BLOCK, 0, stream>>>(S, A); }, anyHit, tlas);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(q.raysDone, stream));
-    q.inFlight = true; q.refreshPending = false; q.chunks = chunks; q.grid = grid;      // (raysDone lies behind `staged`: the stream waited for it)
+    RCCHK(end_query(stream));
+    q.chunks = chunks; q.grid = grid;
     return CRT_OK;
 }
 

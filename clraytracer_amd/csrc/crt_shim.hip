@@ -3,16 +3,18 @@
 // Replaces the OpenCL side of the reference's Renderer.cpp / ResourceManager.cpp: device pools,
 // uploads, the per-frame RayGen -> Trace -> PostProcess launch (Renderer.cpp:305-375). Uploads
 // arrive in the reference's struct layouts and are re-laid-out on the device (crt_device.h).
-// One translation unit (and crt_rays.hip, the ray-query kernel, beside it); the parts (round 5 split what used to be one 2,000-line file):
+// One translation unit (and crt_rays.hip, the ray-query kernel, and crt_ao.hip, the ambient-occlusion kernels, beside it); the parts (round 5 split what used to be one 2,000-line file):
 //   kernels     crt_device.h (traversal + shading), crt_kernels.h (launches), crt_refill.h (opt-in in-wave compaction forms), crt_ldstop.h (opt-in: tree tops staged in LDS),
-//               crt_relayout.h (upload-time layouts), crt_bvh_build.h (device BuildBVH); crt_rays.h declares the ray-query kernel of the second unit, crt_rays.hip
+//               crt_relayout.h (upload-time layouts), crt_bvh_build.h (device BuildBVH); crt_rays.h declares the ray-query kernel of the second unit, crt_rays.hip,
+//               crt_ao.h the ambient-occlusion kernels of the third, crt_ao.hip
 //   host state  crt_own.h (the owners of device / pinned buffers, events and streams), crt_state.h (State / FrameSlot, helpers), crt_instances.h (instance tables, cull bounds, instance tree)
 //   entry impl  crt_upload.h (init, uploads, read-backs), crt_bvh_driver.h (crt_build_bvh), crt_frame.h (crt_render and what a frame
-//               needs), crt_multidev.h (several devices behind the same calls)
-// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared crt_shim.hip crt_rays.hip (the Makefile's rule; a library of this unit alone links
-// but does not load: crt_frame.h refers to the kernels crt_rays.hip defines)
+//               needs), crt_ao_host.h (crt_trace_ao, crt_frame_ao), crt_multidev.h (several devices behind the same calls)
+// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared crt_shim.hip crt_rays.hip crt_ao.hip (the Makefile's rule; a library of this unit
+// alone links but does not load: crt_frame.h and crt_ao_host.h refer to the kernels the other two define)
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <cmath>
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
@@ -22,6 +24,7 @@
 #include "crt_refill.h"
 #include "crt_ldstop.h"
 #include "crt_rays.h"
+#include "crt_ao.h"
 #include "crt_relayout.h"
 #include "crt_bvh_build.h"
 #include <vector>
@@ -38,6 +41,7 @@
 #include "crt_upload.h"
 #include "crt_bvh_driver.h"
 #include "crt_frame.h"
+#include "crt_ao_host.h"
 
 #include "crt_multidev.h"
 
@@ -303,6 +307,28 @@ int crt_trace_rays(const CrtRayBatch* rays, uint32_t numInstances, int mode, voi
     ON_PRIMARY(crt1_trace_rays(rays, numInstances, mode, out, static_cast<hipStream_t>(stream)));
 }
 int crt_debug_rays_stats(uint64_t out[3]) { ON_PRIMARY(crt1_debug_rays_stats(out)); }
+// ambient occlusion: pure table; the two queries on one GPU's pointers / planes, refused in a session of several like crt_trace_rays
+int crt_ao_directions(float out[768])
+{
+    if (!out) return CRT_E_BAD_ARGUMENT;
+    for (int i = 0; i < CRT_AO_TABLE_SIZE; ++i) { out[3 * i] = kAoTable[i].x; out[3 * i + 1] = kAoTable[i].y; out[3 * i + 2] = kAoTable[i].z; }
+    return CRT_OK;
+}
+int crt_trace_ao(const CrtAoPoints* points, const CrtAoParams* params, uint32_t numInstances, float* out, void* stream)
+{
+    NEED_SESSION();
+    if (M.n > 1) return CRT_E_UNSUPPORTED;
+    ON_PRIMARY(crt1_trace_ao(points, params, numInstances, out, static_cast<hipStream_t>(stream)));
+}
+int crt_frame_ao(const CrtAoParams* params, void* stream)
+{
+    NEED_SESSION();
+    if (M.n > 1) return CRT_E_UNSUPPORTED;
+    ON_PRIMARY(crt1_frame_ao(params, static_cast<hipStream_t>(stream)));
+}
+int crt_read_ao(float* dst, size_t floats) { ON_PRIMARY(crt1_read_ao(dst, floats)); }
+void* crt_ao_device_ptr(void) { if (M.n == 0) return nullptr; Use u(0); return crt1_ao_device_ptr(); }
+int crt_debug_ao_stats(uint64_t out[3]) { ON_PRIMARY(crt1_debug_ao_stats(out)); }
 int crt_read_output(float* dst, size_t floats) { NEED_SESSION(); RCCHK(drain_secondaries()); ON_PRIMARY(crt1_read_output(dst, floats)); }
 int crt_read_output_rows(float* dst, int row0, int rows) { NEED_SESSION(); RCCHK(drain_secondaries()); ON_PRIMARY(crt1_read_output_rows(dst, row0, rows)); }
 int crt_read_output_rgba8(uint8_t* dst, size_t bytes) { NEED_SESSION(); RCCHK(drain_secondaries()); ON_PRIMARY(crt1_read_output_rgba8(dst, bytes)); }

@@ -49,6 +49,12 @@ struct FrameSlot : SlotTables {
     // CRT_RENDER_GBUFFER: this slot's first-hit planes, one allocation of 36 B per pixel (geometry, ids, albedo back to back), made on
     // the slot's first G-buffer frame (slot_gbuffer)
     DevBuf<char> gbuf;
+    // crt_frame_ao: what the slot's last G-buffer frame was rendered with (the matrices and camera its pixels' rays are regenerated from,
+    // its instance count), the event recorded behind it (an AO query's stream waits for it on the device), and the slot's AO plane --
+    // W x H floats, allocated by the slot's first crt_frame_ao; `aoRaw`: the unfiltered plane CRT_AO_FILTER reads. aoPending: an AO query
+    // that reads the planes may still run -- the slot's next G-buffer frame waits for it on the device.
+    float gbufInvView[16] = { 0 }, gbufInvProj[16] = { 0 }; CrtTraceArgs gbufArgs = {}; Event gbufDone;
+    DevBuf<float> ao, aoRaw; bool aoPending = false;
     DevBuf<uint32_t> lists;                    // feedback launch lists: order, costs, sort keys, lengths (prepare_launch_lists)
     int orderSlots = -1; int orderKey[7] = { 0, 0, 0, 0, 0, 0, 0 };
     bool listsReady = false;                   // the lists for the next frame were already sorted at the end of the last one
@@ -73,11 +79,13 @@ struct FrameSlot : SlotTables {
 struct QueryContext {
     SlotTables tables;
     bool ready = false;                        // allocated (by the first query)
-    DevBuf<uint32_t> ctl;                      // device: [0] chunk counter, [1] chunks traced without the cull (CrtRaysArgs::ctl)
+    DevBuf<uint32_t> ctl;                      // device: [0] chunk counter, [1] chunks traced without the cull (CrtRaysArgs::ctl); [2], [3]: the same of the AO queries (CrtAoArgs::ctl)
     Event raysDone; bool inFlight = false;     // recorded behind the last query on the caller's stream; inFlight: not yet known to be over
     bool refreshPending = false;               // a table refresh was queued on tables.stream and no raysDone covers it yet (a query that failed behind it): quiesce waits for tables.staged
     unsigned long long chunks = 0, grid = 0;   // of the last query (crt_debug_rays_stats)
     int residentPerCU[4] = { 0, 0, 0, 0 };     // hipOccupancyMaxActiveBlocksPerMultiprocessor of crt_rays_kernel<ANYHIT, TLAS>, [2 * ANYHIT + TLAS]; 0 = not asked yet
+    unsigned long long aoChunks = 0, aoGrid = 0;   // of the last AO query (crt_debug_ao_stats)
+    int aoResidentPerCU[4] = { 0, 0, 0, 0 };   // the same of crt_ao_kernel<SOURCE, TLAS>, [2 * SOURCE + TLAS]
 };
 
 // Whatever a State holds is released when it is deleted, with its device current: destroy_group (crt_multidev.h) is the only place.
@@ -91,6 +99,7 @@ struct State {
     hipStream_t stream = nullptr;              // == slot[0].stream: uploads, queries, diagnostics
     int cur = 0;                               // slot of the most recently submitted frame
     int gbufSlot = -1;                         // ... of the most recently submitted CRT_RENDER_GBUFFER frame; -1: none since crt_init / the last resize
+    int aoSlot = -1;                           // ... of the most recent crt_frame_ao (its AO plane); -1: none since crt_init / the last resize
     int readbackRing[CRT_MAX_FRAMES_IN_FLIGHT] = { -1, -1, -1, -1, -1, -1, -1, -1 }; unsigned readbackCount = 0;   // slots of the latest CRT_RENDER_READBACK frames
     unsigned asyncSeq = 0; bool othersBusy = false;   // frames possibly running on slots > 0
     // Start-up stagger of a burst of frames in flight: frames submitted to an idle device start together, run in lockstep and have
@@ -275,9 +284,9 @@ int alloc_frame_buffers(int w, int h)
     for (int i = 0; i < CRT_MAX_FRAMES_IN_FLIGHT; ++i) {
         FrameSlot& fs = g.slot[i];
         fs.out = std::move(outs[i]);
-        fs.aux = DevBuf<float4>(); fs.gbuf = DevBuf<char>();
+        fs.aux = DevBuf<float4>(); fs.gbuf = DevBuf<char>(); fs.ao = DevBuf<float>(); fs.aoRaw = DevBuf<float>(); fs.aoPending = false;
     }
-    g.width = w; g.height = h; g.readbackCount = 0; g.pipelinedLatencyMs = 0.0f; g.gbufSlot = -1;
+    g.width = w; g.height = h; g.readbackCount = 0; g.pipelinedLatencyMs = 0.0f; g.gbufSlot = -1; g.aoSlot = -1;
     return CRT_OK;
 }
 

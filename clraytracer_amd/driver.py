@@ -289,6 +289,49 @@ class Session:
         _lib.check(self.hip.crt_debug_rays_stats(out), "crt_debug_rays_stats")
         return int(out[0]), int(out[1]), int(out[2])
 
+    # ---- ambient occlusion (Renderer::TraceAmbientOcclusion / ComputeAmbientOcclusion -> crt_trace_ao / crt_frame_ao) ----
+    # radius and bias are lengths in the scene's units and have no default: what counts as "near" is the caller's knowledge of the scene.
+    def trace_ao(self, points, normals, samples=8, *, radius, bias, seed=0):
+        """Ambient occlusion (1 = open, 0 = closed; include/crt_api.h) at n points with normals, float32 torch tensors on the session's device
+        in the shapes trace_rays takes: (n, 3) packed or as rows of a wider tensor, or (3,) / (1, 3) for one value shared by every point.
+        `samples` rays (1, 2, 4, ..., 64) per point reach `radius` far from the point lifted by normal * `bias`. Returns a float32 tensor of
+        shape (n,), enqueued on torch.cuda.current_stream() without synchronising."""
+        import torch
+        (np_, sp), (nn, sn) = self._ray_array("points", points, 3), self._ray_array("normals", normals, 3)
+        counts = [c for c, st in ((np_, sp), (nn, sn)) if st != 0 or c == 0]
+        n = counts[0] if counts else 1
+        if any(c != n for c in counts):
+            raise ValueError(f"points and normals disagree about the number of points: {counts}")
+        for name, x in (("points", points), ("normals", normals)):
+            if x.device.type != "cuda" or x.device.index != self.device:
+                raise ValueError(f"{name}: the tensor is on {x.device}, the session on cuda:{self.device}")
+        dev = torch.device("cuda", self.device)
+        pts = _lib.CrtAoPoints(points.data_ptr(), normals.data_ptr(), sp, sn, n)
+        params = _lib.CrtAoParams(int(samples), float(radius), float(bias), int(seed) & 0xFFFFFFFF, 0, 0.0, 0.0)
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        if not self.h.crth_trace_ao(C.byref(pts), C.byref(params), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream):
+            self._raise_and_clear("Renderer::TraceAmbientOcclusion")
+        return out
+
+    def ambient_occlusion(self, samples=8, *, radius, bias, seed=0, filter=False, depth_tol=0.05, normal_cos=0.9, stream=None):
+        """Ambient occlusion of the pixels of the last frame rendered with gbuffer=True, as a (height, width) float32 array (1 = open; a pixel
+        of sky is 1). filter=True: the 5 x 5 mean over neighbours whose distance is within depth_tol (relative) and whose normal's cosine is
+        at least normal_cos. `stream`: a hipStream_t as an integer; None: HIP's null stream."""
+        params = _lib.CrtAoParams(int(samples), float(radius), float(bias), int(seed) & 0xFFFFFFFF, _lib.CRT_AO_FILTER if filter else 0,
+                                  float(depth_tol), float(normal_cos))
+        if not self.h.crth_compute_ao(C.byref(params), stream):
+            self._raise_and_clear("Renderer::ComputeAmbientOcclusion")
+        ptr = self.h.crth_map_ao()
+        if not ptr:
+            self._raise_and_clear("Renderer::MapAmbientOcclusion")
+        return _lib.as_array(ptr, self.width * self.height, np.float32).reshape(self.height, self.width)
+
+    def ao_stats(self):
+        """(chunks, chunks traced without the instance cull, workgroups launched) of the last trace_ao / ambient_occlusion, after waiting for it."""
+        out = (C.c_uint64 * 3)()
+        _lib.check(self.hip.crt_debug_ao_stats(out), "crt_debug_ao_stats")
+        return int(out[0]), int(out[1]), int(out[2])
+
     def set_row_bands(self, band_rows, rank, n_ranks):
         self.h.crth_set_row_bands(int(band_rows), int(rank), int(n_ranks))
         self._check("SetRowBands")

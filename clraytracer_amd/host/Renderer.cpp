@@ -23,7 +23,7 @@ namespace {
     float timeSeconds = 0.0f;
     unsigned frameIndex = 0;
     int lastError = 0;
-    std::vector<float> hostFrame;
+    std::vector<float> hostFrame, hostAo;
 
     uint numRegisteredInstances = 0, lastRegisterInstanceIndex = 0;
     ushort removedInstances[50];
@@ -228,6 +228,27 @@ bool Renderer::TraceRays(const CrtRayBatch& rays, int mode, void* out, void* str
 {
     if (!deviceReady) { lastError = CRT_E_NOT_INITIALIZED; return false; }
     return check(crt_trace_rays(&rays, g_NumMeshInstances, mode, out, stream), "crt_trace_rays");
+}
+
+bool Renderer::TraceAmbientOcclusion(const CrtAoPoints& points, const CrtAoParams& params, float* out, void* stream)
+{
+    if (!deviceReady) { lastError = CRT_E_NOT_INITIALIZED; return false; }
+    return check(crt_trace_ao(&points, &params, g_NumMeshInstances, out, stream), "crt_trace_ao");
+}
+
+bool Renderer::ComputeAmbientOcclusion(const CrtAoParams& params, void* stream)
+{
+    if (!deviceReady) { lastError = CRT_E_NOT_INITIALIZED; return false; }
+    return check(crt_frame_ao(&params, stream), "crt_frame_ao");
+}
+
+const float* Renderer::MapAmbientOcclusion()
+{
+    if (!deviceReady) { lastError = CRT_E_NOT_INITIALIZED; return nullptr; }
+    const size_t n = (size_t)camera.projWidth * (size_t)camera.projHeight;
+    hostAo.resize(n);
+    if (!check(crt_read_ao(hostAo.data(), n), "crt_read_ao")) return nullptr;
+    return hostAo.data();
 }
 
 void Renderer::Terminate()

@@ -48,6 +48,13 @@ namespace Renderer
     // extension: closest hit (CRT_RAYS_CLOSEST: CrtRayHit per ray) or occlusion (CRT_RAYS_OCCLUDED: one byte per ray) for a batch of rays on the device
     // against the registered instances (as last uploaded), enqueued on `stream` (a hipStream_t; null: HIP's null stream) without waiting; false: LastError()
     bool TraceRays(const CrtRayBatch& rays, int mode, void* out, void* stream = nullptr);
+    // extension: ambient occlusion (crt_api.h: crt_trace_ao, crt_frame_ao). TraceAmbientOcclusion: n floats into `out` for points + normals on the device,
+    // against the registered instances, enqueued on `stream` without waiting. ComputeAmbientOcclusion: the same for the pixels of the last frame rendered
+    // with SetGBuffer(true), into that frame's AO plane; MapAmbientOcclusion: a host copy of it (width*height floats, valid until the next call; null
+    // without one). false / null: LastError()
+    bool TraceAmbientOcclusion(const CrtAoPoints& points, const CrtAoParams& params, float* out, void* stream = nullptr);
+    bool ComputeAmbientOcclusion(const CrtAoParams& params, void* stream = nullptr);
+    const float* MapAmbientOcclusion();
     void SetRefraction(bool enabled);     // extension: upstream's README TODO "refraction / transculency": materials with MTL d < 1 transmit; off by default
     void SetPipelined(bool enabled);      // Render() returns without waiting (frames in flight); MapOutput()/uploads wait. Off by default (upstream clFinish()es)
     void SetTime(float seconds);          // TraceArgs.time (Window::GetTime upstream)

@@ -121,6 +121,19 @@ int crth_trace_rays(const CrtRayBatch* rays, int mode, void* out, void* stream)
     if (!rays) { hostOnlyError = CRT_E_BAD_ARGUMENT; return 0; }      // (reported through crth_last_error like the host-only refusals)
     return Renderer::TraceRays(*rays, mode, out, stream) ? 1 : 0;
 }
+int crth_trace_ao(const CrtAoPoints* points, const CrtAoParams* params, float* out, void* stream)
+{
+    if (hostOnly) { hostOnlyError = CRT_E_NOT_INITIALIZED; return 0; }
+    if (!points || !params) { hostOnlyError = CRT_E_BAD_ARGUMENT; return 0; }
+    return Renderer::TraceAmbientOcclusion(*points, *params, out, stream) ? 1 : 0;
+}
+int crth_compute_ao(const CrtAoParams* params, void* stream)
+{
+    if (hostOnly) { hostOnlyError = CRT_E_NOT_INITIALIZED; return 0; }
+    if (!params) { hostOnlyError = CRT_E_BAD_ARGUMENT; return 0; }
+    return Renderer::ComputeAmbientOcclusion(*params, stream) ? 1 : 0;
+}
+const float* crth_map_ao(void) { if (hostOnly) { hostOnlyError = CRT_E_NOT_INITIALIZED; return nullptr; } return Renderer::MapAmbientOcclusion(); }
 const float* crth_map_output(void) { return hostOnly ? nullptr : Renderer::MapOutput(); }
 float crth_last_frame_ms(void) { return hostOnly ? -1.0f : Renderer::LastFrameMs(); }
 

@@ -221,6 +221,54 @@ int crt_query_hits(const float* origins, const float* dirs, int n, uint32_t numI
 enum { CRT_RAYS_CLOSEST = 0, CRT_RAYS_OCCLUDED = 1 };
 int crt_trace_rays(const CrtRayBatch* rays, uint32_t numInstances, int mode, void* out, void* stream);
 
+/* Ambient occlusion (no reference counterpart: upstream's ambient term is the flat max(-ndl, 0.1) * atmosphere of kernel_main.cl:262), for
+ * points on the device (crt_trace_ao) and for the pixels of the most recently submitted CRT_RENDER_GBUFFER frame (crt_frame_ao). One fused
+ * kernel generates the sample rays in registers, traces them with the any-hit traversal of crt_trace_rays(CRT_RAYS_OCCLUDED) and reduces per
+ * item: no ray is materialised. Every value is defined in float32 arithmetic without contraction; dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *
+ * Direction table  T[256], unit vectors, spherical Fibonacci in index order: in double precision z_i = 1 - (2i + 1) / 256,
+ *   phi_i = i * pi * (3 - sqrt 5), T_i = (sqrt(1 - z^2) cos phi, sqrt(1 - z^2) sin phi, z), rounded to float32 once by tools/make_ao_table.py
+ *   (committed as literals: csrc/crt_ao_table.h). crt_ao_directions copies the 256 xyz triples out: a pure function, needs no device.
+ * Per item k (the point's index; y * W + x for a pixel) with position P, normal n and CrtAoParams {samples = N, radius = R, bias, seed}:
+ *   1. h = lowbias32(k ^ (seed * 0x9E3779B9u)); lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (uint32).
+ *   2. o = P + n * bias (a multiply, then an add, per component): the origin of every sample ray.
+ *   3. for s = 0 .. N-1: j = (h + s * (256 / N)) & 255; d = T[j] with x, y, z negated where bits 8, 9, 10 of h are set, then all of d negated
+ *      if dot3(d, n) < 0; w = dot3(d, n) of the final d; occ = exactly what crt_trace_rays(CRT_RAYS_OCCLUDED) answers for the ray
+ *      (o, d, tmax = R) -- the same bound rule B, the same any-hit form -- as 1.0f or 0.0f; num += w * occ; den += w, in this order.
+ *   4. ao = den > 0 ? 1 - num / den : 1.            1 = open, 0 = every weighted sample occluded.
+ *   5. an item whose normal is exactly (0, 0, 0) traces nothing and gets 1.0f. NaNs get what these expressions give.
+ * Frame form: dir = the pixel's RayGen direction (kernel_main.cl:277-287) from the matrices of that G-buffer frame, t and the normal from its
+ *   GEOMETRY plane: P = cameraPos + dir * t, n = the plane's normal turned towards the viewer (dot3(n, dir) > 0 ? -n : n). A miss pixel
+ *   (t > 99998: a miss carries t = 99999 and a zero normal) gets 1.0f.
+ * CRT_AO_FILTER (frame form only): a second small kernel writes the AO plane from the raw one -- for a hit centre pixel c the 5 x 5 window
+ *   clipped to the frame, dy = -2..2 outside, dx = -2..2 inside: m = 1 for the centre; m = 1 for a hit neighbour with
+ *   fabsf(t_n - t_c) <= filterDepthTol * t_c and dot3(n_n, n_c) >= filterNormalCos (the plane's normals as stored); else m = 0;
+ *   sum += ao * m; cnt += m; the result is sum / cnt. Miss pixels stay 1.0f. Refused (CRT_E_UNSUPPORTED) while crt_set_row_bands leaves this
+ *   rank a share of the rows: the window crosses band edges.
+ *
+ * crt_trace_ao follows crt_trace_rays in every respect: it ENQUEUES AND RETURNS on the caller's stream, in the ray queries' context -- one
+ * query at a time (the stream waits, on the device, for the query before, of either kind), instance tables refreshed behind the query
+ * before, an overflow area owned per workgroup, CRT_RAYS_GRID caps the persistent grid; whatever waits for the ray query in flight also waits
+ * for an AO query. positions / normals / out (n floats) are device-accessible; strides in floats, 0 = one value for every point. A ray origin
+ * beyond the cull's proven range costs only its 64-point chunk (8 x 8 tile) the instance cull. The colour frame, the G-buffer planes, the work
+ * counters and noCullFrames are not touched. n == 0: CRT_OK, no pointer is looked at. Errors, all before anything is enqueued:
+ * CRT_E_NOT_INITIALIZED; CRT_E_BAD_ARGUMENT (points or params NULL; samples not one of 1, 2, 4, 8, 16, 32, 64; !(radius > 0), so a NaN too;
+ * a bias that is not finite; an unknown flag, CRT_AO_FILTER on the points form; positions, normals or out NULL; a stride of 1 or 2;
+ * numInstances > 401; an invalid scene); CRT_E_OUT_OF_RANGE (n > 2^30); CRT_E_UNSUPPORTED (a session of several devices).
+ * crt_frame_ao: the same context and ordering, against the instances that frame was rendered with (as last uploaded). In addition the caller's
+ * stream waits, on the device, for the G-buffer frame it reads, and a later G-buffer frame into the same frame slot waits, on the device, for
+ * the AO query: pipelined frames get no host wait. The AO plane -- float, W x H, row-major -- belongs to the frame slot and is allocated by the
+ * slot's first crt_frame_ao (the one host wait); under crt_set_row_bands only this rank's rows are written. CRT_E_BAD_ARGUMENT when no
+ * G-buffer frame has been submitted since crt_init or the last crt_resize that changed the frame (when crt_read_gbuffer refuses).
+ * crt_read_ao (floats = width * height, after waiting for the frames and the query in flight) and crt_ao_device_ptr refer to the most recent
+ * crt_frame_ao and refuse (CRT_E_BAD_ARGUMENT / NULL) when there is none since crt_init or such a crt_resize. */
+enum { CRT_AO_FILTER = 1 };
+int crt_ao_directions(float out[768]);
+int crt_trace_ao(const CrtAoPoints* points, const CrtAoParams* params, uint32_t numInstances, float* out, void* stream);
+int crt_frame_ao(const CrtAoParams* params, void* stream);
+int crt_read_ao(float* dst, size_t floats);                   /* width*height */
+void* crt_ao_device_ptr(void);
+
 /* Output: the HDR float4 frame (the reference writes a CL-GL RGBA8 texture, Renderer.cpp:63,192). */
 int crt_read_output(float* dstRGBA, size_t floats);           /* full frame, width*height*4 floats */
 int crt_read_output_rows(float* dstRGBA, int row0, int rows); /* rows [row0,row0+rows) */

@@ -54,6 +54,10 @@ int crt_debug_tlas_stats(uint64_t* builds, uint32_t* refitsSinceBuild, uint32_t*
  * origin beyond the cull's proven range, or NaN), workgroups launched }. The launch is a persistent grid -- min(chunks, CUs x resident
  * workgroups per CU, CRT_RAYS_GRID) workgroups claim the chunks from a device counter. Zeros before the first query. */
 int crt_debug_rays_stats(uint64_t out[3]);
+/* Diagnostic: the last crt_trace_ao / crt_frame_ao launch, after waiting for it: out = { chunks (64 points, or one 8 x 8 pixel tile of the
+ * rows this rank owns), chunks traced without the instance cull (a tracing item's ray origin beyond the cull's proven range, or NaN),
+ * workgroups launched } -- the same persistent grid as crt_debug_rays_stats describes, with its own counters. Zeros before the first. */
+int crt_debug_ao_stats(uint64_t out[3]);
 /* Diagnostic: device buffers, pinned host buffers, events and streams the library holds in this process right now (every one is
  * counted when it is created and when it is released). Works without a session: 0 before the first crt_init and again after
  * crt_shutdown -- what the tests use to see that a session leaves nothing behind (tests/test_gpu_resources.py). */

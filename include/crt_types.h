@@ -92,6 +92,26 @@ typedef struct CrtRayBatch {
     uint64_t n;
 } CrtRayBatch;
 
+/* Ambient occlusion (crt_trace_ao, crt_frame_ao; definition in include/crt_api.h). */
+typedef struct CrtAoParams {
+    uint32_t samples;                 /* N: 1, 2, 4, 8, 16, 32 or 64 sample rays per item */
+    float radius;                     /* R > 0: how far an occluder counts (the sample rays' tmax; their directions are unit vectors) */
+    float bias;                       /* finite: the ray origin is lifted off the surface by normal * bias */
+    uint32_t seed;                    /* decorrelates calls; the same seed gives the same bits */
+    uint32_t flags;                   /* CRT_AO_FILTER (crt_frame_ao only) or 0 */
+    float filterDepthTol;             /* CRT_AO_FILTER: a neighbour counts when |t_n - t_c| <= filterDepthTol * t_c ... */
+    float filterNormalCos;            /* ... and dot(n_n, n_c) >= filterNormalCos */
+} CrtAoParams;
+
+/* n points on the device for crt_trace_ao. Strides are in floats: 0 = every point shares element 0, otherwise >= 3. */
+typedef struct CrtAoPoints {
+    const float* positions;           /* device-accessible; point k is positions[k * positionStride + 0..2] */
+    const float* normals;             /* device-accessible; normals[k * normalStride + 0..2]; (0, 0, 0): the point traces nothing and gets 1 */
+    uint32_t positionStride;
+    uint32_t normalStride;
+    uint64_t n;
+} CrtAoPoints;
+
 /* One pixel of the three first-hit planes of a CRT_RENDER_GBUFFER frame (crt_pick_pixel; crt_api.h describes the planes):
  * hit: record.normal (kernel_main.cl:236), the hit record as CrtRayHit holds it, 0xFF000000 | b << 16 | g << 8 | r of record.color;
  * miss: normal 0, t = 99999, instance -1, everything else 0. */
@@ -128,6 +148,7 @@ static_assert(sizeof(CrtMeshInstance) == 80, "MeshInstance must be 80 B");
 static_assert(sizeof(CrtTraceArgs) == 24, "TraceArgs must be 24 B");
 static_assert(sizeof(CrtGBufferPixel) == 36, "GBufferPixel must be 36 B (16 + 16 + 4, the three planes)");
 static_assert(sizeof(CrtRayHit) == 20 && sizeof(CrtRayBatch) == 40, "RayHit must be 20 B, RayBatch 40 B");
+static_assert(sizeof(CrtAoParams) == 28 && sizeof(CrtAoPoints) == 32, "AoParams must be 28 B, AoPoints 32 B");
 #endif
 #endif
 

@@ -1,0 +1,191 @@
+"""Ambient occlusion (crt_trace_ao / crt_frame_ao), the part that needs no GPU: the direction table and its generator, the ABI before
+crt_init, and a physics check of the DEFINITION (tests/ao_ref.py over the C oracle's records) on a scene whose answer is known.
+Definition: include/crt_api.h (crt_trace_ao)."""
+import ctypes as C
+import importlib.util
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from clraytracer_amd import _lib, driver, scenes
+import ao_ref
+import oracle_lib
+from test_abi import declared
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GENERATOR = os.path.join(ROOT, "tools", "make_ao_table.py")
+HEADER = os.path.join(ROOT, "clraytracer_amd", "csrc", "crt_ao_table.h")
+
+
+def _generator():
+    spec = importlib.util.spec_from_file_location("make_ao_table", GENERATOR)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_table_rows_are_unit_vectors_of_the_generators_formula():
+    t = ao_ref.table()
+    assert t.shape == (256, 3) and t.dtype == np.float32
+    length = np.sqrt((t.astype(np.float64) ** 2).sum(axis=1))
+    ulp = float(np.spacing(np.float32(1.0)))
+    assert np.abs(length - 1.0).max() <= 2 * ulp, np.abs(length - 1.0).max()
+    want = np.array(_generator().directions(), np.float64)
+    assert want.shape == (256, 3) and np.abs(t.astype(np.float64) - want).max() <= 1e-7
+    # the formula itself: z descends in equal steps, the azimuth advances by the golden angle
+    assert np.allclose(want[:, 2], 1.0 - (2 * np.arange(256) + 1) / 256.0, atol=0, rtol=0)
+    assert _lib.hip().crt_ao_directions(None) == _lib.CRT_E_BAD_ARGUMENT
+
+
+def test_generator_reproduces_the_committed_header():
+    p = subprocess.run([sys.executable, GENERATOR, "--stdout"], stdout=subprocess.PIPE, check=True)
+    assert p.stdout == open(HEADER, "rb").read()
+
+
+def test_abi_declares_the_ao_entry_points_and_they_refuse_before_init():
+    api, dbg, host = declared("crt_api.h", "crt_"), declared("crt_debug.h", "crt_"), declared("crt_host.h", "crth_")
+    for n in ("crt_ao_directions", "crt_trace_ao", "crt_frame_ao", "crt_read_ao", "crt_ao_device_ptr"):
+        assert n in api, n
+    assert "crt_debug_ao_stats" in dbg and all(n in host for n in ("crth_trace_ao", "crth_compute_ao", "crth_map_ao"))
+    assert C.sizeof(_lib.CrtAoParams) == 28 and C.sizeof(_lib.CrtAoPoints) == 32 and _lib.CRT_AO_FILTER == 1
+    hip = _lib.hip()
+    # no crt_init has been made in this process (tests/test_abi.py relies on the same)
+    pts = _lib.CrtAoPoints(None, None, 3, 3, 64)
+    par = _lib.CrtAoParams(8, 1.0, 1e-3, 0, 0, 0.0, 0.0)
+    out = np.zeros(64, np.float32)
+    assert hip.crt_trace_ao(C.byref(pts), C.byref(par), 1, out.ctypes.data, None) == _lib.CRT_E_NOT_INITIALIZED
+    assert hip.crt_frame_ao(C.byref(par), None) == _lib.CRT_E_NOT_INITIALIZED
+    assert hip.crt_read_ao(out.ctypes.data, out.size) == _lib.CRT_E_NOT_INITIALIZED
+    assert hip.crt_ao_device_ptr() is None
+    assert hip.crt_debug_ao_stats((C.c_uint64 * 3)()) == _lib.CRT_E_NOT_INITIALIZED
+    assert ao_ref.table().shape == (256, 3)                                   # the table needs no session
+
+
+def test_every_build_recipe_links_the_ao_unit():
+    found = 0
+    for rel in ("Makefile", "INTEGRATION.md", os.path.join("tools", "ab_build.sh"), os.path.join("tools", "ab_define.sh")):
+        text = open(os.path.join(ROOT, rel)).read().replace("\\\n", " ")
+        for line in text.splitlines():
+            if "-shared" in line and "crt_shim.hip" in line:
+                found += 1
+                assert "crt_ao.hip" in line, (rel, line)
+    assert found >= 4
+
+
+def test_session_refuses_tensors_and_parameters_it_cannot_hand_to_the_device():
+    import torch
+    with driver.Session(64, 48, host_only=True) as s:
+        s.load_scene(scenes.get("tiny"))
+        good = torch.zeros(8, 3, dtype=torch.float32)
+        with pytest.raises(TypeError):                       # radius and bias have no default
+            s.trace_ao(good, good)
+        with pytest.raises(ValueError):
+            s.trace_ao(torch.zeros(8, 3, dtype=torch.float64), good, radius=1.0, bias=1e-3)
+        with pytest.raises(ValueError):
+            s.trace_ao(good, torch.zeros(7, 3, dtype=torch.float32), radius=1.0, bias=1e-3)
+        with pytest.raises(ValueError):                      # CPU tensors: not the session's device (and no call into the library)
+            s.trace_ao(good, good, radius=1.0, bias=1e-3)
+        assert s.h.crth_last_error() == 0
+        with pytest.raises(_lib.CrtError):                   # a host-only session has no device
+            s.ambient_occlusion(radius=1.0, bias=1e-3)
+        assert s.h.crth_last_error() == 0
+
+
+def test_reference_restates_the_hash_and_the_hemisphere_rule():
+    t = ao_ref.table()
+    # by hand, in Python integers
+    def lb(x):
+        x ^= x >> 16; x = (x * 0x7feb352d) & 0xFFFFFFFF; x ^= x >> 15; x = (x * 0x846ca68b) & 0xFFFFFFFF; x ^= x >> 16
+        return x
+    ks = np.array([0, 1, 2, 63, 64, 4098, 0x7FFFFFFF, 0xFFFFFFFF], np.uint32)
+    assert [int(x) for x in ao_ref.lowbias32(ks)] == [lb(int(k)) for k in ks]
+    rng = np.random.RandomState(3)
+    n = rng.normal(size=(32, 3)).astype(np.float32)
+    P = rng.normal(size=(32, 3)).astype(np.float32)
+    k = np.arange(32, dtype=np.uint32) * 977
+    for N in (1, 8, 64):
+        par = {"samples": N, "bias": 0.25, "seed": 5}
+        o, d, w = ao_ref.rays(P, n, k, par, t)
+        assert o.shape == (32, 3) and d.shape == (32, N, 3) and w.shape == (32, N)
+        assert np.array_equal(o, P + n * np.float32(0.25)) and (w >= 0).all()
+        h = [lb(int(kk) ^ ((5 * 0x9E3779B9) & 0xFFFFFFFF)) for kk in k]
+        for i in (0, 7, 31):
+            for s in (0, N - 1):
+                row = t[(h[i] + s * (256 // N)) & 255].copy()
+                for c, bit in enumerate((8, 9, 10)):
+                    if (h[i] >> bit) & 1:
+                        row[c] = -row[c]
+                assert np.array_equal(np.abs(d[i, s]), np.abs(row)) and (np.array_equal(d[i, s], row) or np.array_equal(d[i, s], -row))
+    # a zero normal weighs nothing: AO 1 whatever occludes
+    o, d, w = ao_ref.rays(P[:2], np.zeros((2, 3), np.float32), k[:2], {"samples": 8, "bias": 0.0, "seed": 0}, t)
+    assert (w == 0).all() and np.array_equal(ao_ref.compose(w, np.ones_like(w)), np.ones(2, np.float32))
+
+
+def _corner_scene(tmp_path, wall):
+    """A 6 x 6 floor through the origin (normal +y) and, with `wall`, a 6 x 3 wall standing on it in the plane z = 0 (normal +z): two meshes,
+    one instance each, every one leaning by 0.002 rad. Upstream's slab test (kernel_main.cl:108-117) enters a box only for tnear < tfar and
+    tnear > 0: a box of zero thickness is never entered (hence the lean), and neither is a box the ray starts in (hence a wall of its own,
+    whose 0.006-thick boxes the sample rays start outside of)."""
+    d = str(tmp_path)
+    sky = os.path.join(d, "sky.ppm")
+    scenes.write_ppm(sky, scenes._skybox(64, 32))
+    lean = 0.002
+    Rx = np.array([[1, 0, 0], [0, np.cos(lean), -np.sin(lean)], [0, np.sin(lean), np.cos(lean)]])
+    parts = [scenes._grid((-3, 0, 3), (6, 0, 0), (0, 0, -6), 6, 6, (0, 1, 0))]
+    if wall:
+        parts.append(scenes._grid((-3, 0, 0), (6, 0, 0), (0, 3, 0), 6, 3, (0, 0, 1)))
+    objs = []
+    for i, m in enumerate(parts):
+        m.pos = (m.pos.astype(np.float64) @ Rx.T).astype(np.float32)
+        m.nrm = (m.nrm.astype(np.float64) @ Rx.T).astype(np.float32)
+        objs.append(scenes._write_mesh(d, "part%d" % i, m, [((0.7, 0.7, 0.7), None)]))
+    inst = [scenes.Instance(i, 0xFFFF, np.eye(4, dtype=np.float32)) for i in range(len(objs))]
+    sc = scenes.Scene("ao-corner", d, sky, objs, inst, (0.0, 1.0, 3.0), (0.0, 0.0, -1.0))
+    with driver.Session(64, 48, host_only=True) as s:
+        s.load_scene(sc)
+        a = {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in s.arenas().items()}
+    return a, Rx
+
+
+def _reference_ao(a, P, n, k, par, nthreads):
+    """ao_ref.compose over the oracle's unbounded records filtered by t < R (trace_rays_ref.filtered's rule)"""
+    t = ao_ref.table()
+    o, d, w = ao_ref.rays(P, n, k, par, t)
+    N = par["samples"]
+    rec, _ = oracle_lib.Oracle(a, nthreads=nthreads).closest_hits(np.repeat(o, N, axis=0), d.reshape(-1, 3))
+    assert np.isfinite(rec["u"]).all() and np.isfinite(rec["v"]).all()
+    occ = ((rec["instance"] >= 0) & (rec["t"] < np.float32(par["radius"]))).reshape(len(o), N)
+    return ao_ref.compose(w, occ), occ
+
+
+K0, COUNT = 1000, 256
+
+
+def test_open_floor_is_exactly_one(tmp_path, nthreads):
+    a, R = _corner_scene(tmp_path, wall=False)
+    P = np.tile((np.array([0.3, 0.0, 1.1]) @ R.T).astype(np.float32), (COUNT, 1))
+    n = np.tile((np.array([0.0, 1.0, 0.0]) @ R.T).astype(np.float32), (COUNT, 1))
+    par = {"samples": 64, "radius": 1.0, "bias": 1e-3, "seed": 0}
+    ao, occ = _reference_ao(a, P, n, np.arange(K0, K0 + COUNT, dtype=np.uint32), par, nthreads)
+    assert not occ.any() and np.array_equal(ao, np.ones(COUNT, np.float32))
+
+
+def test_foot_of_a_wall_is_one_half(tmp_path, nthreads):
+    """A point on the floor 0.02 in front of a perpendicular wall, both reaching farther than R = 1 in every direction: the wall covers the
+    half of the hemisphere behind its plane, whose cosine-weighted share is exactly 1/2 -- minus the sliver of rays within 1.15 degrees of
+    the wall's plane, which leave the radius before they arrive (0.02 / R of that half's directions in the plane of incidence: AO a little
+    above 1/2).
+    Measured here on the CPU, N = 64, items k = 1000 .. 1255: mean 0.509868, |mean - 0.5| = 9.868e-3; every single item lies within 0.0180
+    of 0.5; 0.4913 of the sample rays are occluded. The assertion allows twice the measured deviation of the mean."""
+    a, R = _corner_scene(tmp_path, wall=True)
+    P = np.tile((np.array([0.3, 0.0, 0.02]) @ R.T).astype(np.float32), (COUNT, 1))
+    n = np.tile((np.array([0.0, 1.0, 0.0]) @ R.T).astype(np.float32), (COUNT, 1))
+    par = {"samples": 64, "radius": 1.0, "bias": 1e-3, "seed": 0}
+    ao, occ = _reference_ao(a, P, n, np.arange(K0, K0 + COUNT, dtype=np.uint32), par, nthreads)
+    mean = float(ao.astype(np.float64).mean())
+    print(f"mean AO at the foot of the wall: {mean:.6f} (|mean - 0.5| = {abs(mean - 0.5):.3e}); items within {np.abs(ao - 0.5).max():.4f} of 0.5; "
+          f"{occ.mean():.4f} of the sample rays occluded")
+    assert abs(mean - 0.5) <= 2 * 9.868e-3

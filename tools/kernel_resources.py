@@ -14,7 +14,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
-SOURCES = ("crt_shim.hip", "crt_rays.hip")     # the Makefile's units of libcrt_hip.so, in link order
+SOURCES = ("crt_shim.hip", "crt_rays.hip", "crt_ao.hip")     # the Makefile's units of libcrt_hip.so, in link order
 
 
 def kernel_resource_rows(defs=(), source=SOURCES[0]):

@@ -16,18 +16,6 @@ __device__ __forceinline__ uint32_t lowbias32(uint32_t x)
     return x;
 }
 
-// element k of a point array: three dwords per lane at the given stride, or (stride 0) one scalar load for the wave (as crt_rays.hip)
-__device__ __forceinline__ v3 load_point_xyz(const float* __restrict__ p, uint32_t stride, uint32_t k)
-{
-    if (stride == 0) {
-        typedef const float __attribute__((address_space(4)))* crt_const_f32_ptr;
-        const crt_const_f32_ptr q = (crt_const_f32_ptr)p;
-        return mk3(q[0], q[1], q[2]);
-    }
-    const float* e = p + (size_t)k * (size_t)stride;
-    return mk3(e[0], e[1], e[2]);
-}
-
 // FRAME: pixel of lane `lane` in chunk `chunk` -- tile chunk % tilesX of the chunk / tilesX'th tile row this rank owns (deal_tile's band
 // arithmetic without the XCD interleave: chunks are claimed, not dealt), rows of 8 pixels inside the tile
 __device__ __forceinline__ void ao_pixel(const CrtFrame& F, uint32_t chunk, uint32_t lane, int& px, int& py)
@@ -58,15 +46,13 @@ template <int SOURCE>
 __device__ __forceinline__ bool ao_item(const CrtAoArgs& A, const CrtFrame& F, uint32_t chunk, uint32_t lane, uint32_t& k, v3& P, v3& n)
 {
     P = mk3(0.0f, 0.0f, 0.0f); n = P;
+    if (!ao_index<SOURCE>(A, F, chunk, lane, k)) return false;
     if constexpr (SOURCE == CRT_AO_POINTS) {
-        if (!ao_index<SOURCE>(A, F, chunk, lane, k)) return false;
-        P = load_point_xyz(A.positions, A.positionStride, k);
-        n = load_point_xyz(A.normals, A.normalStride, k);
+        P = load_xyz(A.positions, A.positionStride, k);
+        n = load_xyz(A.normals, A.normalStride, k);
     } else {
         int px, py;
         ao_pixel(F, chunk, lane, px, py);
-        k = (uint32_t)py * (uint32_t)F.width + (uint32_t)px;
-        if (!(px < F.width && py < F.height)) return false;
         const float4 gm = A.geometry[k];
         if (gm.w > 99998.0f) return false;                        // a miss (t = 99999), or a hit beyond upstream's InfMinusOne: its normal is 0 anyway
         const v3 dir = raygen_dir(F, px, py);
@@ -83,13 +69,9 @@ __global__ __launch_bounds__(CRT_BLOCK, CRT_WAVES_PER_SIMD) void crt_ao_kernel(C
     __shared__ uint32_t s_stack[CRT_LDS_SLOTS * CRT_BLOCK];
     LaneCounters lc = {};                        // COUNT = false: never read
     for (;;) {
-        uint32_t chunk = 0;
-        if ((threadIdx.x & 63) == 0) chunk = atomicAdd(&A.ctl[0], 1u);
-        chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)chunk);
-        if (chunk >= A.chunks) break;
-        // (opaque per chunk and per sample, as in crt_rays_kernel: what derives from the lane number is recomputed where it is used)
-        uint32_t lane = threadIdx.x & 63u;
-        asm volatile("" : "+v"(lane));
+        uint32_t chunk;
+        if (claim_chunk(A.q, A.chunks, chunk)) break;
+        const uint32_t lane = opaque_lane();
         float ao = 1.0f;
         {
             uint32_t k; v3 P, n;
@@ -97,19 +79,14 @@ __global__ __launch_bounds__(CRT_BLOCK, CRT_WAVES_PER_SIMD) void crt_ao_kernel(C
             if (__ballot(traces) != 0 && traces) {
                 // the chunk's cull decision, on the origin every sample of the lane shares
                 const v3 o0 = add3(P, scale3(n, A.bias));
-                const bool beyond = !(sqrt((double)o0.x * (double)o0.x + (double)o0.y * (double)o0.y + (double)o0.z * (double)o0.z) <= A.cullOriginLimit);
-                const bool noCull = __ballot(beyond) != 0;          // wave-uniform
                 CrtDevScene S = S0;
-                if (noCull) {
-                    S.instBounds = A.noCullBounds; S.tlas = nullptr; S.tlasNodes = 0; S.alwaysList = nullptr; S.numAlways = 0;
-                    if ((int)lane == __ffsll((long long)__ballot(1)) - 1) atomicAdd(&A.ctl[1], 1u);      // one vector atomic per affected chunk
-                }
-                const float best0 = !(A.radius >= 99999.0f) ? A.radius : 99999.0f;      // crt_trace_rays' bound B for tmax = radius
+                const bool noCull = cull_decision(A.q, o0, lane, S);
+                const float best0 = query_bound(A.radius);
                 float num = 0.0f, den = 0.0f;
                 for (uint32_t s = 0; s < A.samples; ++s) {
                     // the item once more (an L1 hit), behind the traversal of the sample before
-                    uint32_t chunk2 = chunk, lane2 = threadIdx.x & 63u;
-                    asm volatile("" : "+s"(chunk2), "+v"(lane2));
+                    uint32_t chunk2 = chunk, lane2;
+                    chunk_lane_again(chunk2, lane2);
                     uint32_t k2; v3 P2, n2;
                     (void)ao_item<SOURCE>(A, F, chunk2, lane2, k2, P2, n2);
                     const v3 o = add3(P2, scale3(n2, A.bias));
@@ -128,8 +105,8 @@ __global__ __launch_bounds__(CRT_BLOCK, CRT_WAVES_PER_SIMD) void crt_ao_kernel(C
             }
         }
         // the item's index once more, behind the traversals
-        uint32_t chunk3 = chunk, lane3 = threadIdx.x & 63u;
-        asm volatile("" : "+s"(chunk3), "+v"(lane3));
+        uint32_t chunk3 = chunk, lane3;
+        chunk_lane_again(chunk3, lane3);
         uint32_t k3;
         if (ao_index<SOURCE>(A, F, chunk3, lane3, k3)) A.out[k3] = ao;
     }

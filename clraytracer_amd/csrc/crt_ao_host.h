@@ -1,6 +1,6 @@
 // crt_ao_host.h -- ambient occlusion on device points and on G-buffer frames: crt_trace_ao, crt_frame_ao, the AO plane's reads, statistics
-// Part of the one translation unit crt_shim.hip (included there behind crt_frame.h, whose query context and helpers it uses); everything
-// here has internal linkage. The kernels: crt_ao.h (declared), crt_ao.hip (compiled).
+// Part of the one translation unit crt_shim.hip (included there behind crt_query_host.h, whose launch_query and query_stats it uses);
+// everything here has internal linkage. The kernels: crt_ao.h (declared), crt_ao.hip (compiled).
 #pragma once
 namespace {
 
@@ -21,48 +21,14 @@ static int check_ao_params(const CrtAoParams* p, uint32_t allowed)
     return CRT_OK;
 }
 
-// workgroups of crt_ao_kernel<frame ? FRAME : POINTS, tlas> a CU holds at once (asked once per instantiation)
-static int ao_resident_per_cu(bool frame, bool tlas, int& out)
-{
-    int& cached = g.rayQuery.aoResidentPerCU[2 * (int)frame + (int)tlas];
-    if (cached == 0) {
-        int n = 0;
-        hipError_t e = hipSuccess;
-        with_bools([&](auto Fr, auto Tl) {
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, crt_ao_kernel<decltype(Fr)::value ? CRT_AO_FRAME : CRT_AO_POINTS, decltype(Tl)::value>, CRT_BLOCK, 0);
-        }, frame, tlas);
-        HIPCHK(e);
-        cached = n > 0 ? n : 1;
-    }
-    out = cached;
-    return CRT_OK;
-}
-
-// The launch both forms share, as a query on the ray queries' context (query_scene / query_grid / end_query of crt_frame.h): `A` holds the
-// form's own arguments, `before(stream)` queues what the kernel must wait for, `after(stream)` what belongs to the query behind it.
+// The launch both forms share, a query of the AO family (launch_query): `A` holds the form's own arguments, the parameters are filled here
+typedef void CrtAoKernel(CrtDevScene, CrtAoArgs, CrtFrame);
+static CrtAoKernel* const kAoKernels[4] = { crt_ao_kernel<CRT_AO_POINTS, false>, crt_ao_kernel<CRT_AO_POINTS, true>, crt_ao_kernel<CRT_AO_FRAME, false>, crt_ao_kernel<CRT_AO_FRAME, true> };
 template <class Before, class After>
 static int launch_ao(bool frame, CrtAoArgs A, const CrtFrame& F, const CrtAoParams& p, uint32_t numInstances, uint64_t chunks, hipStream_t stream, Before&& before, After&& after)
 {
-    CrtDevScene S;
-    RCCHK(query_scene(numInstances, S));
-    const bool tlas = use_tlas(S);
-    int perCU = 1;
-    RCCHK(ao_resident_per_cu(frame, tlas, perCU));
-    uint64_t grid = 0;
-    RCCHK(query_grid(chunks, perCU, stream, S, grid));
-    QueryContext& q = g.rayQuery;
-    RCCHK(before(stream));
-    HIPCHK(hipMemsetAsync(q.ctl + 2, 0, 2 * sizeof(uint32_t), stream));
-    A.ctl = q.ctl + 2; A.noCullBounds = g.noCullBounds; A.cullOriginLimit = (double)g.cullOriginLimit; A.chunks = (uint32_t)chunks;
     A.samples = p.samples; A.step = CRT_AO_TABLE_SIZE / p.samples; A.seedMul = p.seed * 0x9E3779B9u; A.radius = p.radius; A.bias = p.bias;
-    with_bools([&](auto Fr, auto Tl) {
-        crt_ao_kernel<decltype(Fr)::value ? CRT_AO_FRAME : CRT_AO_POINTS, decltype(Tl)::value><<<(unsigned)grid, CRT_BLOCK, 0, stream>>>(S, A, F);
-    }, frame, tlas);
-    HIPCHK(hipGetLastError());
-    RCCHK(after(stream));
-    RCCHK(end_query(stream));
-    q.aoChunks = chunks; q.aoGrid = grid;
-    return CRT_OK;
+    return launch_query(g.rayQuery.ao, kAoKernels, frame, numInstances, chunks, stream, before, after, A, F);
 }
 
 // Enqueue-and-return like crt1_trace_rays: every check comes before the first thing that is queued.
@@ -80,8 +46,7 @@ int crt1_trace_ao(const CrtAoPoints* pts, const CrtAoParams* params, uint32_t nu
     A.positions = pts->positions; A.normals = pts->normals; A.positionStride = pts->positionStride; A.normalStride = pts->normalStride;
     A.out = out; A.n = (uint32_t)pts->n;
     CrtFrame F; memset(&F, 0, sizeof F);
-    auto nothing = [](hipStream_t) { return (int)CRT_OK; };
-    return launch_ao(false, A, F, *params, numInstances, (pts->n + CRT_BLOCK - 1) / CRT_BLOCK, stream, nothing, nothing);
+    return launch_ao(false, A, F, *params, numInstances, (pts->n + CRT_BLOCK - 1) / CRT_BLOCK, stream, no_query_step, no_query_step);
 }
 
 // The slot of the most recently submitted G-buffer frame, if its planes exist (what crt_read_gbuffer asks too)
@@ -143,20 +108,6 @@ int crt1_read_ao(float* dst, size_t floats)
 
 void* crt1_ao_device_ptr(void) { return g.initialized ? (void*)ao_plane() : nullptr; }
 
-// {chunks, chunks traced without the cull, workgroups launched} of the last AO query, after waiting for it
-int crt1_debug_ao_stats(uint64_t out[3])
-{
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (!out) return CRT_E_BAD_ARGUMENT;
-    QueryContext& q = g.rayQuery;
-    out[0] = q.aoChunks; out[1] = 0; out[2] = q.aoGrid;
-    if (!q.ready || q.aoChunks == 0) return CRT_OK;
-    HIPCHK(hipEventSynchronize(q.raysDone));
-    q.inFlight = false;
-    uint32_t ctl[2] = { 0, 0 };
-    HIPCHK(hipMemcpy(ctl, q.ctl + 2, sizeof ctl, hipMemcpyDeviceToHost));
-    out[1] = ctl[1];
-    return CRT_OK;
-}
+int crt1_debug_ao_stats(uint64_t out[3]) { return query_stats(&QueryContext::ao, out); }
 
 } // namespace

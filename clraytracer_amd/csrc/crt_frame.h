@@ -1,6 +1,6 @@
-// crt_frame.h -- one frame: feedback launch lists, the Trace launch by kernel structure, frame slots and events (Renderer.cpp:305-375), queries, reads, statistics
+// crt_frame.h -- one frame: feedback launch lists, the Trace launch by kernel structure, frame slots and events (Renderer.cpp:305-375), the host-memory query (crt_query_hits), reads, statistics
 // Part of the one translation unit crt_shim.hip (included there, in this order: crt_own.h, crt_state.h, crt_instances.h, crt_upload.h,
-// crt_bvh_driver.h, crt_frame.h, crt_multidev.h); everything here has internal linkage.
+// crt_bvh_driver.h, crt_frame.h, crt_query_host.h, crt_ao_host.h, crt_multidev.h); everything here has internal linkage.
 #pragma once
 namespace {
 
@@ -669,133 +669,6 @@ int crt1_query_hits(const float* origins, const float* dirs, int n, uint32_t num
     HIPCHK(hipMemcpyAsync(c, g.counters, sizeof c, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
     unpack_counters(c);
-    return CRT_OK;
-}
-
-// ---- ray queries on device buffers (crt_trace_rays; State::rayQuery, crt_rays_kernel) ----
-#define CRT_RAYS_MAX ((uint64_t)1 << 30)
-
-// first query of the session: the context's stream, tables, control words and event (the one allocation a query may wait for, besides a
-// growing overflow area)
-static int ensure_ray_query_context()
-{
-    QueryContext& q = g.rayQuery;
-    if (q.ready) return CRT_OK;
-    if (!q.tables.stream) RCCHK(q.tables.stream.create(hipStreamNonBlocking));
-    if (!q.tables.instBlock) RCCHK(create_slot_tables(q.tables));
-    if (!q.ctl) RCCHK(q.ctl.alloc(4));
-    if (!q.raysDone) RCCHK(q.raysDone.create(hipEventDisableTiming));
-    q.ready = true;
-    return CRT_OK;
-}
-
-// The three steps every query on the context shares (crt_trace_rays, crt_trace_ao, crt_frame_ao); all of the caller's checks come first.
-// 1. The scene as the query sees it: the context exists, its instance tables are current -- an instance upload since the last query is
-//    refreshed on the context's own stream behind the query that may still read the old tables.
-static int query_scene(uint32_t numInstances, CrtDevScene& S)
-{
-    RCCHK(ensure_ray_query_context());
-    QueryContext& q = g.rayQuery;
-    SlotTables& fs = q.tables;
-    if (fs.instVersion != g.instVersion) {
-        if (q.inFlight) HIPCHK(hipStreamWaitEvent(fs.stream, q.raysDone, 0));
-        q.refreshPending = true;               // until a raysDone lies behind it: a step that fails below must not leave it unseen by quiesce()
-        RCCHK(ensure_slot_instances(fs));
-    }
-    fill_scene(S, numInstances, fs);
-    return CRT_OK;
-}
-// 2. The persistent grid -- min(chunks, CUs x resident workgroups, CRT_RAYS_GRID) -- with an overflow block per workgroup (the host waits
-//    only when the area has to grow), and the caller's stream ordered, on the device, behind the query before and the table refresh.
-static int query_grid(uint64_t chunks, int perCU, hipStream_t stream, CrtDevScene& S, uint64_t& grid)
-{
-    QueryContext& q = g.rayQuery;
-    SlotTables& fs = q.tables;
-    grid = (uint64_t)g.numCUs * (uint64_t)perCU;
-    if (g.raysGridCap > 0 && grid > (uint64_t)g.raysGridCap) grid = (uint64_t)g.raysGridCap;
-    if (grid > chunks) grid = chunks;
-    if (grid * CRT_OVF_WORDS_PER_BLOCK > fs.ovf.capacity()) {
-        if (q.inFlight) { HIPCHK(hipEventSynchronize(q.raysDone)); q.inFlight = false; }      // the query before still owns the old area (grow() frees it)
-        RCCHK(ensure_overflow(fs, (size_t)grid));
-    }
-    S.stackOverflow = fs.ovf;
-    if (q.inFlight) HIPCHK(hipStreamWaitEvent(stream, q.raysDone, 0));
-    HIPCHK(hipStreamWaitEvent(stream, fs.staged, 0));
-    return CRT_OK;
-}
-// 3. Behind the query's last launch: the event the next query, and whatever edits shared device state (quiesce), waits for.
-static int end_query(hipStream_t stream)
-{
-    QueryContext& q = g.rayQuery;
-    HIPCHK(hipEventRecord(q.raysDone, stream));
-    q.inFlight = true; q.refreshPending = false;      // (raysDone lies behind `staged`: the stream waited for it)
-    return CRT_OK;
-}
-
-// workgroups of crt_rays_kernel<anyHit, tlas> a CU holds at once, as the runtime computes it for this device (asked once per instantiation)
-static int rays_resident_per_cu(bool anyHit, bool tlas, int& out)
-{
-    int& cached = g.rayQuery.residentPerCU[2 * (int)anyHit + (int)tlas];
-    if (cached == 0) {
-        int n = 0;
-        hipError_t e = hipSuccess;
-        with_bools([&](auto A, auto Tl) { e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, crt_rays_kernel<decltype(A)::value, decltype(Tl)::value>, CRT_BLOCK, 0); }, anyHit, tlas);
-        HIPCHK(e);
-        cached = n > 0 ? n : 1;
-    }
-    out = cached;
-    return CRT_OK;
-}
-
-// Enqueue-and-return: every check comes before the first thing that is queued; the host waits only for the context's first allocation and
-// for a growing overflow area. Ordering: the caller's stream waits (hipStreamWaitEvent) for the query before -- queries share the context
-// -- and for the context's instance tables, which are refreshed on the context's own stream behind that same query (it may still read the
-// old tables). Frames in flight are neither waited for nor touched.
-int crt1_trace_rays(const CrtRayBatch* rays, uint32_t numInstances, int mode, void* out, hipStream_t stream)
-{
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (!rays) return CRT_E_BAD_ARGUMENT;
-    if (rays->n == 0) return CRT_OK;
-    if (!rays->origins || !rays->dirs || !out) return CRT_E_BAD_ARGUMENT;
-    if (rays->originStride == 1 || rays->originStride == 2 || rays->dirStride == 1 || rays->dirStride == 2) return CRT_E_BAD_ARGUMENT;
-    if (mode != CRT_RAYS_CLOSEST && mode != CRT_RAYS_OCCLUDED) return CRT_E_BAD_ARGUMENT;
-    if (numInstances > CRT_MAX_INSTANCES || !g.sceneValid) return CRT_E_BAD_ARGUMENT;
-    if (rays->n > CRT_RAYS_MAX) return CRT_E_OUT_OF_RANGE;
-    const bool anyHit = mode == CRT_RAYS_OCCLUDED;
-    CrtDevScene S;
-    RCCHK(query_scene(numInstances, S));
-    const bool tlas = use_tlas(S);
-    const uint64_t chunks = (rays->n + CRT_BLOCK - 1) / CRT_BLOCK;
-    int perCU = 1;
-    RCCHK(rays_resident_per_cu(anyHit, tlas, perCU));
-    uint64_t grid = 0;
-    RCCHK(query_grid(chunks, perCU, stream, S, grid));
-    QueryContext& q = g.rayQuery;
-    HIPCHK(hipMemsetAsync(q.ctl, 0, 2 * sizeof(uint32_t), stream));
-    CrtRaysArgs A;
-    A.origins = rays->origins; A.dirs = rays->dirs; A.tmax = rays->tmax; A.out = out; A.ctl = q.ctl; A.noCullBounds = g.noCullBounds;
-    A.originStride = rays->originStride; A.dirStride = rays->dirStride; A.n = (uint32_t)rays->n; A.chunks = (uint32_t)chunks;
-    A.cullOriginLimit = (double)g.cullOriginLimit;
-    with_bools([&](auto An, auto Tl) { crt_rays_kernel<decltype(An)::value, decltype(Tl)::value><<<(unsigned)grid, CRT_BLOCK, 0, stream>>>(S, A); }, anyHit, tlas);
-    HIPCHK(hipGetLastError());
-    RCCHK(end_query(stream));
-    q.chunks = chunks; q.grid = grid;
-    return CRT_OK;
-}
-
-// {chunks, chunks traced without the cull, workgroups launched} of the last query, after waiting for it
-int crt1_debug_rays_stats(uint64_t out[3])
-{
-    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    if (!out) return CRT_E_BAD_ARGUMENT;
-    QueryContext& q = g.rayQuery;
-    out[0] = q.chunks; out[1] = 0; out[2] = q.grid;
-    if (!q.ready || q.chunks == 0) return CRT_OK;
-    HIPCHK(hipEventSynchronize(q.raysDone));
-    q.inFlight = false;
-    uint32_t ctl[2] = { 0, 0 };
-    HIPCHK(hipMemcpy(ctl, q.ctl, sizeof ctl, hipMemcpyDeviceToHost));
-    out[1] = ctl[1];
     return CRT_OK;
 }
 

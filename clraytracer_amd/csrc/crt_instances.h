@@ -1,6 +1,6 @@
 // crt_instances.h -- everything derived from the instance table and the root nodes: device records, bounding spheres and the cull range, the instance tree, per-slot copies
 // Part of the one translation unit crt_shim.hip (included there, in this order: crt_own.h, crt_state.h, crt_instances.h, crt_upload.h,
-// crt_bvh_driver.h, crt_frame.h, crt_multidev.h); everything here has internal linkage.
+// crt_bvh_driver.h, crt_frame.h, crt_query_host.h, crt_ao_host.h, crt_multidev.h); everything here has internal linkage.
 #pragma once
 namespace {
 

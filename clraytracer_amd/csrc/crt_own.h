@@ -1,6 +1,6 @@
 // crt_own.h -- owners of what the host side allocates: device buffers, pinned host buffers, events, streams
 // Part of the one translation unit crt_shim.hip (included there, in this order: crt_own.h, crt_state.h, crt_instances.h, crt_upload.h,
-// crt_bvh_driver.h, crt_frame.h, crt_multidev.h); everything here has internal linkage.
+// crt_bvh_driver.h, crt_frame.h, crt_query_host.h, crt_ao_host.h, crt_multidev.h); everything here has internal linkage.
 //
 // Four move-only types, the only callers of the HIP create / destroy functions in this directory. What a session creates is a member
 // of its State (or a local of the function that needs it) and is released exactly once, by the destructor: no list of things to free.

@@ -6,12 +6,12 @@
 // One translation unit (and crt_rays.hip, the ray-query kernel, and crt_ao.hip, the ambient-occlusion kernels, beside it); the parts (round 5 split what used to be one 2,000-line file):
 //   kernels     crt_device.h (traversal + shading), crt_kernels.h (launches), crt_refill.h (opt-in in-wave compaction forms), crt_ldstop.h (opt-in: tree tops staged in LDS),
 //               crt_relayout.h (upload-time layouts), crt_bvh_build.h (device BuildBVH); crt_rays.h declares the ray-query kernel of the second unit, crt_rays.hip,
-//               crt_ao.h the ambient-occlusion kernels of the third, crt_ao.hip
+//               crt_ao.h the ambient-occlusion kernels of the third, crt_ao.hip; crt_query.h: the steps those two units' kernels share
 //   host state  crt_own.h (the owners of device / pinned buffers, events and streams), crt_state.h (State / FrameSlot, helpers), crt_instances.h (instance tables, cull bounds, instance tree)
 //   entry impl  crt_upload.h (init, uploads, read-backs), crt_bvh_driver.h (crt_build_bvh), crt_frame.h (crt_render and what a frame
-//               needs), crt_ao_host.h (crt_trace_ao, crt_frame_ao), crt_multidev.h (several devices behind the same calls)
+//               needs), crt_query_host.h (the queries on device buffers: context, launch, statistics; crt_trace_rays), crt_ao_host.h (crt_trace_ao, crt_frame_ao), crt_multidev.h (several devices behind the same calls)
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared crt_shim.hip crt_rays.hip crt_ao.hip (the Makefile's rule; a library of this unit
-// alone links but does not load: crt_frame.h and crt_ao_host.h refer to the kernels the other two define)
+// alone links but does not load: crt_query_host.h and crt_ao_host.h refer to the kernels the other two define)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <cmath>
@@ -41,6 +41,7 @@
 #include "crt_upload.h"
 #include "crt_bvh_driver.h"
 #include "crt_frame.h"
+#include "crt_query_host.h"
 #include "crt_ao_host.h"
 
 #include "crt_multidev.h"

@@ -1,6 +1,6 @@
 // crt_state.h -- host state of one device session: frame slots, pools, the helpers every other part uses
 // Part of the one translation unit crt_shim.hip (included there, in this order: crt_own.h, crt_state.h, crt_instances.h, crt_upload.h,
-// crt_bvh_driver.h, crt_frame.h, crt_multidev.h); everything here has internal linkage.
+// crt_bvh_driver.h, crt_frame.h, crt_query_host.h, crt_ao_host.h, crt_multidev.h); everything here has internal linkage.
 #pragma once
 // ------------------------------------------------------------------------------------------------
 // host state
@@ -71,21 +71,26 @@ struct FrameSlot : SlotTables {
     bool frameIs8 = false;
 };
 
-// The context of the ray queries on device buffers (crt_trace_rays, crt_frame.h): queries never touch a frame slot, so they neither wait
-// for the frames in flight nor make them wait. `tables`: the context's own stream (the instance-table refresh runs there), its copy of
-// the instance tables with the staging block and `staged` event (ensure_slot_instances), and its overflow area, one block per workgroup
-// of the persistent grid. One query at a time: every launch makes the caller's stream wait for `raysDone` of the one before (no host
-// wait), and whatever edits shared device state waits for it on the host (quiesce).
+// One family of queries on the context below (crt_trace_rays; crt_trace_ao / crt_frame_ao): its pair of control words, what its last launch
+// was, and how many workgroups of each of its kernel's four instantiations a CU holds. Families share everything else of the context.
+struct QueryFamily {
+    uint32_t ctl0;                             // its words in QueryContext::ctl: [ctl0] chunk counter, [ctl0 + 1] chunks traced without the cull (CrtQueryArgs::ctl)
+    unsigned long long chunks = 0, grid = 0;   // of the family's last query (crt_debug_rays_stats, crt_debug_ao_stats)
+    int residentPerCU[4] = { 0, 0, 0, 0 };     // hipOccupancyMaxActiveBlocksPerMultiprocessor of the kernel<X, TLAS>, [2 * X + TLAS]; 0 = not asked yet
+};
+
+// The context of the queries on device buffers (crt_query_host.h): queries never touch a frame slot, so they neither wait for the frames
+// in flight nor make them wait. `tables`: the context's own stream (the instance-table refresh runs there), its copy of the instance
+// tables with the staging block and `staged` event (ensure_slot_instances), and its overflow area, one block per workgroup of the
+// persistent grid. One query at a time: every launch makes the caller's stream wait for `raysDone` of the one before (no host wait), and
+// whatever edits shared device state waits for it on the host (quiesce).
 struct QueryContext {
     SlotTables tables;
     bool ready = false;                        // allocated (by the first query)
-    DevBuf<uint32_t> ctl;                      // device: [0] chunk counter, [1] chunks traced without the cull (CrtRaysArgs::ctl); [2], [3]: the same of the AO queries (CrtAoArgs::ctl)
+    DevBuf<uint32_t> ctl;                      // device: four words, a pair per family
     Event raysDone; bool inFlight = false;     // recorded behind the last query on the caller's stream; inFlight: not yet known to be over
     bool refreshPending = false;               // a table refresh was queued on tables.stream and no raysDone covers it yet (a query that failed behind it): quiesce waits for tables.staged
-    unsigned long long chunks = 0, grid = 0;   // of the last query (crt_debug_rays_stats)
-    int residentPerCU[4] = { 0, 0, 0, 0 };     // hipOccupancyMaxActiveBlocksPerMultiprocessor of crt_rays_kernel<ANYHIT, TLAS>, [2 * ANYHIT + TLAS]; 0 = not asked yet
-    unsigned long long aoChunks = 0, aoGrid = 0;   // of the last AO query (crt_debug_ao_stats)
-    int aoResidentPerCU[4] = { 0, 0, 0, 0 };   // the same of crt_ao_kernel<SOURCE, TLAS>, [2 * SOURCE + TLAS]
+    QueryFamily rays = { 0 }, ao = { 2 };      // crt_rays_kernel<ANYHIT, TLAS>, crt_ao_kernel<SOURCE, TLAS>
 };
 
 // Whatever a State holds is released when it is deleted, with its device current: destroy_group (crt_multidev.h) is the only place.
@@ -151,7 +156,7 @@ struct State {
     DevBuf<float4> topPairs; DevBuf<uint32_t> topRootRefs;   // the tree-top table (CRT_TOP_PAIRS records) and every mesh's entry into it, rebuilt with the BVH layout
     char lastKernel[128] = { 0 };              // crt_debug_last_kernel: the Trace launch(es) of the most recently submitted frame
     DevBuf<char> queryBuf;                     // scratch of crt_query_hits and crt_read_output_rgba8
-    QueryContext rayQuery;                     // crt_trace_rays
+    QueryContext rayQuery;                     // crt_trace_rays, crt_trace_ao, crt_frame_ao
     int raysGridCap = 0;                       // CRT_RAYS_GRID=n: at most n workgroups per query (tests: few waves walking many chunks); 0 = as many as are resident
     DevBuf<char> buildBuf;                                    // crt_build_bvh scratch
     std::vector<CrtBuildCtl> buildReplay; unsigned long long buildReplayKey = 0;   // CRT_DEBUG_BVH_REPLAY (crt_bvh_driver.h): the level records of the last build

@@ -1,6 +1,6 @@
 // crt_upload.h -- session set-up / tear-down, uploads in the reference layouts (Renderer.cpp:122-193, ResourceManager.cpp:145-300) and read-backs of the pools
 // Part of the one translation unit crt_shim.hip (included there, in this order: crt_own.h, crt_state.h, crt_instances.h, crt_upload.h,
-// crt_bvh_driver.h, crt_frame.h, crt_multidev.h); everything here has internal linkage.
+// crt_bvh_driver.h, crt_frame.h, crt_query_host.h, crt_ao_host.h, crt_multidev.h); everything here has internal linkage.
 #pragma once
 namespace {
 // ---- per-device implementation of the C-ABI entry points (current state = g) ----

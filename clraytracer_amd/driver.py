@@ -256,6 +256,20 @@ class Session:
             raise ValueError(f"{name}: a row stride of at least {width} floats (or 0) is required, not {x.stride(0)}")
         return x.shape[0], x.stride(0)
 
+    def _ray_arrays(self, items, **tensors):
+        """(n, strides) of the tensor arguments of one query, name=(tensor, width): each as _ray_array takes it (None: left out, stride None),
+        all of those that are not one shared value with the same number of `items`, all on the session's device."""
+        given = {name: (x, self._ray_array(name, x, width)) for name, (x, width) in tensors.items() if x is not None}
+        counts = [c for _, (c, st) in given.values() if st != 0 or c == 0]
+        n = counts[0] if counts else 1
+        if any(c != n for c in counts):
+            names = list(tensors)
+            raise ValueError(f"{', '.join(names[:-1])} and {names[-1]} disagree about the number of {items}: {counts}")
+        for name, (x, _) in given.items():
+            if x.device.type != "cuda" or x.device.index != self.device:
+                raise ValueError(f"{name}: the tensor is on {x.device}, the session on cuda:{self.device}")
+        return n, tuple(given[name][1][1] if name in given else None for name in tensors)
+
     def trace_rays(self, origins, dirs, tmax=None, mode="closest"):
         """Closest hit ("closest": a RayHits) or occlusion ("occluded": a torch.bool tensor) of n world-space rays given as float32 torch tensors
         on the session's device: origins / dirs of shape (n, 3) -- packed, rows of a wider tensor such as x[:, :3] of (n, 4), or (3,) / (1, 3)
@@ -264,16 +278,7 @@ class Session:
         import torch
         if mode not in ("closest", "occluded"):
             raise ValueError(f"mode must be 'closest' or 'occluded', not {mode!r}")
-        (no, so), (nd, sd) = self._ray_array("origins", origins, 3), self._ray_array("dirs", dirs, 3)
-        counts = [c for c, st in ((no, so), (nd, sd)) if st != 0 or c == 0]
-        if tmax is not None:
-            counts.append(self._ray_array("tmax", tmax, 1)[0])
-        n = counts[0] if counts else 1
-        if any(c != n for c in counts):
-            raise ValueError(f"origins, dirs and tmax disagree about the number of rays: {counts}")
-        for name, x in (("origins", origins), ("dirs", dirs), ("tmax", tmax)):
-            if x is not None and (x.device.type != "cuda" or x.device.index != self.device):
-                raise ValueError(f"{name}: the tensor is on {x.device}, the session on cuda:{self.device}")
+        n, (so, sd, _) = self._ray_arrays("rays", origins=(origins, 3), dirs=(dirs, 3), tmax=(tmax, 1))
         dev = torch.device("cuda", self.device)
         batch = _lib.CrtRayBatch(origins.data_ptr(), dirs.data_ptr(), tmax.data_ptr() if tmax is not None else None, so, sd, n)
         closest = mode == "closest"
@@ -297,14 +302,7 @@ class Session:
         `samples` rays (1, 2, 4, ..., 64) per point reach `radius` far from the point lifted by normal * `bias`. Returns a float32 tensor of
         shape (n,), enqueued on torch.cuda.current_stream() without synchronising."""
         import torch
-        (np_, sp), (nn, sn) = self._ray_array("points", points, 3), self._ray_array("normals", normals, 3)
-        counts = [c for c, st in ((np_, sp), (nn, sn)) if st != 0 or c == 0]
-        n = counts[0] if counts else 1
-        if any(c != n for c in counts):
-            raise ValueError(f"points and normals disagree about the number of points: {counts}")
-        for name, x in (("points", points), ("normals", normals)):
-            if x.device.type != "cuda" or x.device.index != self.device:
-                raise ValueError(f"{name}: the tensor is on {x.device}, the session on cuda:{self.device}")
+        n, (sp, sn) = self._ray_arrays("points", points=(points, 3), normals=(normals, 3))
         dev = torch.device("cuda", self.device)
         pts = _lib.CrtAoPoints(points.data_ptr(), normals.data_ptr(), sp, sn, n)
         params = _lib.CrtAoParams(int(samples), float(radius), float(bias), int(seed) & 0xFFFFFFFF, 0, 0.0, 0.0)

@@ -23,7 +23,7 @@ def test_abi_declares_and_exports_the_ray_queries():
 
 
 def test_every_build_recipe_links_both_translation_units():
-    """The kernel lives in crt_rays.hip and crt_frame.h refers to it: a libcrt_hip.so built from crt_shim.hip alone links but cannot be loaded.
+    """The kernel lives in crt_rays.hip and crt_query_host.h refers to it: a libcrt_hip.so built from crt_shim.hip alone links but cannot be loaded.
     Every committed line that builds the shared library names both units."""
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -35,6 +35,7 @@ class CrtRayBatch(C.Structure):
 
 
 CRT_RAYS_CLOSEST, CRT_RAYS_OCCLUDED = 0, 1      # crt_trace_rays modes
+CRT_RAYS_INCLUSIVE = 0x100                      # OR-ed into the mode: the inclusive box test (include/crt_api.h)
 
 
 class CrtAoParams(C.Structure):
@@ -49,6 +50,7 @@ class CrtAoPoints(C.Structure):
 
 
 CRT_AO_FILTER = 1                               # CrtAoParams.flags
+CRT_AO_INCLUSIVE = 4                            # the inclusive box test of CRT_RAYS_INCLUSIVE for the sample rays
 
 
 class CrtFrameStats(C.Structure):

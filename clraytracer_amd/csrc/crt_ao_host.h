@@ -1,6 +1,6 @@
 // crt_ao_host.h -- ambient occlusion on device points and on G-buffer frames: crt_trace_ao, crt_frame_ao, the AO plane's reads, statistics
 // Part of the one translation unit crt_shim.hip (included there behind crt_query_host.h, whose launch_query and query_stats it uses);
-// everything here has internal linkage. The kernels: crt_ao.h (declared), crt_ao.hip (compiled).
+// everything here has internal linkage. The kernels: crt_ao.h (declared), crt_ao.hip (compiled); under CRT_AO_INCLUSIVE crt_inclusive.h, crt_inclusive.hip.
 #pragma once
 namespace {
 
@@ -24,11 +24,14 @@ static int check_ao_params(const CrtAoParams* p, uint32_t allowed)
 // The launch both forms share, a query of the AO family (launch_query): `A` holds the form's own arguments, the parameters are filled here
 typedef void CrtAoKernel(CrtDevScene, CrtAoArgs, CrtFrame);
 static CrtAoKernel* const kAoKernels[4] = { crt_ao_kernel<CRT_AO_POINTS, false>, crt_ao_kernel<CRT_AO_POINTS, true>, crt_ao_kernel<CRT_AO_FRAME, false>, crt_ao_kernel<CRT_AO_FRAME, true> };
+static CrtAoKernel* const kAoInclusiveKernels[4] = { crt_ao_inclusive_kernel<CRT_AO_POINTS, false>, crt_ao_inclusive_kernel<CRT_AO_POINTS, true>,
+                                                     crt_ao_inclusive_kernel<CRT_AO_FRAME, false>, crt_ao_inclusive_kernel<CRT_AO_FRAME, true> };
 template <class Before, class After>
 static int launch_ao(bool frame, CrtAoArgs A, const CrtFrame& F, const CrtAoParams& p, uint32_t numInstances, uint64_t chunks, hipStream_t stream, Before&& before, After&& after)
 {
     A.samples = p.samples; A.step = CRT_AO_TABLE_SIZE / p.samples; A.seedMul = p.seed * 0x9E3779B9u; A.radius = p.radius; A.bias = p.bias;
-    return launch_query(g.rayQuery.ao, kAoKernels, frame, numInstances, chunks, stream, before, after, A, F);
+    const bool inclusive = (p.flags & CRT_AO_INCLUSIVE) != 0;
+    return launch_query(g.rayQuery.ao, inclusive ? kAoInclusiveKernels : kAoKernels, inclusive, frame, numInstances, chunks, stream, before, after, A, F);
 }
 
 // Enqueue-and-return like crt1_trace_rays: every check comes before the first thing that is queued.
@@ -37,7 +40,7 @@ int crt1_trace_ao(const CrtAoPoints* pts, const CrtAoParams* params, uint32_t nu
     if (!g.initialized) return CRT_E_NOT_INITIALIZED;
     if (!pts || !params) return CRT_E_BAD_ARGUMENT;
     if (pts->n == 0) return CRT_OK;
-    RCCHK(check_ao_params(params, 0u));         // (the filter needs a frame's neighbours)
+    RCCHK(check_ao_params(params, (uint32_t)CRT_AO_INCLUSIVE));      // (the filter needs a frame's neighbours)
     if (!pts->positions || !pts->normals || !out) return CRT_E_BAD_ARGUMENT;
     if (pts->positionStride == 1 || pts->positionStride == 2 || pts->normalStride == 1 || pts->normalStride == 2) return CRT_E_BAD_ARGUMENT;
     if (numInstances > CRT_MAX_INSTANCES || !g.sceneValid) return CRT_E_BAD_ARGUMENT;
@@ -58,7 +61,7 @@ static FrameSlot* gbuffer_slot() { return (g.gbufSlot >= 0 && g.slot[g.gbufSlot]
 int crt1_frame_ao(const CrtAoParams* params, hipStream_t stream)
 {
     if (!g.initialized) return CRT_E_NOT_INITIALIZED;
-    RCCHK(check_ao_params(params, (uint32_t)CRT_AO_FILTER));
+    RCCHK(check_ao_params(params, (uint32_t)(CRT_AO_FILTER | CRT_AO_INCLUSIVE)));
     FrameSlot* fsp = gbuffer_slot();
     if (!fsp || !g.sceneValid) return CRT_E_BAD_ARGUMENT;
     FrameSlot& fs = *fsp;

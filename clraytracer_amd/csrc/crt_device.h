@@ -233,13 +233,19 @@ struct LaneCounters {
 __device__ __forceinline__ void count_culled(LaneCounters& lc, uint32_t n) { lc.traversals += n; lc.pops += n; lc.innerVisits += n; lc.culled += n; }
 
 // kernel_main.cl:108-117
+// INCLUSIVE (the device queries' opt-in rule, crt_api.h: CRT_RAYS_INCLUSIVE; never a frame): the same tnear / tfar, but a box the ray
+// starts in, or of zero thickness, is entered -- at entry = max(tnear, 0). A compile-time constant: the plain form is what it was.
+template <bool INCLUSIVE = false>
 __device__ __forceinline__ float intersect_aabb(v3 o, v3 inv, float4 bmin, float4 bmax, float minSoFar)
 {
     float tminx = (bmin.x - o.x) * inv.x, tminy = (bmin.y - o.y) * inv.y, tminz = (bmin.z - o.z) * inv.z;
     float tmaxx = (bmax.x - o.x) * inv.x, tmaxy = (bmax.y - o.y) * inv.y, tmaxz = (bmax.z - o.z) * inv.z;
     float tnear = fmaxf(fmaxf(fminf(tminx, tmaxx), fminf(tminy, tmaxy)), fminf(tminz, tmaxz));
     float tfar  = fminf(fminf(fmaxf(tminx, tmaxx), fmaxf(tminy, tmaxy)), fmaxf(tminz, tmaxz));
-    return (tnear < tfar && tnear > 0.0f && tnear < minSoFar) ? tnear : 1e30f;
+    if constexpr (INCLUSIVE) {
+        const float entry = fmaxf(tnear, 0.0f);
+        return (tnear <= tfar && tfar >= 0.0f && entry < minSoFar) ? entry : 1e30f;
+    } else return (tnear < tfar && tnear > 0.0f && tnear < minSoFar) ? tnear : 1e30f;
 }
 
 // kernel_main.cl:84-106; hot = {v0, edge1, edge2}
@@ -410,7 +416,8 @@ struct Traversal {
         if (COUNT) { lc.traversals++; lc.pops++; }
     }
     // kernel_main.cl:142-157: fetch the child pair, two slab tests, near child first, far child pushed
-    template <class STK>
+    // (INCLUSIVE: intersect_aabb's; two boxes that both hold the origin return 0 and 0, `dist1 > dist2` is false: left first)
+    template <bool INCLUSIVE = false, class STK>
     __device__ __forceinline__ void inner(const CrtDevScene& S, const STK& stack, Closest& c, LaneCounters& lc)
     {
         // every lane of this step on the same node (the top of a tree under a coherent packet): one scalar load instead of four
@@ -429,8 +436,8 @@ struct Traversal {
             const crt_const_f32x4_ptr q = (STK::kTop && (ref0 & CRT_TOP_BIT)) ? (crt_const_f32x4_ptr)(S.topPairs + (size_t)(ref0 & 0xFFFFu) * 4)
                                                                              : (crt_const_f32x4_ptr)(S.pairs + (size_t)ref0 * 4);
             const crt_f32x4 a = q[0], b = q[1], c4 = q[2], e = q[3];
-            dist1 = intersect_aabb(mo, inv, make_float4(a.x, a.y, a.z, a.w), make_float4(b.x, b.y, b.z, b.w), tr.t);
-            dist2 = intersect_aabb(mo, inv, make_float4(c4.x, c4.y, c4.z, c4.w), make_float4(e.x, e.y, e.z, e.w), tr.t);
+            dist1 = intersect_aabb<INCLUSIVE>(mo, inv, make_float4(a.x, a.y, a.z, a.w), make_float4(b.x, b.y, b.z, b.w), tr.t);
+            dist2 = intersect_aabb<INCLUSIVE>(mo, inv, make_float4(c4.x, c4.y, c4.z, c4.w), make_float4(e.x, e.y, e.z, e.w), tr.t);
             nearRef = __float_as_uint(a.w); farRef = __float_as_uint(c4.w);
 #ifndef CRT_TOP_NO_LDS_PATH
 #define CRT_TOP_NO_LDS_PATH 0                // A/B builds: 1 = the four-wave form without its LDS reads (what the workgroup shape alone costs)
@@ -440,16 +447,16 @@ struct Traversal {
             // lane instead of four vector-memory instructions for the wave (north_star's "hot BVH tiles staged in LDS")
             const auto q = stack.top_record(ref & 0xFFFFu);
             const crt_f32x4 a = q[0], b = q[1], c4 = q[2], e = q[3];
-            dist1 = intersect_aabb(mo, inv, make_float4(a.x, a.y, a.z, a.w), make_float4(b.x, b.y, b.z, b.w), tr.t);
-            dist2 = intersect_aabb(mo, inv, make_float4(c4.x, c4.y, c4.z, c4.w), make_float4(e.x, e.y, e.z, e.w), tr.t);
+            dist1 = intersect_aabb<INCLUSIVE>(mo, inv, make_float4(a.x, a.y, a.z, a.w), make_float4(b.x, b.y, b.z, b.w), tr.t);
+            dist2 = intersect_aabb<INCLUSIVE>(mo, inv, make_float4(c4.x, c4.y, c4.z, c4.w), make_float4(e.x, e.y, e.z, e.w), tr.t);
             nearRef = __float_as_uint(a.w); farRef = __float_as_uint(c4.w);
         } else {
             // one aligned 64-byte record (a step that mixes tree-top and other records takes the top ones from the table's global copy:
             // the four vector loads are issued for the wave either way)
             const float4* p = (STK::kTop && (ref & CRT_TOP_BIT)) ? S.topPairs + (size_t)(ref & 0xFFFFu) * 4 : S.pairs + (size_t)ref * 4;
             const float4 lmin = p[0], lmax = p[1], rmin = p[2], rmax = p[3];
-            dist1 = intersect_aabb(mo, inv, lmin, lmax, tr.t);
-            dist2 = intersect_aabb(mo, inv, rmin, rmax, tr.t);
+            dist1 = intersect_aabb<INCLUSIVE>(mo, inv, lmin, lmax, tr.t);
+            dist2 = intersect_aabb<INCLUSIVE>(mo, inv, rmin, rmax, tr.t);
             nearRef = __float_as_uint(lmin.w); farRef = __float_as_uint(rmin.w);
         }
         if (COUNT) lc.innerVisits++;
@@ -531,6 +538,13 @@ struct Traversal {
 // and |C - c_i| + w_i <= R): a rejected node has dist(ray, c_i) >= dist(ray, C) - (R - w_i) > w_i + sqrt(1.02 R^2 + 2.8e-6 X^2) - R,
 // and with x_i <= X + R the same minimisation gives R (0.00995 - 2 c1) - g4 (kappa O + tau) >= the instance's own margin
 // w_i (0.00995 - c1) - ... for every c1 in the admitted range: a subtree is never rejected for a ray one of its instances admits.
+// Inclusive pass (intersect_aabb<true>: tnear <= tfar, tfar >= 0, entry = max(tnear, 0)). (1) holds with t* = max(tnear, 0) >= 0 in
+// place of tnear: for tnear > 0 it is the same point, now of the closed grown box (lo_k (1 + theta) <= tnear <= hi_k (1 + theta'));
+// for tnear <= 0 <= tfar every slab holds t = 0, so p = mo -- the computed origin -- lies in the closed box exactly, and |d| t* <= x + r
+// as before. (2) both rejection clauses already bound the distance for EVERY t >= 0, t = 0 included: the first bounds the whole line, the
+// second needs oc2 > r2 -- the origin itself outside the grown sphere -- besides b < 0. (3), (4) and (5) use only (1) and (2): unchanged.
+// So the cull, the instance tree and the cull range serve inclusive queries as they are; an origin INSIDE an instance's sphere fails
+// both clauses and the instance is a candidate.
 // ------------------------------------------------------------------------------------------------
 // The ray/sphere rejection of candidate_mask for the instance tree (same arithmetic; any NaN -> not culled).
 __device__ __forceinline__ bool sphere_culls(const float4 bs, v3 o, v3 d, float dd)
@@ -635,12 +649,12 @@ __device__ __forceinline__ bool tlas_candidates(const CrtDevScene& S, v3 o, v3 d
 // for all later instances. `anyHit` is the same boolean the full closest-hit loop would return, because until the
 // first passing triangle both visit the same nodes in the same order; only the work (and the counters) shrink.
 // ITERS (stamped diagnostic launches): the counters record wave-level trips instead of per-ray work.
-template <bool COUNT, bool ITERS, bool ANYHIT, class STK>
+template <bool COUNT, bool ITERS, bool ANYHIT, bool INCLUSIVE = false, class STK>
 __device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stack, Traversal<COUNT>& T, Closest& c, LaneCounters& lc, bool done)
 {
     if (!done && T.at_inner()) {
         if (ITERS) { lc.rays++; if (first_active_lane()) lc.innerVisits++; }
-        T.inner(S, stack, c, lc);
+        T.template inner<INCLUSIVE>(S, stack, c, lc);
     }
     if (!done && T.at_leaf()) {
         if (ITERS) {
@@ -654,7 +668,7 @@ __device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stac
     }
     if (!done && T.at_inner()) {
         if (ITERS) { if (first_active_lane()) lc.hits++; }
-        T.inner(S, stack, c, lc);      // lanes that just popped an inner node go on at once
+        T.template inner<INCLUSIVE>(S, stack, c, lc);      // lanes that just popped an inner node go on at once
     }
 }
 
@@ -663,7 +677,9 @@ __device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stac
 // chunkedOnly (TLAS only, wave-uniform): take the chunked candidate loop although an instance tree exists -- what a wave of the TLAS
 // instantiation does anyway when a lane's candidates do not fit its list; crt_rays_kernel forces it for a wave with an origin beyond
 // the cull's proven range, whose scene then has the all-never bounds table. Both are defaulted and constant for every other caller.
-template <bool COUNT, bool ITERS = false, bool ANYHIT = false, bool TLAS = false, class STK = CrtStack>
+// INCLUSIVE (the device queries only): intersect_aabb's rule for every box test, threaded down through trip_steps and Traversal::inner as a
+// template parameter -- no run-time branch in a step; the instance cull stays on (sphere_culls' derivation, "Inclusive pass").
+template <bool COUNT, bool ITERS = false, bool ANYHIT = false, bool TLAS = false, bool INCLUSIVE = false, class STK = CrtStack>
 __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d, const STK& stack, LaneCounters& lc, float best0 = 99999.0f,
                                                bool chunkedOnly = false)
 {
@@ -697,7 +713,7 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
                         T.template enter<STK::kTop>(S, k, o, d, c.distance, lc);
                     }
                 }
-                trip_steps<COUNT, false, ANYHIT>(S, stack, T, c, lc, done);
+                trip_steps<COUNT, false, ANYHIT, INCLUSIVE>(S, stack, T, c, lc, done);
             }
             return c;
         }
@@ -733,7 +749,7 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
                     T.template enter<STK::kTop>(S, base + k, o, d, c.distance, lc);
                 }
             }
-            trip_steps<COUNT, ITERS, ANYHIT>(S, stack, T, c, lc, done);
+            trip_steps<COUNT, ITERS, ANYHIT, INCLUSIVE>(S, stack, T, c, lc, done);
         }
     }
     return c;

@@ -68,22 +68,24 @@ static int end_query(hipStream_t stream)
 // Ordering: the caller's stream waits (hipStreamWaitEvent) for the query before -- queries share the context -- and for the context's
 // instance tables, which are refreshed on the context's own stream behind that same query (it may still read the old tables). Frames
 // in flight are neither waited for nor touched.
-// kernels: the family's four instantiations, [2 * x + TLAS], launched as kernel(S, A, extra...); A: the form's own arguments, its `q` and
+// kernels: the family's four instantiations under the box rule asked for (inclusive: those of crt_inclusive.hip), [2 * x + TLAS], launched as
+// kernel(S, A, extra...); A: the form's own arguments, its `q` and
 // `chunks` are filled here; before(stream) queues what the kernel must wait for, after(stream) what belongs to the query behind it.
 template <class Kernel, class Args, class Before, class After, class... Extra>
-static int launch_query(QueryFamily& fam, Kernel* const (&kernels)[4], bool x, uint32_t numInstances, uint64_t chunks, hipStream_t stream,
+static int launch_query(QueryFamily& fam, Kernel* const (&kernels)[4], bool inclusive, bool x, uint32_t numInstances, uint64_t chunks, hipStream_t stream,
                         Before&& before, After&& after, Args A, const Extra&... extra)
 {
     CrtDevScene S;
     RCCHK(query_scene(numInstances, S));
     const int which = 2 * (int)x + (int)use_tlas(S);
-    if (fam.residentPerCU[which] == 0) {         // as the runtime computes it for this device, asked once per instantiation
+    int& resident = fam.residentPerCU[4 * (int)inclusive + which];
+    if (resident == 0) {         // as the runtime computes it for this device, asked once per instantiation
         int n = 0;
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernels[which], CRT_BLOCK, 0));
-        fam.residentPerCU[which] = n > 0 ? n : 1;
+        resident = n > 0 ? n : 1;
     }
     uint64_t grid = 0;
-    RCCHK(query_grid(chunks, fam.residentPerCU[which], stream, S, grid));
+    RCCHK(query_grid(chunks, resident, stream, S, grid));
     RCCHK(before(stream));
     uint32_t* ctl = g.rayQuery.ctl + fam.ctl0;
     HIPCHK(hipMemsetAsync(ctl, 0, 2 * sizeof(uint32_t), stream));
@@ -117,6 +119,8 @@ static int query_stats(QueryFamily QueryContext::* family, uint64_t out[3])
 // ---- crt_trace_rays ----
 typedef void CrtRaysKernel(CrtDevScene, CrtRaysArgs);
 static CrtRaysKernel* const kRaysKernels[4] = { crt_rays_kernel<false, false>, crt_rays_kernel<false, true>, crt_rays_kernel<true, false>, crt_rays_kernel<true, true> };
+static CrtRaysKernel* const kRaysInclusiveKernels[4] = { crt_rays_inclusive_kernel<false, false>, crt_rays_inclusive_kernel<false, true>,
+                                                         crt_rays_inclusive_kernel<true, false>, crt_rays_inclusive_kernel<true, true> };
 
 // every check comes before the first thing that is queued (launch_query)
 int crt1_trace_rays(const CrtRayBatch* rays, uint32_t numInstances, int mode, void* out, hipStream_t stream)
@@ -126,13 +130,15 @@ int crt1_trace_rays(const CrtRayBatch* rays, uint32_t numInstances, int mode, vo
     if (rays->n == 0) return CRT_OK;
     if (!rays->origins || !rays->dirs || !out) return CRT_E_BAD_ARGUMENT;
     if (rays->originStride == 1 || rays->originStride == 2 || rays->dirStride == 1 || rays->dirStride == 2) return CRT_E_BAD_ARGUMENT;
-    if (mode != CRT_RAYS_CLOSEST && mode != CRT_RAYS_OCCLUDED) return CRT_E_BAD_ARGUMENT;
+    const bool inclusive = (mode & CRT_RAYS_INCLUSIVE) != 0;
+    const int what = mode & ~CRT_RAYS_INCLUSIVE;
+    if (what != CRT_RAYS_CLOSEST && what != CRT_RAYS_OCCLUDED) return CRT_E_BAD_ARGUMENT;
     if (numInstances > CRT_MAX_INSTANCES || !g.sceneValid) return CRT_E_BAD_ARGUMENT;
     if (rays->n > CRT_RAYS_MAX) return CRT_E_OUT_OF_RANGE;
     CrtRaysArgs A;
     A.origins = rays->origins; A.dirs = rays->dirs; A.tmax = rays->tmax; A.out = out;
     A.originStride = rays->originStride; A.dirStride = rays->dirStride; A.n = (uint32_t)rays->n;
-    return launch_query(g.rayQuery.rays, kRaysKernels, mode == CRT_RAYS_OCCLUDED, numInstances, (rays->n + CRT_BLOCK - 1) / CRT_BLOCK, stream,
+    return launch_query(g.rayQuery.rays, inclusive ? kRaysInclusiveKernels : kRaysKernels, inclusive, what == CRT_RAYS_OCCLUDED, numInstances, (rays->n + CRT_BLOCK - 1) / CRT_BLOCK, stream,
                         no_query_step, no_query_step, A);
 }
 

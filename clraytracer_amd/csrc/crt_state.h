@@ -72,11 +72,11 @@ struct FrameSlot : SlotTables {
 };
 
 // One family of queries on the context below (crt_trace_rays; crt_trace_ao / crt_frame_ao): its pair of control words, what its last launch
-// was, and how many workgroups of each of its kernel's four instantiations a CU holds. Families share everything else of the context.
+// was, and how many workgroups of each of its kernel's instantiations -- four per box rule -- a CU holds. Families share everything else of the context.
 struct QueryFamily {
     uint32_t ctl0;                             // its words in QueryContext::ctl: [ctl0] chunk counter, [ctl0 + 1] chunks traced without the cull (CrtQueryArgs::ctl)
     unsigned long long chunks = 0, grid = 0;   // of the family's last query (crt_debug_rays_stats, crt_debug_ao_stats)
-    int residentPerCU[4] = { 0, 0, 0, 0 };     // hipOccupancyMaxActiveBlocksPerMultiprocessor of the kernel<X, TLAS>, [2 * X + TLAS]; 0 = not asked yet
+    int residentPerCU[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };   // hipOccupancyMaxActiveBlocksPerMultiprocessor of the kernel<X, TLAS>, [4 * inclusive + 2 * X + TLAS]; 0 = not asked yet
 };
 
 // The context of the queries on device buffers (crt_query_host.h): queries never touch a frame slot, so they neither wait for the frames

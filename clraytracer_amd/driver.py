@@ -270,10 +270,12 @@ class Session:
                 raise ValueError(f"{name}: the tensor is on {x.device}, the session on cuda:{self.device}")
         return n, tuple(given[name][1][1] if name in given else None for name in tensors)
 
-    def trace_rays(self, origins, dirs, tmax=None, mode="closest"):
+    def trace_rays(self, origins, dirs, tmax=None, mode="closest", inclusive=False):
         """Closest hit ("closest": a RayHits) or occlusion ("occluded": a torch.bool tensor) of n world-space rays given as float32 torch tensors
         on the session's device: origins / dirs of shape (n, 3) -- packed, rows of a wider tensor such as x[:, :3] of (n, 4), or (3,) / (1, 3)
         for one value shared by every ray -- and optionally tmax of shape (n,), the distance bound in units of the direction's length.
+        inclusive=True: the inclusive box test (CRT_RAYS_INCLUSIVE, include/crt_api.h) -- a ray enters the boxes it starts in, so a ray from a
+        surface sees the mesh it starts on; False: upstream's rule, bit-identical with the frames' traversal.
         Enqueued on torch.cuda.current_stream() without synchronising; the result tensors are ordered on that stream like any torch op."""
         import torch
         if mode not in ("closest", "occluded"):
@@ -284,7 +286,8 @@ class Session:
         closest = mode == "closest"
         out = torch.empty((n, 5), dtype=torch.int32, device=dev) if closest else torch.empty(n, dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if not self.h.crth_trace_rays(C.byref(batch), _lib.CRT_RAYS_CLOSEST if closest else _lib.CRT_RAYS_OCCLUDED, out.data_ptr(), stream):
+        flags = (_lib.CRT_RAYS_CLOSEST if closest else _lib.CRT_RAYS_OCCLUDED) | (_lib.CRT_RAYS_INCLUSIVE if inclusive else 0)
+        if not self.h.crth_trace_rays(C.byref(batch), flags, out.data_ptr(), stream):
             self._raise_and_clear("Renderer::TraceRays")
         return RayHits(out) if closest else out.view(torch.bool)
 
@@ -296,26 +299,29 @@ class Session:
 
     # ---- ambient occlusion (Renderer::TraceAmbientOcclusion / ComputeAmbientOcclusion -> crt_trace_ao / crt_frame_ao) ----
     # radius and bias are lengths in the scene's units and have no default: what counts as "near" is the caller's knowledge of the scene.
-    def trace_ao(self, points, normals, samples=8, *, radius, bias, seed=0):
+    def trace_ao(self, points, normals, samples=8, *, radius, bias, seed=0, inclusive=False):
         """Ambient occlusion (1 = open, 0 = closed; include/crt_api.h) at n points with normals, float32 torch tensors on the session's device
         in the shapes trace_rays takes: (n, 3) packed or as rows of a wider tensor, or (3,) / (1, 3) for one value shared by every point.
         `samples` rays (1, 2, 4, ..., 64) per point reach `radius` far from the point lifted by normal * `bias`. Returns a float32 tensor of
-        shape (n,), enqueued on torch.cuda.current_stream() without synchronising."""
+        shape (n,), enqueued on torch.cuda.current_stream() without synchronising. inclusive=True: the sample rays under the inclusive box test
+        (CRT_AO_INCLUSIVE), as trace_rays(..., inclusive=True) answers them."""
         import torch
         n, (sp, sn) = self._ray_arrays("points", points=(points, 3), normals=(normals, 3))
         dev = torch.device("cuda", self.device)
         pts = _lib.CrtAoPoints(points.data_ptr(), normals.data_ptr(), sp, sn, n)
-        params = _lib.CrtAoParams(int(samples), float(radius), float(bias), int(seed) & 0xFFFFFFFF, 0, 0.0, 0.0)
+        params = _lib.CrtAoParams(int(samples), float(radius), float(bias), int(seed) & 0xFFFFFFFF, _lib.CRT_AO_INCLUSIVE if inclusive else 0, 0.0, 0.0)
         out = torch.empty(n, dtype=torch.float32, device=dev)
         if not self.h.crth_trace_ao(C.byref(pts), C.byref(params), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream):
             self._raise_and_clear("Renderer::TraceAmbientOcclusion")
         return out
 
-    def ambient_occlusion(self, samples=8, *, radius, bias, seed=0, filter=False, depth_tol=0.05, normal_cos=0.9, stream=None):
+    def ambient_occlusion(self, samples=8, *, radius, bias, seed=0, filter=False, depth_tol=0.05, normal_cos=0.9, stream=None, inclusive=False):
         """Ambient occlusion of the pixels of the last frame rendered with gbuffer=True, as a (height, width) float32 array (1 = open; a pixel
         of sky is 1). filter=True: the 5 x 5 mean over neighbours whose distance is within depth_tol (relative) and whose normal's cosine is
-        at least normal_cos. `stream`: a hipStream_t as an integer; None: HIP's null stream."""
-        params = _lib.CrtAoParams(int(samples), float(radius), float(bias), int(seed) & 0xFFFFFFFF, _lib.CRT_AO_FILTER if filter else 0,
+        at least normal_cos. `stream`: a hipStream_t as an integer; None: HIP's null stream. inclusive=True: the sample rays under the
+        inclusive box test (CRT_AO_INCLUSIVE)."""
+        params = _lib.CrtAoParams(int(samples), float(radius), float(bias), int(seed) & 0xFFFFFFFF,
+                                  (_lib.CRT_AO_FILTER if filter else 0) | (_lib.CRT_AO_INCLUSIVE if inclusive else 0),
                                   float(depth_tol), float(normal_cos))
         if not self.h.crth_compute_ao(C.byref(params), stream):
             self._raise_and_clear("Renderer::ComputeAmbientOcclusion")

@@ -46,12 +46,13 @@ namespace Renderer
     const void* MapGBuffer(int plane);    // host copy of plane CRT_GBUFFER_GEOMETRY / IDS / ALBEDO of the last G-buffer frame (width*height elements), valid until next Render; null without one
     bool PickPixel(int x, int y, CrtGBufferPixel& out); // what that frame's primary ray hit at pixel (x, y): 36 bytes from the device, no ray cast (replaces CPU_RayCast(ScreenPointToRaySSE(mouse)), Engine.cpp:112-126)
     // extension: closest hit (CRT_RAYS_CLOSEST: CrtRayHit per ray) or occlusion (CRT_RAYS_OCCLUDED: one byte per ray) for a batch of rays on the device
-    // against the registered instances (as last uploaded), enqueued on `stream` (a hipStream_t; null: HIP's null stream) without waiting; false: LastError()
+    // against the registered instances (as last uploaded), enqueued on `stream` (a hipStream_t; null: HIP's null stream) without waiting; false: LastError().
+    // mode | CRT_RAYS_INCLUSIVE: the inclusive box test, for rays that start on a surface (crt_api.h)
     bool TraceRays(const CrtRayBatch& rays, int mode, void* out, void* stream = nullptr);
     // extension: ambient occlusion (crt_api.h: crt_trace_ao, crt_frame_ao). TraceAmbientOcclusion: n floats into `out` for points + normals on the device,
     // against the registered instances, enqueued on `stream` without waiting. ComputeAmbientOcclusion: the same for the pixels of the last frame rendered
     // with SetGBuffer(true), into that frame's AO plane; MapAmbientOcclusion: a host copy of it (width*height floats, valid until the next call; null
-    // without one). false / null: LastError()
+    // without one). false / null: LastError(). CRT_AO_INCLUSIVE in params.flags: the sample rays under the inclusive box test, both forms
     bool TraceAmbientOcclusion(const CrtAoPoints& points, const CrtAoParams& params, float* out, void* stream = nullptr);
     bool ComputeAmbientOcclusion(const CrtAoParams& params, void* stream = nullptr);
     const float* MapAmbientOcclusion();

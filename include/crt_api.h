@@ -217,8 +217,20 @@ int crt_query_hits(const float* origins, const float* dirs, int n, uint32_t numI
  * Work counters, crt_get_counters and noCullFrames are not touched. n == 0: CRT_OK, no pointer is looked at. Errors, all before
  * anything is enqueued: CRT_E_NOT_INITIALIZED; CRT_E_BAD_ARGUMENT (rays, origins, dirs or out NULL; a stride of 1 or 2; an unknown
  * mode; numInstances > 401; an invalid scene); CRT_E_OUT_OF_RANGE (n > 2^30); CRT_E_UNSUPPORTED (a session of several devices: the
- * pointers belong to one GPU). CRT_RAYS_GRID=n in the environment (read by crt_init) caps the launch at n workgroups. */
-enum { CRT_RAYS_CLOSEST = 0, CRT_RAYS_OCCLUDED = 1 };
+ * pointers belong to one GPU). CRT_RAYS_GRID=n in the environment (read by crt_init) caps the launch at n workgroups.
+ *
+ * CRT_RAYS_INCLUSIVE (OR-ed into `mode`; the valid modes are 0, 1, 0x100, 0x101) -- the inclusive box test, for rays that start ON a
+ * surface: shadow and visibility rays, ambient-occlusion samples, bounce rays. Upstream's IntersectAABB never enters a box the ray starts
+ * in (tnear > 0, hazard H1) nor one of zero thickness (tnear < tfar), so such a ray sees a fraction of the scene, the mesh it starts on
+ * least of all. With the flag the box test, in float32 without contraction, is: tnear and tfar as upstream computes them;
+ * entry = fmaxf(tnear, 0.0f); the box passes iff tnear <= tfar && tfar >= 0.0f && entry < minSoFar; the function returns entry on a
+ * pass and 1e30f otherwise. Nothing else changes: near child first by the returned distance (swap iff dist1 > dist2, so two boxes that
+ * both hold the origin keep left-first order), the 32-slot stack with its modulo wrap, the 250-pop cap per instance (kept: it bounds every
+ * traversal, so no input can make a kernel run on), IntersectTriangle with its arithmetic blend, the instance loop in ascending order,
+ * the bound B (a NaN bound included), the miss record, and CRT_RAYS_OCCLUDED = the anyHit of the bounded closest-hit query under the
+ * same rule, exactly. The instance cull stays on (it is proven for this rule too). Without the flag every call is what it was; frames,
+ * crt_query_hits and the counters never use the rule. crt_debug_rays_stats counts inclusive launches as any other. */
+enum { CRT_RAYS_CLOSEST = 0, CRT_RAYS_OCCLUDED = 1, CRT_RAYS_INCLUSIVE = 0x100 };
 int crt_trace_rays(const CrtRayBatch* rays, uint32_t numInstances, int mode, void* out, void* stream);
 
 /* Ambient occlusion (no reference counterpart: upstream's ambient term is the flat max(-ndl, 0.1) * atmosphere of kernel_main.cl:262), for
@@ -261,8 +273,11 @@ int crt_trace_rays(const CrtRayBatch* rays, uint32_t numInstances, int mode, voi
  * slot's first crt_frame_ao (the one host wait); under crt_set_row_bands only this rank's rows are written. CRT_E_BAD_ARGUMENT when no
  * G-buffer frame has been submitted since crt_init or the last crt_resize that changed the frame (when crt_read_gbuffer refuses).
  * crt_read_ao (floats = width * height, after waiting for the frames and the query in flight) and crt_ao_device_ptr refer to the most recent
- * crt_frame_ao and refuse (CRT_E_BAD_ARGUMENT / NULL) when there is none since crt_init or such a crt_resize. */
-enum { CRT_AO_FILTER = 1 };
+ * crt_frame_ao and refuse (CRT_E_BAD_ARGUMENT / NULL) when there is none since crt_init or such a crt_resize.
+ * CRT_AO_INCLUSIVE (both forms; combines with CRT_AO_FILTER on the frame form): occ = what crt_trace_rays(CRT_RAYS_OCCLUDED |
+ * CRT_RAYS_INCLUSIVE) answers for the sample ray -- the inclusive box test defined there, under which a point sees the mesh it lies on.
+ * Everything else in the definition above is unchanged. */
+enum { CRT_AO_FILTER = 1, CRT_AO_INCLUSIVE = 4 };
 int crt_ao_directions(float out[768]);
 int crt_trace_ao(const CrtAoPoints* points, const CrtAoParams* params, uint32_t numInstances, float* out, void* stream);
 int crt_frame_ao(const CrtAoParams* params, void* stream);

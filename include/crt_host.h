@@ -68,7 +68,7 @@ void crth_set_pipelined(int enabled);                        /* Renderer::SetPip
 void crth_set_row_bands(int bandRows, int rank, int nRanks);
 unsigned crth_render(float sunAngle);                        /* Renderer::Render: frame index, 0 on failure */
 const float* crth_map_output(void);                          /* Renderer::MapOutput */
-/* Renderer::TraceRays: crt_trace_rays (crt_api.h) against the registered instances; mode CRT_RAYS_CLOSEST / CRT_RAYS_OCCLUDED, `out` and the
+/* Renderer::TraceRays: crt_trace_rays (crt_api.h) against the registered instances; mode CRT_RAYS_CLOSEST / CRT_RAYS_OCCLUDED (| CRT_RAYS_INCLUSIVE), `out` and the
  * batch's arrays on the device, `stream` a hipStream_t or NULL. 1, or 0 on failure (crth_last_error). */
 int crth_trace_rays(const CrtRayBatch* rays, int mode, void* out, void* stream);
 /* Renderer::TraceAmbientOcclusion / ComputeAmbientOcclusion / MapAmbientOcclusion: crt_trace_ao, crt_frame_ao and crt_read_ao (crt_api.h).

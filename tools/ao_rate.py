@@ -13,6 +13,10 @@ second (the rays of the pixels that trace: a pixel of sky has none), and the run
 fused plane is checked against the composition of the materialised answers before anything is timed. Needs a GPU: there is no fallback.
 
     python tools/ao_rate.py [--rounds R] [--repeats K] [--out profiles/ao_rate.txt]
+
+--inclusive: the fused kernel under CRT_AO_INCLUSIVE against the plain fused kernel of the same build on the same frame,
+alternating leg by leg; the inclusive plane is checked against the composition of the inclusive occlusion query first. Writes its section of
+profiles/inclusive_rate.txt (tools/ray_query_rate.py --inclusive writes the other).
 """
 import argparse
 import ctypes as C
@@ -26,6 +30,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 from clraytracer_amd import _lib, driver, scenes
 import ao_ref
 
@@ -38,7 +43,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=3, help="calls per timed leg")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ao_rate.txt"))
+    ap.add_argument("--inclusive", action="store_true", help="CRT_AO_INCLUSIVE against the plain fused kernel (see above)")
     opt = ap.parse_args()
+    if opt.inclusive and opt.out == ap.get_default("out"):
+        opt.out = os.path.join(ROOT, "profiles", "inclusive_rate.txt")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("ao_rate: no GPU (this tool measures; it does not fall back)")
@@ -84,6 +92,13 @@ def main():
 
             legs = {"fused": lambda: _lib.check(s.hip.crt_frame_ao(C.byref(cp), stream), "crt_frame_ao"),
                     "materialised": lambda: s.trace_rays(to, td, tmax=tt, mode="occluded")}
+            if opt.inclusive:
+                cpi = _lib.CrtAoParams(SAMPLES, radius, par["bias"], 0, _lib.CRT_AO_INCLUSIVE, 0.0, 0.0)
+                fused_inc = s.ambient_occlusion(SAMPLES, radius=radius, bias=par["bias"], inclusive=True).copy()
+                occ_inc = s.trace_rays(to, td, tmax=tt, mode="occluded", inclusive=True).cpu().numpy().reshape(-1, SAMPLES)
+                if not np.array_equal(fused_inc.reshape(-1).view(np.uint32), ao_ref.compose(w, occ_inc).view(np.uint32)):
+                    raise SystemExit(f"ao_rate: {view_name}: the inclusive fused plane differs from the composition of the inclusive occlusion answers")
+                legs = {"fused": legs["fused"], "fused-inclusive": lambda: _lib.check(s.hip.crt_frame_ao(C.byref(cpi), stream), "crt_frame_ao")}
             for f in legs.values():                           # warm-up: every leg once
                 leg(f)
             times = {name: [] for name in legs}
@@ -93,6 +108,8 @@ def main():
             rec = {"radius": round(radius, 4), "extent": round(extent, 3), "tracing_pixels": int(traces.sum()), "sample_rays": rays,
                    "materialised_rays": len(to), "occluded_share": round(float(occ[traces].mean()), 4), "mean_ao": round(float(fused.mean()), 4),
                    "ao_stats": s.ao_stats()}
+            if opt.inclusive:
+                rec.update({"occluded_share_inclusive": round(float(occ_inc[traces].mean()), 4), "mean_ao_inclusive": round(float(fused_inc.mean()), 4)})
             for name, ts in times.items():
                 med = statistics.median(ts)
                 rec[name] = {"ms_median": round(med * 1e3, 4), "ms_min": round(min(ts) * 1e3, 4), "ms_max": round(max(ts) * 1e3, 4),
@@ -104,6 +121,20 @@ def main():
         print(text)
         lines.append(text)
 
+    if opt.inclusive:
+        from ray_query_rate import write_section
+        emit(f"== ao_rate --inclusive: crt_frame_ao under CRT_AO_INCLUSIVE against the plain fused kernel, same build, same {W}x{H} G-buffer frame of multi-1M, {SAMPLES} sample rays per pixel; "
+             f"events on the stream, median of {opt.rounds} alternating rounds of {opt.repeats} calls; {result['device']}")
+        for view_name, rec in result["views"].items():
+            emit(f"{view_name}: radius {rec['radius']}, {rec['sample_rays']} sample rays; occluded share {rec['occluded_share']} (mean AO {rec['mean_ao']}) under upstream's rule, "
+                 f"{rec['occluded_share_inclusive']} (mean AO {rec['mean_ao_inclusive']}) under the inclusive rule")
+            for name in ("fused", "fused-inclusive"):
+                r = rec[name]
+                emit(f"  {name:16s} {r['ms_median']:9.3f} ms per frame ({r['ms_min']:.3f} .. {r['ms_max']:.3f}) = {r['grays_per_s']:7.3f} G sample rays/s")
+            emit(f"  inclusive against plain: {rec['fused-inclusive']['ms_median'] / rec['fused']['ms_median']:.3f} x the time")
+        emit(json.dumps(result))
+        write_section(opt.out, "== ao_rate", lines)
+        return
     emit(f"ambient occlusion of a {W}x{H} G-buffer frame of multi-1M, {SAMPLES} sample rays per pixel, radius = {RADIUS_OF_EXTENT} x the extent of the frame's hit points, "
          f"bias = {BIAS_OF_RADIUS} x the radius; events on the stream, median of {opt.rounds} alternating rounds of {opt.repeats} calls; {result['device']}")
     for view_name, rec in result["views"].items():

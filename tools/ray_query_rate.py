@@ -13,6 +13,12 @@ device route's own time). Reports the median leg in Mrays/s, the run-to-run spre
 order against the shuffled order and the device route against crt_query_hits. Needs a GPU: there is no fallback. Run on the GPU box.
 
     python tools/ray_query_rate.py [--rounds R] [--repeats K] [--out profiles/ray_query_rate.txt]
+
+--inclusive: the inclusive box test against the plain mode of the same build, on the same rays, alternating leg by leg --
+closest, closest-inclusive, occluded, occluded-inclusive -- for two ray sets: the camera rays in pixel order (they start outside every box:
+the rule should cost about nothing) and "surface" rays, the workload the mode exists for: the frame's first hits (G-buffer) as origins,
+stepped 1e-3 of their t back towards the camera, with the camera ray reflected about the stored normal as direction. Writes its section of
+profiles/inclusive_rate.txt (tools/ao_rate.py --inclusive writes the other).
 """
 import argparse
 import json
@@ -30,12 +36,28 @@ WRITE_RAYS = 2
 W, H = 1920, 1080
 
 
+def write_section(path, head, lines):
+    """replace the section of `path` that starts with a line beginning with `head` (sections start with "== ") by `lines`, or append it"""
+    kept, skip = [], False
+    if os.path.exists(path):
+        for line in open(path).read().splitlines():
+            if line.startswith("== "):
+                skip = line.startswith(head)
+            if not skip:
+                kept.append(line)
+    with open(path, "w") as f:
+        f.write("\n".join(kept + lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=5, help="queries per timed leg (device legs)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ray_query_rate.txt"))
+    ap.add_argument("--inclusive", action="store_true", help="the inclusive box test against the plain mode (see above)")
     opt = ap.parse_args()
+    if opt.inclusive and opt.out == ap.get_default("out"):
+        opt.out = os.path.join(os.path.dirname(opt.out), "inclusive_rate.txt")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("ray_query_rate: no GPU (this tool measures; it does not fall back)")
@@ -53,8 +75,18 @@ def main():
             origins = np.tile(pos.astype(np.float32), (n, 1))
             perm = np.random.RandomState(11).permutation(n)
             orders = {"pixel": (origins, dirs), "shuffled": (origins[perm].copy(), dirs[perm].copy())}
+            if opt.inclusive:
+                s.render(gbuffer=True)
+                g = s.read_gbuffer()["geometry"].reshape(-1)
+                hit = ~(g["t"] > np.float32(99998.0))
+                nrm, t = np.ascontiguousarray(g["normal"], np.float32)[hit], g["t"].astype(np.float32)[hit]
+                dh = dirs[hit]
+                refl = dh - 2.0 * (dh * nrm).sum(axis=1, keepdims=True) * nrm
+                orders = {"camera": (origins, dirs), "surface": (np.ascontiguousarray(origins[hit] + dh * (t * np.float32(1.0 - 1e-3))[:, None], np.float32),
+                                                                 np.ascontiguousarray(refl, np.float32))}
             view = {}
             for order, (o, d) in orders.items():
+                n = len(d)
                 to, td = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
                 closest = s.trace_rays(to, td)
                 half = (closest.t * 0.5).contiguous()
@@ -62,12 +94,12 @@ def main():
                 occluded_at_half = int(s.trace_rays(to, td, tmax=half, mode="occluded").sum().item())
                 torch.cuda.synchronize()
 
-                def device_leg(mode, tmax=None):
+                def device_leg(mode, tmax=None, inclusive=False):
                     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     t0 = time.perf_counter()
                     ev0.record()
                     for _ in range(opt.repeats):
-                        s.trace_rays(to, td, tmax=tmax, mode=mode)
+                        s.trace_rays(to, td, tmax=tmax, mode=mode, inclusive=inclusive)
                     ev1.record()
                     torch.cuda.current_stream().synchronize()
                     host = (time.perf_counter() - t0) / opt.repeats
@@ -80,6 +112,10 @@ def main():
 
                 legs = {"closest": lambda: device_leg("closest"), "occluded": lambda: device_leg("occluded"),
                         "occluded-half": lambda: device_leg("occluded", half), "query_hits": host_leg}
+                if opt.inclusive:
+                    legs = {"closest": lambda: device_leg("closest"), "closest-inclusive": lambda: device_leg("closest", inclusive=True),
+                            "occluded": lambda: device_leg("occluded"), "occluded-inclusive": lambda: device_leg("occluded", inclusive=True)}
+                    hits_inclusive = int((s.trace_rays(to, td, inclusive=True).instance >= 0).sum().item())
                 for f in legs.values():                       # warm-up: every leg once
                     f()
                 times = {k: [] for k in legs}
@@ -87,7 +123,9 @@ def main():
                     for k, f in legs.items():
                         times[k].append(f())
                 chunks, no_cull, groups = s.rays_stats()
-                rec = {"hits": hits, "occluded_at_half_t": occluded_at_half, "chunks": chunks, "chunks_without_cull": no_cull, "workgroups": groups}
+                rec = {"rays": n, "hits": hits, "occluded_at_half_t": occluded_at_half, "chunks": chunks, "chunks_without_cull": no_cull, "workgroups": groups}
+                if opt.inclusive:
+                    rec["hits_inclusive"] = hits_inclusive
                 for k, ts in times.items():
                     host = [t[0] for t in ts]
                     rec[k] = {"host_ms_median": round(statistics.median(host) * 1e3, 4), "host_ms_min": round(min(host) * 1e3, 4), "host_ms_max": round(max(host) * 1e3, 4),
@@ -104,6 +142,20 @@ def main():
         print(text)
         lines.append(text)
 
+    if opt.inclusive:
+        emit(f"== ray_query_rate --inclusive: the inclusive box test against the plain mode, same build, same rays; multi-1M at {W}x{H}, median of {opt.rounds} alternating rounds, "
+             f"{opt.repeats} queries per leg, device events; {result['device']}")
+        for view_name, view in result["views"].items():
+            for order, rec in view.items():
+                emit(f"{view_name}, {order} rays: {rec['rays']} rays, {rec['hits']} hit under upstream's rule, {rec['hits_inclusive']} under the inclusive rule; {rec['chunks_without_cull']} chunks without the cull")
+                for k in ("closest", "closest-inclusive", "occluded", "occluded-inclusive"):
+                    r = rec[k]
+                    emit(f"  {k:19s} {r['event_ms_median']:8.3f} ms ({r['event_ms_min']:.3f} .. {r['event_ms_max']:.3f}) = {r['mrays_per_s_device']:8.1f} Mrays/s")
+                emit(f"  inclusive against plain: closest {rec['closest-inclusive']['event_ms_median'] / rec['closest']['event_ms_median']:.3f} x the time, "
+                     f"occluded {rec['occluded-inclusive']['event_ms_median'] / rec['occluded']['event_ms_median']:.3f} x")
+        emit(json.dumps(result))
+        write_section(opt.out, "== ray_query_rate", lines)
+        return
     emit(f"ray queries on device buffers, {W}x{H} primary rays of multi-1M ({W * H} rays per query), median of {opt.rounds} alternating rounds, {opt.repeats} queries per device leg; {result['device']}")
     for view_name, view in result["views"].items():
         for order, rec in view.items():

@@ -20,6 +20,7 @@ import pytest
 
 from clraytracer_amd import driver, scenes
 import oracle_lib
+from texel_ref import sky_index, to_int             # the skybox index and the pinned (int) conversion live in tests/texel_ref.py
 
 F = np.float32
 
@@ -49,13 +50,6 @@ def mat_mul_xyz(m, v, w):
 def mat3_mul(m, v):
     """MathAndSTL.cl:104-106 on ConvertToMatrix3(m) (the xyz of rows x, y, z)"""
     return (m[:, 0, :3] * v[:, 0:1] + m[:, 1, :3] * v[:, 1:2]) + m[:, 2, :3] * v[:, 2:3]
-
-
-def to_int(x):                                      # pinned: truncation, NaN -> 0, saturating
-    x = np.asarray(x, np.float32)
-    y = np.where(np.isnan(x), F(0), x)
-    y = np.clip(y.astype(np.float64), -2147483648.0, 2147483647.0)
-    return np.trunc(y).astype(np.int64)
 
 
 def half(h):
@@ -95,11 +89,7 @@ def trace_numpy(a, orc, rays, cam_pos, sun_angle):
         if len(mi):
             dm = d[mi]
             tw, th = int(tex[2]["width"]), int(tex[2]["height"])
-            atan2pi = (np.arctan2(dm[:, 0].astype(np.float64), (-dm[:, 2]).astype(np.float64)) / np.pi).astype(np.float32)
-            acospi = (np.arccos(dm[:, 1].astype(np.float64)) / np.pi).astype(np.float32)
-            theta = to_int((atan2pi * F(0.5)) * F(tw))
-            phi = to_int(acospi * F(th))
-            r, g, b = fetch_texel(texels, phi * tw + (theta + 2))                                                       # mad24(phi, width, theta + 2)
+            r, g, b = fetch_texel(texels, sky_index(dm, tw, th)[2])                                                     # mad24(phi, width, theta + 2), tests/texel_ref.py
             skyc = np.stack([r, g, b], 1).astype(np.float32) * u255
             result[mi] = result[mi] + skyc * energy[mi]
             sky_mask[mi] = True

@@ -581,6 +581,77 @@ __device__ __forceinline__ unsigned long long candidate_mask(const CrtDevScene& 
     return cand;
 }
 
+// candidate_mask for a wave whose rays share their origin (the camera bounce of the uncounted Trace kernels: whole tiles, the quadrant
+// waves of split tiles, the SSAA virtual frame). Of candidate_mask's 27 VALU instructions per instance 16 depend on the origin and the
+// instance alone -- oc, oc2, r2, `w >= 0`, `oc2 > r2` -- and every lane of every wave computed them again. Here the wave's r-th active
+// lane computes them for instances base + r, base + r + (active lanes), ... with candidate_mask's expressions in candidate_mask's order
+// (-ffp-contract=off: the same roundings) and stores them in the wave's stack rows, which are dead until the first push (the ownership
+// rule of tlas_candidates; rows 0..5 of the kLds >= 15 stack rows, no parked slot):
+//     words [4k, 4k + 4)              {oc.x, oc.y, oc.z, oc2}
+//     words [256 + 2k, 256 + 2k + 2)  {r2', thr}:  r2' = r2, or +inf when !(w >= 0);  thr = 0 when w >= 0 && oc2 > r2, else -inf
+// and every lane runs the per-instance loop on broadcast reads (one ds_read_b128 + one ds_read_b64, a wave-uniform address):
+//     b = oc.d,  cull = (oc2 dd - b b > r2' dd) | (b < thr).
+// The two uniform predicates are folded into values without changing a bit of the mask: `x > r2' dd` with r2' = +inf is `x > inf` or
+// `x > NaN` (dd = 0 or NaN) -- false, like `w >= 0` false (w < 0: never cull, or a NaN w); `b < -inf` is false for every b, NaN
+// included, like `oc2 > r2` false; `b < 0.0f` is the original clause. A NaN or overflowing oc2 / r2 takes the original operations.
+// A lane's own stack entries lie in these rows, so every lane of the wave has finished reading before any lane pushes: the loop below
+// is wave-uniform and the trip loop starts behind it; the next 64-chunk restages after the trip loop has ended for the whole wave
+// (every lane's stack empty).
+typedef uint32_t crt_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t crt_u32x2 __attribute__((ext_vector_type(2)));
+typedef crt_u32x4 __attribute__((address_space(3)))* crt_lds_u32x4_ptr;
+typedef crt_u32x2 __attribute__((address_space(3)))* crt_lds_u32x2_ptr;
+#define CRT_STAGE_ROWS 6
+template <class STK>
+__device__ __forceinline__ unsigned long long staged_candidate_mask(const CrtDevScene& S, v3 o, v3 d, uint32_t base, uint32_t cnt, const STK& stack)
+{
+    static_assert(STK::kLds >= CRT_STAGE_ROWS && CRT_BLOCK == 64, "the staged cull terms take six stack rows of a one-wave workgroup");
+    // the wave's row 0. One-wave workgroups: lds = s_stack + threadIdx.x, so this folds to the array's address (the kernel's only LDS
+    // object: offset 0, which is what the 16- and 8-byte records below rely on) -- a constant, where `lds - lane` was a VGPR hoisted out
+    // of the bounce loop and kept alive through both traversals (16 B of scratch)
+    const crt_lds_u32_ptr wave = stack.lds - threadIdx.x;
+    const crt_lds_u32x4_ptr rowA = (crt_lds_u32x4_ptr)wave;
+    const crt_lds_u32x2_ptr rowB = (crt_lds_u32x2_ptr)(wave + 4 * 64);
+    const unsigned long long act = __ballot(1);
+    const uint32_t nAct = (uint32_t)__popcll(act);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
+    for (uint32_t k0 = 0; k0 < cnt; k0 += nAct) {
+        const uint32_t k = k0 + rank;
+        if (k < cnt) {
+            const float4 bs = S.instBounds[base + k];
+            const v3 oc = mk3(bs.x - o.x, bs.y - o.y, bs.z - o.z);
+            const float oc2 = dot3(oc, oc);
+            const float r2 = bs.w * bs.w * 1.0201f + 4e-6f * oc2;   // candidate_mask's r2
+            const bool cullable = bs.w >= 0.0f;
+            crt_u32x4 a; crt_u32x2 t;
+            a.x = __float_as_uint(oc.x); a.y = __float_as_uint(oc.y); a.z = __float_as_uint(oc.z); a.w = __float_as_uint(oc2);
+            t.x = cullable ? __float_as_uint(r2) : 0x7F800000u;
+            t.y = (cullable && oc2 > r2) ? 0u : 0xFF800000u;
+            rowA[k] = a; rowB[k] = t;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const float dd = dot3(d, d);
+    const auto culls = [&](uint32_t k) {
+        const crt_u32x4 a = rowA[k]; const crt_u32x2 t = rowB[k];
+        const v3 oc = mk3(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z));
+        const float oc2 = __uint_as_float(a.w), r2 = __uint_as_float(t.x), thr = __uint_as_float(t.y);
+        const float b = dot3(oc, d);
+        return (oc2 * dd - b * b > r2 * dd) | (b < thr);
+    };
+    // the mask in two 32-bit halves: one select and one OR per instance instead of two of each
+    uint32_t lo = 0, hi = 0;
+    const uint32_t nLo = cnt < 32u ? cnt : 32u;
+    for (uint32_t k = 0; k < nLo; ++k) lo |= culls(k) ? 0u : 1u << k;
+    for (uint32_t k = 32; k < cnt; ++k) hi |= culls(k) ? 0u : 1u << (k - 32u);
+    const unsigned long long cand = ((unsigned long long)hi << 32) | lo;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    return cand;
+}
+
 // Candidate instances of one ray from the instance tree: up to CRT_TLAS_LIST indices (16 bits each, unordered, 0xFFFF =
 // empty) in four words; returns false when the lane would need more. The traversal stack is idle at this point
 // and serves as the tree stack. Scenes with hundreds of instances (upstream allows 401 and loops over all of them for
@@ -679,10 +750,14 @@ __device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stac
 // the cull's proven range, whose scene then has the all-never bounds table. Both are defaulted and constant for every other caller.
 // INCLUSIVE (the device queries only): intersect_aabb's rule for every box test, threaded down through trip_steps and Traversal::inner as a
 // template parameter -- no run-time branch in a step; the instance cull stays on (sphere_culls' derivation, "Inclusive pass").
-template <bool COUNT, bool ITERS = false, bool ANYHIT = false, bool TLAS = false, bool INCLUSIVE = false, class STK = CrtStack>
+// STAGE (the uncounted Trace kernels without an instance tree only) + sharedOrigin (wave-uniform, run time: the camera bounce): the
+// chunk's mask comes from staged_candidate_mask -- the same mask, bit for bit. A run-time value, not a second instantiation: the trip
+// loop below exists once per kernel.
+template <bool COUNT, bool ITERS = false, bool ANYHIT = false, bool TLAS = false, bool INCLUSIVE = false, bool STAGE = false, class STK = CrtStack>
 __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d, const STK& stack, LaneCounters& lc, float best0 = 99999.0f,
-                                               bool chunkedOnly = false)
+                                               bool chunkedOnly = false, bool sharedOrigin = false)
 {
+    static_assert(!STAGE || (!COUNT && !ITERS && !ANYHIT && !TLAS && !STK::kTop), "staged cull terms: uncounted closest-hit traversals of one-wave workgroups");
     Closest c = no_hit(best0);
     Traversal<COUNT> T; T.reset();
 
@@ -721,7 +796,9 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
 
     for (uint32_t base = 0; base < S.numInstances; base += 64) {
         const uint32_t cnt = (S.numInstances - base) < 64u ? (S.numInstances - base) : 64u;
-        unsigned long long cand = candidate_mask<COUNT, ANYHIT>(S, o, d, base, cnt, lc);
+        unsigned long long cand;
+        if constexpr (STAGE) cand = sharedOrigin ? staged_candidate_mask(S, o, d, base, cnt, stack) : candidate_mask<false>(S, o, d, base, cnt, lc);
+        else cand = candidate_mask<COUNT, ANYHIT>(S, o, d, base, cnt, lc);
         // ANYHIT + COUNT: a culled instance is only "visited" (one pop, one inner visit upstream) if the ray gets that
         // far, so culled instances are counted when a later candidate is entered or the chunk ends without a hit
         unsigned long long culledLeft = (COUNT && ANYHIT) ? (~cand & (cnt == 64u ? ~0ull : ((1ull << cnt) - 1ull))) : 0ull;

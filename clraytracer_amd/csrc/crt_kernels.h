@@ -380,6 +380,7 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
 {
     constexpr bool SSAA = CASE == CRT_TRACE_SSAA, GBUFFER = CASE == CRT_TRACE_GBUFFER;
     constexpr int kParkNdl = TLAS ? CRT_TLAS_PARK : 0;
+    constexpr bool kStage = !COUNT && !STAMP && !TLAS && !STK::kTop;      // staged_candidate_mask (crt_device.h)
     LaneCounters lc; zero_counters(lc);
     WaveStampStart t0 = { 0, 0 };
     if (STAMP) t0 = wave_stamp_start();
@@ -395,7 +396,8 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
             // would otherwise spill to scratch); the shadow ray's n.l uses the same slot later, when the energy is dead
             // (GBUFFER: the same -- the plane stores' addresses take the register the plain kernel keeps the energy in)
             if (SHADOW || GBUFFER) stack.park(kParkNdl, __float_as_uint(ps.energy));
-            Closest c = closest_hit<COUNT, STAMP, false, TLAS>(S, ps.o, ps.d, stack, lc);
+            // kStage: at the camera bounce every ray of the wave starts at F.camPos -- the cull's origin-only terms are computed once per wave
+            Closest c = closest_hit<COUNT, STAMP, false, TLAS, false, kStage>(S, ps.o, ps.d, stack, lc, 99999.0f, false, bounce == 0);
             if (SHADOW || GBUFFER) ps.energy = __uint_as_float(stack.parked(kParkNdl));
             float ndl = 0.0f;
             int cont;

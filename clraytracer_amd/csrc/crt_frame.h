@@ -70,17 +70,27 @@ static bool frame_is_pipelined(int flags) { return (flags & CRT_RENDER_ASYNC) &&
 // event (sort_for_next_frame), so it runs while the host is between two crt1_render calls and is off the frame's
 // critical path.
 // One allocation per slot (FrameSlot::lists), for n = 8 x listCap entries: order[n] | per-tile costs[n] | sort keys[n] | the 8 list lengths.
+// The sort's launches on a `lists` allocation (a slot's, or crt_debug_launch_lists' scratch copy): spread > 0 ranks by the neighbours too
+static void launch_list_kernels(uint32_t* lists, int slotsPerXcd, int listCap, int tilesX, float spread, uint32_t maxSplit, float splitFactor, hipStream_t stream)
+{
+    const size_t n = (size_t)8 * (size_t)listCap;
+    uint32_t* cost = lists + n; uint32_t* key = cost;
+    if (spread > 0.0f) {
+        key = cost + n;
+        crt_cost_spread_kernel<<<(8 * slotsPerXcd + 255) / 256, 256, 0, stream>>>(cost, key, slotsPerXcd, tilesX, spread);
+    }
+    crt_order_kernel<<<8, 1024, 0, stream>>>(cost, key, lists, lists + 3 * n, slotsPerXcd, listCap, maxSplit, splitFactor);
+}
+static void launch_identity_lists(uint32_t* lists, int slotsPerXcd, int listCap, hipStream_t stream)
+{
+    crt_identity_order_kernel<<<(8 * slotsPerXcd + 255) / 256, 256, 0, stream>>>(lists, lists + 3 * (size_t)8 * (size_t)listCap, slotsPerXcd, listCap);
+}
+
 // this frame's per-tile costs -> the next frame's lists; with g.costSpread > 0 a tile is ranked by its neighbours' costs too
 static void launch_order_kernel(const CrtFrame& F, FrameSlot& fs, bool pipelined, bool noSplit)
 {
-    const size_t n = (size_t)8 * (size_t)F.listCap;
-    uint32_t* cost = fs.lists + n; uint32_t* key = cost;
-    if (g.costSpread > 0.0f && g.viewMoved) {
-        key = cost + n;
-        crt_cost_spread_kernel<<<(8 * F.slotsPerXcd + 255) / 256, 256, 0, fs.stream>>>(cost, key, F.slotsPerXcd, F.tilesX, g.costSpread);
-    }
-    crt_order_kernel<<<8, 1024, 0, fs.stream>>>(cost, key, fs.lists, fs.lists + 3 * n, F.slotsPerXcd, F.listCap, noSplit ? 0u : (uint32_t)(pipelined ? g.maxSplitPipelined : g.maxSplit),
-                                                 (pipelined ? g.splitBetaAsync : g.splitBeta) / (float)((g.numCUs / 8) * 4 * CRT_WAVES_PER_SIMD));
+    launch_list_kernels(fs.lists, F.slotsPerXcd, F.listCap, F.tilesX, g.viewMoved ? g.costSpread : 0.0f, noSplit ? 0u : (uint32_t)(pipelined ? g.maxSplitPipelined : g.maxSplit),
+                        (pipelined ? g.splitBetaAsync : g.splitBeta) / (float)((g.numCUs / 8) * 4 * CRT_WAVES_PER_SIMD), fs.stream);
 }
 
 // noSplit: the lists of the refill / block forms, whose entries are blocks of tiles, are never split
@@ -93,7 +103,7 @@ static int prepare_launch_lists(CrtFrame& F, unsigned& grid, FrameSlot& fs, bool
     RCCHK(fs.lists.grow(3 * n + 8, fs.stream));
     if (fs.orderSlots != F.slotsPerXcd || memcmp(key, fs.orderKey, sizeof key) != 0) {
         HIPCHK(hipMemsetAsync(fs.lists + n, 0, sizeof(uint32_t) * n, fs.stream));
-        crt_identity_order_kernel<<<(8 * F.slotsPerXcd + 255) / 256, 256, 0, fs.stream>>>(fs.lists, fs.lists + 3 * n, F.slotsPerXcd, F.listCap);
+        launch_identity_lists(fs.lists, F.slotsPerXcd, F.listCap, fs.stream);
         fs.orderSlots = F.slotsPerXcd; memcpy(fs.orderKey, key, sizeof key);
     } else if (!fs.listsReady) {
         launch_order_kernel(F, fs, pipelined, noSplit);
@@ -823,6 +833,57 @@ int crt1_debug_read_stamps(uint64_t* dst, size_t maxWaves, size_t* numWaves)
     const size_t n = maxWaves < g.stampWaves ? maxWaves : g.stampWaves;
     RCCHK(sync_all());
     HIPCHK(hipMemcpy(dst, g.stamps + 16, n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
+// Diagnostic: the sort of launch_order_kernel (or, slotsPerXcd < 0, the identity order) on costs the caller chose, in scratch memory and
+// on a stream of its own; the session's slots are not touched. Everything that could index outside a buffer, or take a float beyond an
+// int in the sort (splitFactor x the cost sum x 1023 / the maximum key <= slotsPerXcd x 1023 < 2^31), is refused before any launch.
+int crt1_debug_launch_lists(const uint32_t* cost, int slotsPerXcd, int tilesX, int maxSplit, float splitFactor, float spread,
+                            uint32_t* order, uint32_t* listLen, uint32_t* costAfter)
+{
+    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
+    const bool identity = slotsPerXcd < 0;
+    const long long S = identity ? -(long long)slotsPerXcd : (long long)slotsPerXcd;
+    if (!order || !listLen || S < 1 || S > (1 << 20)) return CRT_E_BAD_ARGUMENT;
+    if (!identity) {
+        if (!cost || !costAfter || tilesX < 1 || S % tilesX != 0 || maxSplit < 0 || maxSplit > CRT_MAX_SPLIT) return CRT_E_BAD_ARGUMENT;
+        if (!(splitFactor >= 0.0f && splitFactor <= 1.0f) || !(spread >= 0.0f && spread <= 1.0f)) return CRT_E_BAD_ARGUMENT;   // NaN fails both
+        // a cost no frame produces (four quadrant waves of at most 0x0FFFFFFF each, add_tile_cost); near 2^32 the lifted key would not fit
+        for (long long i = 0; i < 8 * S; ++i) if (cost[i] > 0x3FFFFFFCu) return CRT_E_BAD_ARGUMENT;
+    }
+    const int slots = (int)S, listCap = slots + 3 * CRT_MAX_SPLIT;
+    const size_t n = (size_t)8 * (size_t)listCap, costs = (size_t)8 * (size_t)slots;
+    DevBuf<uint32_t> lists; Stream st;
+    RCCHK(lists.alloc(3 * n + 8));
+    RCCHK(st.create(hipStreamNonBlocking));
+    if (identity) launch_identity_lists(lists, slots, listCap, st);
+    else {
+        HIPCHK(hipMemcpyAsync(lists + n, cost, costs * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        launch_list_kernels(lists, slots, listCap, tilesX, spread, (uint32_t)maxSplit, splitFactor, st);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(order, lists, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(listLen, lists + 3 * n, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (!identity) HIPCHK(hipMemcpyAsync(costAfter, lists + n, costs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return CRT_OK;
+}
+
+// Diagnostic: the lists slot 0's next frame of the same geometry would run on (the sort queued behind its last frame has built them)
+int crt1_debug_read_launch_lists(uint32_t* order, size_t cap, uint32_t listLen[8], int* slotsPerXcd, int* listCap)
+{
+    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
+    if (!listLen || !slotsPerXcd || !listCap) return CRT_E_BAD_ARGUMENT;
+    const FrameSlot& fs = g.slot[0];
+    if (!fs.lists || fs.orderSlots < 1 || !fs.listsReady) return CRT_E_UNSUPPORTED;
+    const int cap1 = fs.orderSlots + 3 * CRT_MAX_SPLIT;
+    const size_t n = (size_t)8 * (size_t)cap1;
+    *slotsPerXcd = fs.orderSlots; *listCap = cap1;
+    if (order && cap < n) return CRT_E_BAD_ARGUMENT;
+    HIPCHK(hipStreamSynchronize(fs.stream));
+    if (order) HIPCHK(hipMemcpy(order, fs.lists, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(listLen, fs.lists + 3 * n, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return CRT_OK;
 }
 

@@ -350,6 +350,15 @@ int crt_frame_time_stats(CrtFrameStats* out, int reset)
 }
 int crt_debug_read_stamps(uint64_t* dst, size_t maxWaves, size_t* numWaves) { ON_PRIMARY(crt1_debug_read_stamps(dst, maxWaves, numWaves)); }
 int crt_debug_read_frame_times(double* dst, size_t maxFrames, size_t* numFrames) { ON_PRIMARY(crt1_debug_read_frame_times(dst, maxFrames, numFrames)); }
+int crt_debug_launch_lists(const uint32_t* cost, int slotsPerXcd, int tilesX, int maxSplit, float splitFactor, float spread, uint32_t* order, uint32_t* listLen,
+                           uint32_t* costAfter)
+{
+    ON_PRIMARY(crt1_debug_launch_lists(cost, slotsPerXcd, tilesX, maxSplit, splitFactor, spread, order, listLen, costAfter));
+}
+int crt_debug_read_launch_lists(uint32_t* order, size_t cap, uint32_t listLen[8], int* slotsPerXcd, int* listCap)
+{
+    ON_PRIMARY(crt1_debug_read_launch_lists(order, cap, listLen, slotsPerXcd, listCap));
+}
 
 // work counters of the last counted frame: the sum over the devices (maxStack: the maximum)
 int crt_get_counters(CrtCounters* out)

@@ -189,6 +189,32 @@ class Session:
         _lib.check(self.hip.crt_debug_last_kernel(buf, len(buf)), "crt_debug_last_kernel")
         return buf.value.decode()
 
+    def launch_lists(self, cost, tiles_x, max_split, split_factor, spread=0.0):
+        """crt_debug_launch_lists: the feedback sort on chosen per-tile costs, cost of shape (8, slotsPerXcd). Returns (order (8, listCap)
+        uint32, listLen (8,) uint32, costAfter (8, slotsPerXcd) uint32)."""
+        cost = np.ascontiguousarray(cost, np.uint32)
+        S = cost.shape[1]
+        order = np.empty((8, S + 3 * 96), np.uint32); length = np.empty(8, np.uint32); after = np.empty((8, S), np.uint32)
+        _lib.check(self.hip.crt_debug_launch_lists(cost.ctypes.data, S, int(tiles_x), int(max_split), float(split_factor), float(spread),
+                                                   order.ctypes.data, length.ctypes.data, after.ctypes.data), "crt_debug_launch_lists")
+        return order, length, after
+
+    def identity_lists(self, slots_per_xcd):
+        """crt_debug_launch_lists with -slots_per_xcd: the first frame's identity order, (order (8, listCap), listLen (8,))."""
+        S = int(slots_per_xcd)
+        order = np.empty((8, S + 3 * 96), np.uint32); length = np.empty(8, np.uint32)
+        _lib.check(self.hip.crt_debug_launch_lists(None, -S, 1, 0, 0.0, 0.0, order.ctypes.data, length.ctypes.data, None), "crt_debug_launch_lists")
+        return order, length
+
+    def read_launch_lists(self):
+        """crt_debug_read_launch_lists: (order (8, listCap) uint32, listLen (8,) uint32, slotsPerXcd) of the lists the next synchronous
+        frame would run on; CrtError (CRT_E_UNSUPPORTED) when the session keeps none."""
+        length = np.empty(8, np.uint32); S, cap = C.c_int(0), C.c_int(0)
+        _lib.check(self.hip.crt_debug_read_launch_lists(None, 0, length.ctypes.data, C.byref(S), C.byref(cap)), "crt_debug_read_launch_lists")
+        order = np.empty((8, cap.value), np.uint32)
+        _lib.check(self.hip.crt_debug_read_launch_lists(order.ctypes.data, order.size, length.ctypes.data, C.byref(S), C.byref(cap)), "crt_debug_read_launch_lists")
+        return order, length, int(S.value)
+
     def read_output(self):
         out = np.empty((self.height, self.width, 4), np.float32)
         _lib.check(self.hip.crt_read_output(out.ctypes.data, out.size), "crt_read_output")

@@ -62,6 +62,23 @@ int crt_debug_ao_stats(uint64_t out[3]);
  * counted when it is created and when it is released). Works without a session: 0 before the first crt_init and again after
  * crt_shutdown -- what the tests use to see that a session leaves nothing behind (tests/test_gpu_resources.py). */
 int crt_debug_live_resources(uint64_t* out);
+/* Test hook: the feedback sort of a synchronous frame (crt_cost_spread_kernel iff spread > 0, then crt_order_kernel, with production's
+ * launch shapes) on per-tile costs the caller chose -- cost[8 * slotsPerXcd], XCD x's tile i at [x * slotsPerXcd + i] -- in scratch memory
+ * laid out as a frame slot's lists and on a stream of its own; the session is not touched. Returns order[8 * listCap] with listCap =
+ * slotsPerXcd + 3 * 96 (entry = tile | quadrant << 28 | split << 31; XCD x's list at [x * listCap], listLen[x] entries of it are defined),
+ * listLen[8] and costAfter[8 * slotsPerXcd] (the costs as the sort leaves them for the next frame's waves: zero). slotsPerXcd < 0: the
+ * identity order of the first frame (crt_identity_order_kernel) for -slotsPerXcd tiles; cost and costAfter are then not used.
+ * CRT_E_BAD_ARGUMENT, with nothing launched: a null pointer, |slotsPerXcd| outside 1 .. 1 << 20, tilesX < 1 or not a divisor of
+ * slotsPerXcd, maxSplit outside 0 .. 96, splitFactor or spread not finite or outside [0, 1], a cost above 0x3FFFFFFC (more than a frame's
+ * waves can add). */
+int crt_debug_launch_lists(const uint32_t* cost, int slotsPerXcd, int tilesX, int maxSplit, float splitFactor, float spread,
+                           uint32_t* order, uint32_t* listLen, uint32_t* costAfter);
+/* Diagnostic: the feedback launch lists of the first frame slot (the slot of synchronous frames) as its next frame of the same geometry
+ * would run on them, once what is queued on the slot has finished: *slotsPerXcd, *listCap, listLen[8] and, if order is not NULL, the
+ * 8 * *listCap entries (cap, the entries order has room for, smaller: CRT_E_BAD_ARGUMENT with the two sizes set). CRT_E_UNSUPPORTED when
+ * the slot has no lists: no frame yet, CRT_FEEDBACK=0, or a kernel form without them (wavefront, ldstop). For refill and block a
+ * list entry is a block of tiles. */
+int crt_debug_read_launch_lists(uint32_t* order, size_t cap, uint32_t listLen[8], int* slotsPerXcd, int* listCap);
 
 #ifdef __cplusplus
 }

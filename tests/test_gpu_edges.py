@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from clraytracer_amd import _lib, driver, scenes
+import launch_lists_ref
 import oracle_lib
 from util import bits, seeded_rays
 
@@ -160,6 +161,12 @@ def test_feedback_launch_lists_never_change_pixels(nthreads):
 
         for _ in range(4):                       # identity order, then lists built from real costs (with split tiles)
             check()
+        # "with split tiles" is checked, not assumed: the lists the next frame runs on cover every tile exactly once and hold quadrant
+        # entries (an XCD of this 25 x 15-tile frame has 50 tiles for 1024 wave slots, so most owned tiles outlast the default threshold)
+        order, length, slots = s.read_launch_lists()
+        split = [n for n, _ in launch_lists_ref.check_structure(order, length, slots)]
+        print(f"tiny 200x120, default split rule: split tiles per XCD {split}")
+        assert slots == 50 and max(split) >= 1
         s.render_raw(8)                          # steady state: every tile exactly once (or as four quadrants) -> counters match
         iv, ip, pos = s.camera()
         _, st = orc.trace(orc.raygen(s.width, s.height, iv, ip), pos, sc.sun_angle)

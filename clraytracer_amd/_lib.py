@@ -140,6 +140,7 @@ HIP_API = {
     "crt_ao_device_ptr": (_vp, []),
     "crt_debug_ao_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "crt_debug_live_resources": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "crt_debug_recip_sweep": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]),
     "crt_read_output": (C.c_int, [_vp, _sz]),
     "crt_read_output_rows": (C.c_int, [_vp, C.c_int, C.c_int]),
     "crt_read_output_rgba8": (C.c_int, [_vp, _sz]),

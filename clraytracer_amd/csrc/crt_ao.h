@@ -141,7 +141,10 @@ __device__ __forceinline__ void crt_ao_body(CrtDevScene S0, CrtAoArgs A, CrtFram
                     if (dot3(d, n2) < 0.0f) d = neg3(d);
                     const float w = dot3(d, n2);
                     const CrtStackT<TLAS ? CRT_TLAS_PARK : 0> stack = { s_stack + lane2, S0.stackOverflow };
-                    const Closest c = closest_hit<false, false, true, TLAS, INCLUSIVE>(S, o, d, stack, lc, best0, noCull);
+                    // (kDivide: the G-buffer source without an instance tree keeps the reciprocals as divisions, crt_device.h: recip -- with the
+                    // short form's branch in the triangle loop it spills one register)
+                    constexpr bool kDivide = SOURCE == CRT_AO_FRAME && !TLAS;
+                    const Closest c = closest_hit<false, false, true, TLAS, INCLUSIVE, false, kDivide>(S, o, d, stack, lc, best0, noCull);
                     const float occ = c.anyHit ? 1.0f : 0.0f;
                     num += w * occ; den += w;
                 }

@@ -248,12 +248,67 @@ __device__ __forceinline__ float intersect_aabb(v3 o, v3 inv, float4 bmin, float
     } else return (tnear < tfar && tnear > 0.0f && tnear < minSoFar) ? tnear : 1e30f;
 }
 
+// ------------------------------------------------------------------------------------------------
+// `1.0f / x` of the traversal (native_recip pinned to IEEE: Traversal::enter's three 1 / md, intersect_triangle's 1 / a) in four
+// instructions instead of the division's eleven: v_rcp_f32, one Newton step, v_div_fixup_f32. Over all 2^32 inputs the short
+// sequence returns the bits of `1.0f / x` for every x with a biased exponent of 1 ... 252 and for every zero, infinity and NaN
+// (payloads included); it differs only for denormal x and for finite |x| >= 2^126, whose quotient is denormal
+// (tools/ubench/recip_exhaustive.hip; crt_debug_recip_sweep re-checks both facts on the device the library runs on).
+// The guard: v_frexp_exp_i32_f32 is 0 for zeros, infinities and NaNs, <= -126 for denormals, >= 127 for finite |x| >= 2^126, and
+// -125 ... 126 for everything the short sequence gets right -- so "outside -125 ... 126" is exactly the set that needs the division.
+// The decision is taken for the WAVE (one compare mask against zero, a uniform branch the wave falls through): if any lane active at
+// this step needs the division, every lane of the step takes the division's result, otherwise the division is a block no lane enters.
+// DIVIDE: the division as written, no guard. The counted instantiations (Traversal<COUNT = true>: diagnostics, never the frame a user
+// waits for) keep it, so that a counted launch runs the same instructions whatever the uncounted ones do; so does everything under
+// -DCRT_IEEE_RECIP (A/B builds).
+// ------------------------------------------------------------------------------------------------
+#ifdef CRT_IEEE_RECIP
+#define CRT_RECIP_DIVIDES(DIVIDE) true
+#else
+#define CRT_RECIP_DIVIDES(DIVIDE) (DIVIDE)
+#endif
+__device__ __forceinline__ float recip_short(float x)
+{
+    float r = __builtin_amdgcn_rcpf(x);
+    const float e = __builtin_fmaf(-x, r, 1.0f);
+    r = __builtin_fmaf(e, r, r);
+    return __builtin_amdgcn_div_fixupf(r, x, 1.0f);
+}
+// per lane: x is outside what recip_short gets right (x = m 2^e, 0.5 <= |m| < 1: e outside -125 ... 126; 0, inf, NaN give e = 0)
+__device__ __forceinline__ bool recip_needs_division(int e) { return (uint32_t)(e + 125) > 251u; }
+__device__ __forceinline__ bool recip_needs_division(float x) { return recip_needs_division(__builtin_amdgcn_frexp_expf(x)); }
+
+template <bool DIVIDE = false>
+__device__ __forceinline__ float recip(float x)
+{
+    if constexpr (CRT_RECIP_DIVIDES(DIVIDE)) return 1.0f / x;
+    else {
+        float r = recip_short(x);
+        if (__builtin_expect(__ballot(recip_needs_division(x)) != 0, 0)) r = 1.0f / x;
+        return r;
+    }
+}
+// the three of an instance entry under one decision: the largest and the smallest exponent stand for all three
+template <bool DIVIDE = false>
+__device__ __forceinline__ v3 recip3(v3 d)
+{
+    if constexpr (CRT_RECIP_DIVIDES(DIVIDE)) return mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    else {
+        const int ex = __builtin_amdgcn_frexp_expf(d.x), ey = __builtin_amdgcn_frexp_expf(d.y), ez = __builtin_amdgcn_frexp_expf(d.z);
+        const int hi = max(max(ex, ey), ez), lo = min(min(ex, ey), ez);
+        v3 r = mk3(recip_short(d.x), recip_short(d.y), recip_short(d.z));
+        if (__builtin_expect(__ballot(hi > 126 || lo < -125) != 0, 0)) r = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+        return r;
+    }
+}
+
 // kernel_main.cl:84-106; hot = {v0, edge1, edge2}
+template <bool DIVIDE = false>
 __device__ __forceinline__ int intersect_triangle(v3 o, v3 d, v3 x, v3 edge1, v3 edge2, Triout& out, uint32_t i)
 {
     const v3 h = cross3(d, edge2);
     const float a = dot3(edge1, h);
-    const float f = 1.0f / a;
+    const float f = recip<DIVIDE>(a);
     const v3 s = sub3(o, x);
     const float u = f * dot3(s, h);
     const v3 q = cross3(s, edge1);
@@ -361,7 +416,7 @@ __device__ __forceinline__ CrtDevInstance load_instance(const CrtDevInstance* __
 // so results are bit-identical; only the interleaving between lanes differs.
 // The stack lives in LDS/scratch (CRT_STACK_*); slot indices wrap modulo 32 where upstream's array would overflow.
 // ------------------------------------------------------------------------------------------------
-template <bool COUNT>
+template <bool COUNT, bool DIVIDE = COUNT>
 struct Traversal {
     v3 mo, md, inv;               // ray in the current instance's object space (direction not renormalised, hazard H6)
     Triout tr;                    // running best of the current instance (kernel_main.cl:200-202)
@@ -409,7 +464,7 @@ struct Traversal {
         const CrtDevInstance I = load_instance(S.devInstances, inst);
         mo = xform_xyz(I, o.x, o.y, o.z, 1.0f);
         md = xform_xyz(I, d.x, d.y, d.z, 0.0f);
-        inv = mk3(1.0f / md.x, 1.0f / md.y, 1.0f / md.z);       // native_recip pinned to IEEE
+        inv = recip3<DIVIDE>(md);                                   // native_recip pinned to IEEE: the bits of 1.0f / x
         tr.t = bestSoFar; tr.tri = 0; tr.u = 0.0f; tr.v = 0.0f;
         ref = __float_as_uint(TOP ? I.r2.w : I.r0.w);            // the root is popped at once: sp 1 -> 0, protection 0 -> 1
         sp = 0; prot = 1; inters = 0; active = true;
@@ -486,7 +541,7 @@ struct Traversal {
         for (uint32_t i = first, end = first + n; i < end; ++i) {
             if (COUNT) lc.triTests++;
             const float* __restrict__ hot = S.triHot + (size_t)i * 9;
-            inters |= intersect_triangle(mo, md, mk3(hot[0], hot[1], hot[2]), mk3(hot[3], hot[4], hot[5]), mk3(hot[6], hot[7], hot[8]), tr, i);
+            inters |= intersect_triangle<DIVIDE>(mo, md, mk3(hot[0], hot[1], hot[2]), mk3(hot[3], hot[4], hot[5]), mk3(hot[6], hot[7], hot[8]), tr, i);
             if (ANYHIT) { if (inters) break; }
         }
         if (ANYHIT && inters) finish(c);
@@ -720,8 +775,8 @@ __device__ __forceinline__ bool tlas_candidates(const CrtDevScene& S, v3 o, v3 d
 // for all later instances. `anyHit` is the same boolean the full closest-hit loop would return, because until the
 // first passing triangle both visit the same nodes in the same order; only the work (and the counters) shrink.
 // ITERS (stamped diagnostic launches): the counters record wave-level trips instead of per-ray work.
-template <bool COUNT, bool ITERS, bool ANYHIT, bool INCLUSIVE = false, class STK>
-__device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stack, Traversal<COUNT>& T, Closest& c, LaneCounters& lc, bool done)
+template <bool COUNT, bool ITERS, bool ANYHIT, bool INCLUSIVE = false, bool DIVIDE, class STK>
+__device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stack, Traversal<COUNT, DIVIDE>& T, Closest& c, LaneCounters& lc, bool done)
 {
     if (!done && T.at_inner()) {
         if (ITERS) { lc.rays++; if (first_active_lane()) lc.innerVisits++; }
@@ -753,13 +808,13 @@ __device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stac
 // STAGE (the uncounted Trace kernels without an instance tree only) + sharedOrigin (wave-uniform, run time: the camera bounce): the
 // chunk's mask comes from staged_candidate_mask -- the same mask, bit for bit. A run-time value, not a second instantiation: the trip
 // loop below exists once per kernel.
-template <bool COUNT, bool ITERS = false, bool ANYHIT = false, bool TLAS = false, bool INCLUSIVE = false, bool STAGE = false, class STK = CrtStack>
+template <bool COUNT, bool ITERS = false, bool ANYHIT = false, bool TLAS = false, bool INCLUSIVE = false, bool STAGE = false, bool DIVIDE = COUNT, class STK = CrtStack>
 __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d, const STK& stack, LaneCounters& lc, float best0 = 99999.0f,
                                                bool chunkedOnly = false, bool sharedOrigin = false)
 {
     static_assert(!STAGE || (!COUNT && !ITERS && !ANYHIT && !TLAS && !STK::kTop), "staged cull terms: uncounted closest-hit traversals of one-wave workgroups");
     Closest c = no_hit(best0);
-    Traversal<COUNT> T; T.reset();
+    Traversal<COUNT, DIVIDE> T; T.reset();
 
     if constexpr (TLAS) {
         // Many instances: every lane collects its (few) candidates from the instance tree and walks them in ascending

@@ -641,6 +641,28 @@ int crt1_debug_measure_clock(int micros, double* ghz)
     return CRT_OK;
 }
 
+// Diagnostic: crt_recip_sweep_kernel (crt_recip.h) over `count` bit patterns from `first`; one launch on a stream of its own.
+int crt1_debug_recip_sweep(uint32_t first, uint64_t count, uint64_t out[4])
+{
+    if (!g.initialized) return CRT_E_NOT_INITIALIZED;
+    if (!out || count > (1ull << 32)) return CRT_E_BAD_ARGUMENT;
+    DevBuf<unsigned long long> d; Stream st;
+    RCCHK(d.alloc(4));
+    RCCHK(st.create(hipStreamNonBlocking));
+    unsigned long long h[4] = { 0, 0, 0, ~0ull };
+    HIPCHK(hipMemcpyAsync(d, h, sizeof h, hipMemcpyHostToDevice, st));
+    if (count) {
+        const unsigned long long blocks = (count + 255) / 256;
+        crt_recip_sweep_kernel<<<(unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, st>>>(first, (unsigned long long)count, d);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    out[0] = h[0]; out[1] = h[1]; out[2] = h[2];
+    out[3] = h[3] == ~0ull ? ~0ull : (uint64_t)(uint32_t)(first + (uint32_t)h[3]);
+    return CRT_OK;
+}
+
 int crt1_sync(void)
 {
     if (!g.initialized) return CRT_E_NOT_INITIALIZED;

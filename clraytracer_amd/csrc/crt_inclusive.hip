@@ -1,6 +1,6 @@
 // crt_inclusive.hip -- crt_rays_inclusive_kernel and crt_ao_inclusive_kernel, the kernels of crt_trace_rays / crt_trace_ao / crt_frame_ao under
 // the inclusive box test (declarations and description: crt_inclusive.h; bodies: crt_rays.h, crt_ao.h); fourth translation unit of libcrt_hip.so.
-// Build: with the other three units, same flags (Makefile).
+// Build: with the other units, same flags (Makefile).
 #include <hip/hip_runtime.h>
 #include "../../include/crt_api.h"
 #define CRT_AO_DEVICE_TABLE crt_ao_inclusive_table_dev

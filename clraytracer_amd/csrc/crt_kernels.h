@@ -381,6 +381,9 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
     constexpr bool SSAA = CASE == CRT_TRACE_SSAA, GBUFFER = CASE == CRT_TRACE_GBUFFER;
     constexpr int kParkNdl = TLAS ? CRT_TLAS_PARK : 0;
     constexpr bool kStage = !COUNT && !STAMP && !TLAS && !STK::kTop;      // staged_candidate_mask (crt_device.h)
+    // the reciprocals as divisions (crt_device.h: recip): the counted launches, and the one G-buffer kernel that sits at its 64 VGPRs so
+    // tightly that the short form's branch costs it 8 spilled registers (shadow rays + instance tree without refraction)
+    constexpr bool kDivide = COUNT || (GBUFFER && SHADOW && TLAS && !REFRACT);
     LaneCounters lc; zero_counters(lc);
     WaveStampStart t0 = { 0, 0 };
     if (STAMP) t0 = wave_stamp_start();
@@ -397,7 +400,7 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
             // (GBUFFER: the same -- the plane stores' addresses take the register the plain kernel keeps the energy in)
             if (SHADOW || GBUFFER) stack.park(kParkNdl, __float_as_uint(ps.energy));
             // kStage: at the camera bounce every ray of the wave starts at F.camPos -- the cull's origin-only terms are computed once per wave
-            Closest c = closest_hit<COUNT, STAMP, false, TLAS, false, kStage>(S, ps.o, ps.d, stack, lc, 99999.0f, false, bounce == 0);
+            Closest c = closest_hit<COUNT, STAMP, false, TLAS, false, kStage, kDivide>(S, ps.o, ps.d, stack, lc, 99999.0f, false, bounce == 0);
             if (SHADOW || GBUFFER) ps.energy = __uint_as_float(stack.parked(kParkNdl));
             float ndl = 0.0f;
             int cont;
@@ -417,7 +420,7 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
                     if (ndl > 0.0f) {
                         if (COUNT) { lc.rays++; lc.shadowRays++; }
                         stack.park(kParkNdl, __float_as_uint(ndl));
-                        const Closest sc = closest_hit<COUNT, false, true, TLAS>(S, ps.o, neg3(mk3(0.0f, F.lightY, F.lightZ)), stack, lc);
+                        const Closest sc = closest_hit<COUNT, false, true, TLAS, false, false, kDivide>(S, ps.o, neg3(mk3(0.0f, F.lightY, F.lightZ)), stack, lc);
                         if (sc.anyHit) { shadow = 0.0f; if (COUNT) lc.shadowHits++; }
                         ndl = __uint_as_float(stack.parked(kParkNdl));
                     }
@@ -591,7 +594,8 @@ __global__ __launch_bounds__(CRT_BLOCK, COUNT ? CRT_WAVES_PER_SIMD_COUNT : CRT_W
         const float4 partial = out[r.pixel];
         PathState ps = unpack_bounce(r, mk3(partial.x, partial.y, partial.z));
         if (COUNT) { lc.rays++; lc.secondary++; }
-        Closest c = closest_hit<COUNT>(S, ps.o, ps.d, stack, lc);
+        // (the reciprocals as divisions, crt_device.h: recip -- this opt-in form's kernel is recorded register for register, and stays that)
+        Closest c = closest_hit<COUNT, false, false, false, false, false, true>(S, ps.o, ps.d, stack, lc);
         const bool cont = shade_bounce(S, c, ps, 1, F.lightY, F.lightZ) != 0;
         if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
         out[r.pixel] = make_float4(ps.result.x, ps.result.y, ps.result.z, 1.0f);

@@ -3,15 +3,15 @@
 // Replaces the OpenCL side of the reference's Renderer.cpp / ResourceManager.cpp: device pools,
 // uploads, the per-frame RayGen -> Trace -> PostProcess launch (Renderer.cpp:305-375). Uploads
 // arrive in the reference's struct layouts and are re-laid-out on the device (crt_device.h).
-// One translation unit (and crt_rays.hip, the ray-query kernel, crt_ao.hip, the ambient-occlusion kernels, and crt_inclusive.hip, both under the inclusive box test, beside it); the parts (round 5 split what used to be one 2,000-line file):
+// One translation unit (and crt_rays.hip, the ray-query kernel, crt_ao.hip, the ambient-occlusion kernels, crt_inclusive.hip, both under the inclusive box test, and crt_recip.hip, the reciprocal sweep, beside it); the parts (round 5 split what used to be one 2,000-line file):
 //   kernels     crt_device.h (traversal + shading), crt_kernels.h (launches), crt_refill.h (opt-in in-wave compaction forms), crt_ldstop.h (opt-in: tree tops staged in LDS),
 //               crt_relayout.h (upload-time layouts), crt_bvh_build.h (device BuildBVH); crt_rays.h declares the ray-query kernel of the second unit, crt_rays.hip,
 //               crt_ao.h the ambient-occlusion kernels of the third, crt_ao.hip, crt_inclusive.h both under the inclusive box test, the fourth, crt_inclusive.hip; crt_query.h: the steps those units' kernels share
 //   host state  crt_own.h (the owners of device / pinned buffers, events and streams), crt_state.h (State / FrameSlot, helpers), crt_instances.h (instance tables, cull bounds, instance tree)
 //   entry impl  crt_upload.h (init, uploads, read-backs), crt_bvh_driver.h (crt_build_bvh), crt_frame.h (crt_render and what a frame
 //               needs), crt_query_host.h (the queries on device buffers: context, launch, statistics; crt_trace_rays), crt_ao_host.h (crt_trace_ao, crt_frame_ao), crt_multidev.h (several devices behind the same calls)
-// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared crt_shim.hip crt_rays.hip crt_ao.hip crt_inclusive.hip (the Makefile's rule; a library of this unit
-// alone links but does not load: crt_query_host.h and crt_ao_host.h refer to the kernels the other three define)
+// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared crt_shim.hip crt_rays.hip crt_ao.hip crt_inclusive.hip crt_recip.hip (the Makefile's rule; a library of this unit
+// alone links but does not load: crt_query_host.h, crt_ao_host.h and crt_frame.h refer to the kernels the other four define)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <cmath>
@@ -26,6 +26,7 @@
 #include "crt_rays.h"
 #include "crt_ao.h"
 #include "crt_inclusive.h"
+#include "crt_recip.h"
 #include "crt_relayout.h"
 #include "crt_bvh_build.h"
 #include <vector>
@@ -194,6 +195,7 @@ int crt_debug_last_kernel(char* dst, size_t cap)
     return CRT_OK;
 }
 int crt_debug_measure_clock(int micros, double* ghz) { ON_PRIMARY(crt1_debug_measure_clock(micros, ghz)); }
+int crt_debug_recip_sweep(uint32_t first, uint64_t count, uint64_t out[4]) { ON_PRIMARY(crt1_debug_recip_sweep(first, count, out)); }
 int crt_debug_live_resources(uint64_t* out) { if (!out) return CRT_E_BAD_ARGUMENT; *out = (uint64_t)gLiveOwned.load(); return CRT_OK; }
 
 int crt_shutdown(void)

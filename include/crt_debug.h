@@ -73,6 +73,16 @@ int crt_debug_live_resources(uint64_t* out);
  * waves can add). */
 int crt_debug_launch_lists(const uint32_t* cost, int slotsPerXcd, int tilesX, int maxSplit, float splitFactor, float spread,
                            uint32_t* order, uint32_t* listLen, uint32_t* costAfter);
+/* Diagnostic: the traversal's short reciprocal (v_rcp_f32 + one Newton step + v_div_fixup_f32 behind a wave-level guard that sends denormal
+ * operands and finite |x| >= 2^126 to the division) against the device's own `1.0f / x`, compared as bits, NaN payloads included, over the
+ * `count` (<= 2^32) float bit patterns first, first + 1, ... (mod 2^32), in one launch; 64 consecutive patterns share a wave.
+ *   out[0]  results of the guarded form that differ: each pattern alone in its wave step, then the wave's 64 deciding together, then as one
+ *           of three operands under the instance entry's single decision
+ *   out[1]  patterns the unguarded short sequence gets wrong that the guard would NOT send to the division
+ *   out[2]  patterns the guard sends to the division although the short sequence is right (informational: how tight the guard is)
+ *   out[3]  the first pattern, in sweep order, counted in out[0] or out[1]; UINT64_MAX if none
+ * A library built with -DCRT_IEEE_RECIP divides everywhere: out[0] is then 0 by construction, out[1] and out[2] describe the same guard. */
+int crt_debug_recip_sweep(uint32_t first, uint64_t count, uint64_t out[4]);
 /* Diagnostic: the feedback launch lists of the first frame slot (the slot of synchronous frames) as its next frame of the same geometry
  * would run on them, once what is queued on the slot has finished: *slotsPerXcd, *listCap, listLen[8] and, if order is not NULL, the
  * 8 * *listCap entries (cap, the entries order has room for, smaller: CRT_E_BAD_ARGUMENT with the two sizes set). CRT_E_UNSUPPORTED when

@@ -36,11 +36,11 @@ tools/ubench/cumask: tools/ubench/cumask.hip
 $(EXAMPLE): examples/headless_main.cpp $(HOST_SO)
 	$(CXX) $(CXXFLAGS) -o $@ examples/headless_main.cpp -Lclraytracer_amd/host -lcrt_host -Lclraytracer_amd/csrc -lcrt_hip -Wl,-rpath,'$$ORIGIN/../clraytracer_amd/host' -Wl,-rpath,'$$ORIGIN/../clraytracer_amd/csrc'
 
-# five translation units: crt_shim.hip (the C-ABI and every frame kernel), crt_rays.hip (the kernel of crt_trace_rays), crt_ao.hip (the
+# six translation units: crt_shim.hip (the C-ABI and every frame kernel), crt_rays.hip (the kernel of crt_trace_rays), crt_ao.hip (the
 # kernels of crt_trace_ao / crt_frame_ao; its direction table crt_ao_table.h is written by tools/make_ao_table.py and committed),
-# crt_inclusive.hip (the kernels of the three queries under the inclusive box test) and crt_recip.hip (the kernel of crt_debug_recip_sweep)
-$(HIP_SO): $(wildcard clraytracer_amd/csrc/*.h) clraytracer_amd/csrc/crt_shim.hip clraytracer_amd/csrc/crt_rays.hip clraytracer_amd/csrc/crt_ao.hip clraytracer_amd/csrc/crt_inclusive.hip clraytracer_amd/csrc/crt_recip.hip include/crt_api.h include/crt_debug.h include/crt_types.h
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ clraytracer_amd/csrc/crt_shim.hip clraytracer_amd/csrc/crt_rays.hip clraytracer_amd/csrc/crt_ao.hip clraytracer_amd/csrc/crt_inclusive.hip clraytracer_amd/csrc/crt_recip.hip
+# crt_inclusive.hip (the kernels of the three queries under the inclusive box test), crt_recip.hip (the kernel of crt_debug_recip_sweep) and crt_shade.hip (the kernel of crt_shade_rays)
+$(HIP_SO): $(wildcard clraytracer_amd/csrc/*.h) clraytracer_amd/csrc/crt_shim.hip clraytracer_amd/csrc/crt_rays.hip clraytracer_amd/csrc/crt_ao.hip clraytracer_amd/csrc/crt_inclusive.hip clraytracer_amd/csrc/crt_recip.hip clraytracer_amd/csrc/crt_shade.hip include/crt_api.h include/crt_debug.h include/crt_types.h
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ clraytracer_amd/csrc/crt_shim.hip clraytracer_amd/csrc/crt_rays.hip clraytracer_amd/csrc/crt_ao.hip clraytracer_amd/csrc/crt_inclusive.hip clraytracer_amd/csrc/crt_recip.hip clraytracer_amd/csrc/crt_shade.hip
 
 $(HOST_SO): $(HOST_SRC) $(HOST_HDR) $(HIP_SO)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRC) -Lclraytracer_amd/csrc -lcrt_hip -lrt -Wl,-rpath,'$$ORIGIN/../csrc'

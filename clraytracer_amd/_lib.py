@@ -38,6 +38,11 @@ CRT_RAYS_CLOSEST, CRT_RAYS_OCCLUDED = 0, 1      # crt_trace_rays modes
 CRT_RAYS_INCLUSIVE = 0x100                      # OR-ed into the mode: the inclusive box test (include/crt_api.h)
 
 
+class CrtShadeParams(C.Structure):
+    """Parameters of crt_shade_rays (include/crt_types.h): a finite sun angle, flags 0."""
+    _fields_ = [("sunAngle", C.c_float), ("flags", C.c_uint32)]
+
+
 class CrtAoParams(C.Structure):
     """Parameters of crt_trace_ao / crt_frame_ao (include/crt_types.h): samples in {1, 2, 4, ..., 64}, radius > 0, a finite bias."""
     _fields_ = [("samples", C.c_uint32), ("radius", C.c_float), ("bias", C.c_float), ("seed", C.c_uint32), ("flags", C.c_uint32),
@@ -90,6 +95,9 @@ GBUFFER_PLANE_DTYPES = {"geometry": (CRT_GBUFFER_GEOMETRY, GBUFFER_GEOMETRY_DTYP
 GBUFFER_PIXEL_DTYPE = np.dtype([("normal", "<f4", 3), ("t", "<f4"), ("instance", "<i4"), ("tri", "<u4"), ("u", "<f4"), ("v", "<f4"),
                                 ("albedo", "<u4")])
 assert GBUFFER_GEOMETRY_DTYPE.itemsize == 16 and GBUFFER_IDS_DTYPE.itemsize == 16 and GBUFFER_PIXEL_DTYPE.itemsize == 36
+# one ray's first-hit surface record of crt_shade_rays (CrtSurfaceHit): the G-buffer pixel, then the material index and the interpolated uv
+SURFACE_HIT_DTYPE = np.dtype(GBUFFER_PIXEL_DTYPE.descr + [("material", "<u4"), ("texU", "<f4"), ("texV", "<f4")])
+assert SURFACE_HIT_DTYPE.itemsize == 48 and C.sizeof(CrtShadeParams) == 8
 
 _f = C.c_float
 _fp = C.POINTER(C.c_float)
@@ -139,6 +147,8 @@ HIP_API = {
     "crt_read_ao": (C.c_int, [_vp, _sz]),
     "crt_ao_device_ptr": (_vp, []),
     "crt_debug_ao_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "crt_shade_rays": (C.c_int, [C.POINTER(CrtRayBatch), C.POINTER(CrtShadeParams), C.c_uint32, _vp, _vp, _vp]),
+    "crt_debug_shade_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "crt_debug_live_resources": (C.c_int, [C.POINTER(C.c_uint64)]),
     "crt_debug_recip_sweep": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]),
     "crt_read_output": (C.c_int, [_vp, _sz]),
@@ -212,6 +222,7 @@ HOST_API = {
     "crth_render": (C.c_uint, [_f]),
     "crth_map_output": (_vp, []),
     "crth_trace_rays": (C.c_int, [C.POINTER(CrtRayBatch), C.c_int, _vp, _vp]),
+    "crth_shade_rays": (C.c_int, [C.POINTER(CrtRayBatch), C.POINTER(CrtShadeParams), _vp, _vp, _vp]),
     "crth_trace_ao": (C.c_int, [C.POINTER(CrtAoPoints), C.POINTER(CrtAoParams), _vp, _vp]),
     "crth_compute_ao": (C.c_int, [C.POINTER(CrtAoParams), _vp]),
     "crth_map_ao": (_vp, []),

@@ -30,6 +30,7 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 #include <type_traits>
+#include <utility>
 #include "../../include/crt_types.h"
 
 #define CRT_LEAF_BIT 0x80000000u
@@ -962,7 +963,13 @@ __device__ __forceinline__ float specular_x(float ndl, float shadow)
 // SINK (CRT_RENDER_GBUFFER: GBufferSink, crt_kernels.h; NoSink: nothing): at bounce 0 `sink` is handed what the primary ray found
 // where it is in registers anyway -- sink->miss(c) before the skybox lookup, sink->hit(c, record.normal, the bytes of record.color)
 // (kernel_main.cl:236,245) behind the texture fetch -- so that nothing of it has to stay alive through the second traversal.
+// A sink that also wants what only this function knows of the hit -- the material index as clamped below (kernel_main.cl:229) and the
+// interpolated uv before SampleTexture's fract (kernel_main.cl:238-240) -- provides hit(c, normal, albedo, material, texU, texV) as well
+// (SurfaceSink, crt_shade.h); GBufferSink does not and is called as before.
 struct NoSink { };
+template <class SINK, class = void> struct SinkTakesSurface : std::false_type { };
+template <class SINK>
+struct SinkTakesSurface<SINK, std::void_t<decltype(std::declval<const SINK&>().hit(std::declval<const Closest&>(), v3(), 0u, 0u, 0.0f, 0.0f))>> : std::true_type { };
 template <bool DEFER_ENERGY = false, bool REFRACT = false, class SINK = NoSink>
 __device__ __forceinline__ int shade_bounce(const CrtDevScene& S, const Closest& c, PathState& ps, int bounce, float lightY, float lightZ,
                                             float* ndlOut = nullptr, const SINK* sink = nullptr)
@@ -1013,7 +1020,12 @@ __device__ __forceinline__ int shade_bounce(const CrtDevScene& S, const Closest&
     const uint32_t cg = ((((a >> 8) & 0xffu) * ((px >> 8) & 0xffu)) >> 8) & 0xffu;
     const uint32_t cb = ((((a >> 16) & 0xffu) * ((px >> 16) & 0xffu)) >> 8) & 0xffu;
     const v3 color = scale3(mk3((float)cr, (float)cg, (float)cb), UcharToFloat01);
-    if constexpr (kSink) { if (bounce == 0) sink->hit(c, normal, 0xFF000000u | (cb << 16) | (cg << 8) | cr); }
+    if constexpr (kSink) {
+        if (bounce == 0) {
+            if constexpr (SinkTakesSurface<SINK>::value) sink->hit(c, normal, 0xFF000000u | (cb << 16) | (cg << 8) | cr, mi, uvx, uvy);
+            else sink->hit(c, normal, 0xFF000000u | (cb << 16) | (cg << 8) | cr);
+        }
+    }
     const v3 point = add3(mo, scale3(md, c.hit.t));
 
 

@@ -9,6 +9,7 @@
 //   crt_postprocess_kernel  PostProcess (kernel_main.cl:342-359)
 //   crt_query_kernel        closest-hit records for explicit rays on the host (parity tests, counted)
 //   crt_rays_kernel         closest hit / occlusion for batches of rays on the device (crt_trace_rays): declared in crt_rays.h, compiled in crt_rays.hip
+//   crt_shade_kernel        radiance / first-hit surface records for batches of rays on the device (crt_shade_rays): declared in crt_shade.h, compiled in crt_shade.hip
 //   crt_order_kernel        feedback launch lists: per-XCD counting sort of the tiles by last frame's cost
 // Device-side traversal/shading code lives in crt_device.h. (Two further kernel structures of round 1 -- resident waves
 // pulling tiles from per-XCD queues, and 768-thread workgroups with the hot BVH tiles staged in LDS -- were measured

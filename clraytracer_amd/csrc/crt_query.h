@@ -1,5 +1,5 @@
-// crt_query.h -- the queries on device buffers (crt_trace_rays, crt_trace_ao, crt_frame_ao): the shape their kernels share, written once.
-// Included by crt_rays.h and crt_ao.h; the host half is crt_query_host.h. The traversal is shared text too: closest_hit of crt_device.h.
+// crt_query.h -- the queries on device buffers (crt_trace_rays, crt_trace_ao, crt_frame_ao, crt_shade_rays): the shape their kernels share, written once.
+// Included by crt_rays.h, crt_ao.h and crt_shade.h; the host half is crt_query_host.h. The traversal is shared text too: closest_hit of crt_device.h.
 #pragma once
 #include "crt_device.h"
 

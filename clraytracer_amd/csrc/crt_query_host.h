@@ -1,5 +1,5 @@
 // crt_query_host.h -- the queries on device buffers, host half: the context (State::rayQuery), the one launch sequence and the one statistics
-// reader of every family, and crt_trace_rays. crt_trace_ao / crt_frame_ao: crt_ao_host.h. The kernels' half: crt_query.h.
+// reader of every family, and crt_trace_rays. crt_trace_ao / crt_frame_ao: crt_ao_host.h; crt_shade_rays: crt_shade_host.h. The kernels' half: crt_query.h.
 // Part of the one translation unit crt_shim.hip (included there behind crt_frame.h and in front of crt_ao_host.h); everything here has
 // internal linkage.
 #pragma once
@@ -15,7 +15,7 @@ static int ensure_ray_query_context()
     if (q.ready) return CRT_OK;
     if (!q.tables.stream) RCCHK(q.tables.stream.create(hipStreamNonBlocking));
     if (!q.tables.instBlock) RCCHK(create_slot_tables(q.tables));
-    if (!q.ctl) RCCHK(q.ctl.alloc(4));
+    if (!q.ctl) RCCHK(q.ctl.alloc(6));
     if (!q.raysDone) RCCHK(q.raysDone.create(hipEventDisableTiming));
     q.ready = true;
     return CRT_OK;
@@ -68,16 +68,19 @@ static int end_query(hipStream_t stream)
 // Ordering: the caller's stream waits (hipStreamWaitEvent) for the query before -- queries share the context -- and for the context's
 // instance tables, which are refreshed on the context's own stream behind that same query (it may still read the old tables). Frames
 // in flight are neither waited for nor touched.
-// kernels: the family's four instantiations under the box rule asked for (inclusive: those of crt_inclusive.hip), [2 * x + TLAS], launched as
+// kernels: the family's instantiations under the box rule asked for (inclusive: those of crt_inclusive.hip), [2 * x + TLAS] -- four, x a
+// bool; the shaded queries have six, x = 0 .. 2, and no inclusive form (QueryFamily::residentPerCU holds either) --, launched as
 // kernel(S, A, extra...); A: the form's own arguments, its `q` and
 // `chunks` are filled here; before(stream) queues what the kernel must wait for, after(stream) what belongs to the query behind it.
-template <class Kernel, class Args, class Before, class After, class... Extra>
-static int launch_query(QueryFamily& fam, Kernel* const (&kernels)[4], bool inclusive, bool x, uint32_t numInstances, uint64_t chunks, hipStream_t stream,
+template <class Kernel, size_t N, class Args, class Before, class After, class... Extra>
+static int launch_query(QueryFamily& fam, Kernel* const (&kernels)[N], bool inclusive, int x, uint32_t numInstances, uint64_t chunks, hipStream_t stream,
                         Before&& before, After&& after, Args A, const Extra&... extra)
 {
     CrtDevScene S;
     RCCHK(query_scene(numInstances, S));
-    const int which = 2 * (int)x + (int)use_tlas(S);
+    static_assert(N == 4 || N == 6, "a family's instantiations");
+    const int which = 2 * x + (int)use_tlas(S);
+    if (which < 0 || which >= (int)N || 4 * (int)inclusive + which >= 8) return CRT_E_BAD_ARGUMENT;
     int& resident = fam.residentPerCU[4 * (int)inclusive + which];
     if (resident == 0) {         // as the runtime computes it for this device, asked once per instantiation
         int n = 0;

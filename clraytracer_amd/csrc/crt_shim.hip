@@ -3,15 +3,15 @@
 // Replaces the OpenCL side of the reference's Renderer.cpp / ResourceManager.cpp: device pools,
 // uploads, the per-frame RayGen -> Trace -> PostProcess launch (Renderer.cpp:305-375). Uploads
 // arrive in the reference's struct layouts and are re-laid-out on the device (crt_device.h).
-// One translation unit (and crt_rays.hip, the ray-query kernel, crt_ao.hip, the ambient-occlusion kernels, crt_inclusive.hip, both under the inclusive box test, and crt_recip.hip, the reciprocal sweep, beside it); the parts (round 5 split what used to be one 2,000-line file):
+// One translation unit (and crt_rays.hip, the ray-query kernel, crt_ao.hip, the ambient-occlusion kernels, crt_inclusive.hip, both under the inclusive box test, crt_recip.hip, the reciprocal sweep, and crt_shade.hip, the shaded ray queries, beside it); the parts (round 5 split what used to be one 2,000-line file):
 //   kernels     crt_device.h (traversal + shading), crt_kernels.h (launches), crt_refill.h (opt-in in-wave compaction forms), crt_ldstop.h (opt-in: tree tops staged in LDS),
 //               crt_relayout.h (upload-time layouts), crt_bvh_build.h (device BuildBVH); crt_rays.h declares the ray-query kernel of the second unit, crt_rays.hip,
-//               crt_ao.h the ambient-occlusion kernels of the third, crt_ao.hip, crt_inclusive.h both under the inclusive box test, the fourth, crt_inclusive.hip; crt_query.h: the steps those units' kernels share
+//               crt_ao.h the ambient-occlusion kernels of the third, crt_ao.hip, crt_inclusive.h both under the inclusive box test, the fourth, crt_inclusive.hip, crt_shade.h the shaded ray queries' kernel of the sixth, crt_shade.hip; crt_query.h: the steps those units' kernels share
 //   host state  crt_own.h (the owners of device / pinned buffers, events and streams), crt_state.h (State / FrameSlot, helpers), crt_instances.h (instance tables, cull bounds, instance tree)
 //   entry impl  crt_upload.h (init, uploads, read-backs), crt_bvh_driver.h (crt_build_bvh), crt_frame.h (crt_render and what a frame
-//               needs), crt_query_host.h (the queries on device buffers: context, launch, statistics; crt_trace_rays), crt_ao_host.h (crt_trace_ao, crt_frame_ao), crt_multidev.h (several devices behind the same calls)
-// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared crt_shim.hip crt_rays.hip crt_ao.hip crt_inclusive.hip crt_recip.hip (the Makefile's rule; a library of this unit
-// alone links but does not load: crt_query_host.h, crt_ao_host.h and crt_frame.h refer to the kernels the other four define)
+//               needs), crt_query_host.h (the queries on device buffers: context, launch, statistics; crt_trace_rays), crt_ao_host.h (crt_trace_ao, crt_frame_ao), crt_shade_host.h (crt_shade_rays), crt_multidev.h (several devices behind the same calls)
+// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared crt_shim.hip crt_rays.hip crt_ao.hip crt_inclusive.hip crt_recip.hip crt_shade.hip (the Makefile's rule; a library of this unit
+// alone links but does not load: crt_query_host.h, crt_ao_host.h, crt_shade_host.h and crt_frame.h refer to the kernels the other five define)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <cmath>
@@ -27,6 +27,7 @@
 #include "crt_ao.h"
 #include "crt_inclusive.h"
 #include "crt_recip.h"
+#include "crt_shade.h"
 #include "crt_relayout.h"
 #include "crt_bvh_build.h"
 #include <vector>
@@ -45,6 +46,7 @@
 #include "crt_frame.h"
 #include "crt_query_host.h"
 #include "crt_ao_host.h"
+#include "crt_shade_host.h"
 
 #include "crt_multidev.h"
 
@@ -333,6 +335,14 @@ int crt_frame_ao(const CrtAoParams* params, void* stream)
 int crt_read_ao(float* dst, size_t floats) { ON_PRIMARY(crt1_read_ao(dst, floats)); }
 void* crt_ao_device_ptr(void) { if (M.n == 0) return nullptr; Use u(0); return crt1_ao_device_ptr(); }
 int crt_debug_ao_stats(uint64_t out[3]) { ON_PRIMARY(crt1_debug_ao_stats(out)); }
+// shaded rays on the device: one GPU's pointers, refused in a session of several like crt_trace_rays
+int crt_shade_rays(const CrtRayBatch* rays, const CrtShadeParams* params, uint32_t numInstances, float* radiance, CrtSurfaceHit* surface, void* stream)
+{
+    NEED_SESSION();
+    if (M.n > 1) return CRT_E_UNSUPPORTED;
+    ON_PRIMARY(crt1_shade_rays(rays, params, numInstances, radiance, surface, static_cast<hipStream_t>(stream)));
+}
+int crt_debug_shade_stats(uint64_t out[3]) { ON_PRIMARY(crt1_debug_shade_stats(out)); }
 int crt_read_output(float* dst, size_t floats) { NEED_SESSION(); RCCHK(drain_secondaries()); ON_PRIMARY(crt1_read_output(dst, floats)); }
 int crt_read_output_rows(float* dst, int row0, int rows) { NEED_SESSION(); RCCHK(drain_secondaries()); ON_PRIMARY(crt1_read_output_rows(dst, row0, rows)); }
 int crt_read_output_rgba8(uint8_t* dst, size_t bytes) { NEED_SESSION(); RCCHK(drain_secondaries()); ON_PRIMARY(crt1_read_output_rgba8(dst, bytes)); }

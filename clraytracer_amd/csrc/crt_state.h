@@ -71,12 +71,12 @@ struct FrameSlot : SlotTables {
     bool frameIs8 = false;
 };
 
-// One family of queries on the context below (crt_trace_rays; crt_trace_ao / crt_frame_ao): its pair of control words, what its last launch
-// was, and how many workgroups of each of its kernel's instantiations -- four per box rule -- a CU holds. Families share everything else of the context.
+// One family of queries on the context below (crt_trace_rays; crt_trace_ao / crt_frame_ao; crt_shade_rays): its pair of control words, what its last launch
+// was, and how many workgroups of each of its kernel's instantiations -- four per box rule, or the shaded queries' six -- a CU holds. Families share everything else of the context.
 struct QueryFamily {
     uint32_t ctl0;                             // its words in QueryContext::ctl: [ctl0] chunk counter, [ctl0 + 1] chunks traced without the cull (CrtQueryArgs::ctl)
     unsigned long long chunks = 0, grid = 0;   // of the family's last query (crt_debug_rays_stats, crt_debug_ao_stats)
-    int residentPerCU[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };   // hipOccupancyMaxActiveBlocksPerMultiprocessor of the kernel<X, TLAS>, [4 * inclusive + 2 * X + TLAS]; 0 = not asked yet
+    int residentPerCU[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };   // hipOccupancyMaxActiveBlocksPerMultiprocessor of the kernel<X, TLAS>, [4 * inclusive + 2 * X + TLAS] (crt_shade_kernel<WHAT, TLAS>: [2 * (WHAT - 1) + TLAS]); 0 = not asked yet
 };
 
 // The context of the queries on device buffers (crt_query_host.h): queries never touch a frame slot, so they neither wait for the frames
@@ -87,10 +87,10 @@ struct QueryFamily {
 struct QueryContext {
     SlotTables tables;
     bool ready = false;                        // allocated (by the first query)
-    DevBuf<uint32_t> ctl;                      // device: four words, a pair per family
+    DevBuf<uint32_t> ctl;                      // device: six words, a pair per family
     Event raysDone; bool inFlight = false;     // recorded behind the last query on the caller's stream; inFlight: not yet known to be over
     bool refreshPending = false;               // a table refresh was queued on tables.stream and no raysDone covers it yet (a query that failed behind it): quiesce waits for tables.staged
-    QueryFamily rays = { 0 }, ao = { 2 };      // crt_rays_kernel<ANYHIT, TLAS>, crt_ao_kernel<SOURCE, TLAS>
+    QueryFamily rays = { 0 }, ao = { 2 }, shade = { 4 };      // crt_rays_kernel<ANYHIT, TLAS>, crt_ao_kernel<SOURCE, TLAS>, crt_shade_kernel<WHAT, TLAS>
 };
 
 // Whatever a State holds is released when it is deleted, with its device current: destroy_group (crt_multidev.h) is the only place.
@@ -156,7 +156,7 @@ struct State {
     DevBuf<float4> topPairs; DevBuf<uint32_t> topRootRefs;   // the tree-top table (CRT_TOP_PAIRS records) and every mesh's entry into it, rebuilt with the BVH layout
     char lastKernel[128] = { 0 };              // crt_debug_last_kernel: the Trace launch(es) of the most recently submitted frame
     DevBuf<char> queryBuf;                     // scratch of crt_query_hits and crt_read_output_rgba8
-    QueryContext rayQuery;                     // crt_trace_rays, crt_trace_ao, crt_frame_ao
+    QueryContext rayQuery;                     // crt_trace_rays, crt_trace_ao, crt_frame_ao, crt_shade_rays
     int raysGridCap = 0;                       // CRT_RAYS_GRID=n: at most n workgroups per query (tests: few waves walking many chunks); 0 = as many as are resident
     DevBuf<char> buildBuf;                                    // crt_build_bvh scratch
     std::vector<CrtBuildCtl> buildReplay; unsigned long long buildReplayKey = 0;   // CRT_DEBUG_BVH_REPLAY (crt_bvh_driver.h): the level records of the last build

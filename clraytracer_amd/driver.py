@@ -32,6 +32,29 @@ class RayHits:
         return self.records.cpu().numpy().view(_lib.RAYHIT_DTYPE).reshape(-1)
 
 
+class SurfaceHits:
+    """The records of Session.shade_rays(surface=True): `records` is one (n, 12) int32 tensor on the device holding n CrtSurfaceHit; normal
+    (n, 3), t, u, v, tex_u, tex_v (float32) and instance, tri, albedo, material (int32) are views of its columns. A miss: t = 99999,
+    instance = -1, the rest 0."""
+
+    def __init__(self, records):
+        import torch
+        f = records.view(torch.float32)
+        self.records = records
+        self.normal, self.t = f[:, 0:3], f[:, 3]
+        self.instance, self.tri = records[:, 4], records[:, 5]
+        self.u, self.v = f[:, 6], f[:, 7]
+        self.albedo, self.material = records[:, 8], records[:, 9]
+        self.tex_u, self.tex_v = f[:, 10], f[:, 11]
+
+    def __len__(self):
+        return self.records.shape[0]
+
+    def numpy(self):
+        """The records on the host as _lib.SURFACE_HIT_DTYPE (synchronises with the stream that produced them)."""
+        return self.records.cpu().numpy().view(_lib.SURFACE_HIT_DTYPE).reshape(-1)
+
+
 class Session:
     def __init__(self, width, height, device=0, host_only=False, devices=None):
         """device: one HIP ordinal; devices: a list of ordinals -> several GPUs in this process (Renderer::InitializeDevices;
@@ -321,6 +344,34 @@ class Session:
         """(64-ray chunks, chunks traced without the instance cull, workgroups launched) of the last trace_rays, after waiting for it."""
         out = (C.c_uint64 * 3)()
         _lib.check(self.hip.crt_debug_rays_stats(out), "crt_debug_rays_stats")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    # ---- shaded ray queries on device tensors (Renderer::ShadeRays -> crt_shade_rays) ----
+    def shade_rays(self, origins, dirs, tmax=None, sun_angle=None, radiance=True, surface=False):
+        """What a frame computes for a pixel, for n world-space rays given as trace_rays takes them (include/crt_api.h: crt_shade_rays): the
+        radiance of both bounces as an (n, 4) float32 tensor (rgb, 1) and / or the first hit's surface record (a SurfaceHits: normal, t, ids,
+        barycentrics, albedo, material, uv). tmax bounds the given ray only; sun_angle=None: the scene's. Returns the tensor, the records,
+        or (tensor, records) for radiance=True and surface=True. Enqueued on torch.cuda.current_stream() without synchronising."""
+        import torch
+        if not radiance and not surface:
+            raise ValueError("radiance and surface are both False: nothing to compute")
+        n, (so, sd, _) = self._ray_arrays("rays", origins=(origins, 3), dirs=(dirs, 3), tmax=(tmax, 1))
+        dev = torch.device("cuda", self.device)
+        batch = _lib.CrtRayBatch(origins.data_ptr(), dirs.data_ptr(), tmax.data_ptr() if tmax is not None else None, so, sd, n)
+        params = _lib.CrtShadeParams(float(self.scene.sun_angle if sun_angle is None else sun_angle), 0)
+        rad = torch.empty((n, 4), dtype=torch.float32, device=dev) if radiance else None
+        rec = torch.empty((n, 12), dtype=torch.int32, device=dev) if surface else None
+        if not self.h.crth_shade_rays(C.byref(batch), C.byref(params), rad.data_ptr() if radiance else None, rec.data_ptr() if surface else None,
+                                      torch.cuda.current_stream(dev).cuda_stream):
+            self._raise_and_clear("Renderer::ShadeRays")
+        if radiance and surface:
+            return rad, SurfaceHits(rec)
+        return rad if radiance else SurfaceHits(rec)
+
+    def shade_stats(self):
+        """(64-ray chunks, chunks traced without the instance cull, workgroups launched) of the last shade_rays, after waiting for it."""
+        out = (C.c_uint64 * 3)()
+        _lib.check(self.hip.crt_debug_shade_stats(out), "crt_debug_shade_stats")
         return int(out[0]), int(out[1]), int(out[2])
 
     # ---- ambient occlusion (Renderer::TraceAmbientOcclusion / ComputeAmbientOcclusion -> crt_trace_ao / crt_frame_ao) ----

@@ -230,6 +230,12 @@ bool Renderer::TraceRays(const CrtRayBatch& rays, int mode, void* out, void* str
     return check(crt_trace_rays(&rays, g_NumMeshInstances, mode, out, stream), "crt_trace_rays");
 }
 
+bool Renderer::ShadeRays(const CrtRayBatch& rays, const CrtShadeParams& params, float* radiance, CrtSurfaceHit* surface, void* stream)
+{
+    if (!deviceReady) { lastError = CRT_E_NOT_INITIALIZED; return false; }
+    return check(crt_shade_rays(&rays, &params, g_NumMeshInstances, radiance, surface, stream), "crt_shade_rays");
+}
+
 bool Renderer::TraceAmbientOcclusion(const CrtAoPoints& points, const CrtAoParams& params, float* out, void* stream)
 {
     if (!deviceReady) { lastError = CRT_E_NOT_INITIALIZED; return false; }

@@ -49,6 +49,9 @@ namespace Renderer
     // against the registered instances (as last uploaded), enqueued on `stream` (a hipStream_t; null: HIP's null stream) without waiting; false: LastError().
     // mode | CRT_RAYS_INCLUSIVE: the inclusive box test, for rays that start on a surface (crt_api.h)
     bool TraceRays(const CrtRayBatch& rays, int mode, void* out, void* stream = nullptr);
+    // extension: what a frame computes for a pixel, for a batch of rays on the device (crt_api.h: crt_shade_rays): `radiance` (float4 per ray) and / or
+    // `surface` (the first hit's CrtSurfaceHit per ray) on the device, either may be null; enqueued on `stream` without waiting; false: LastError().
+    bool ShadeRays(const CrtRayBatch& rays, const CrtShadeParams& params, float* radiance, CrtSurfaceHit* surface, void* stream = nullptr);
     // extension: ambient occlusion (crt_api.h: crt_trace_ao, crt_frame_ao). TraceAmbientOcclusion: n floats into `out` for points + normals on the device,
     // against the registered instances, enqueued on `stream` without waiting. ComputeAmbientOcclusion: the same for the pixels of the last frame rendered
     // with SetGBuffer(true), into that frame's AO plane; MapAmbientOcclusion: a host copy of it (width*height floats, valid until the next call; null

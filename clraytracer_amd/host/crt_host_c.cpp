@@ -121,6 +121,12 @@ int crth_trace_rays(const CrtRayBatch* rays, int mode, void* out, void* stream)
     if (!rays) { hostOnlyError = CRT_E_BAD_ARGUMENT; return 0; }      // (reported through crth_last_error like the host-only refusals)
     return Renderer::TraceRays(*rays, mode, out, stream) ? 1 : 0;
 }
+int crth_shade_rays(const CrtRayBatch* rays, const CrtShadeParams* params, float* radiance, CrtSurfaceHit* surface, void* stream)
+{
+    if (hostOnly) { hostOnlyError = CRT_E_NOT_INITIALIZED; return 0; }
+    if (!rays || !params) { hostOnlyError = CRT_E_BAD_ARGUMENT; return 0; }
+    return Renderer::ShadeRays(*rays, *params, radiance, surface, stream) ? 1 : 0;
+}
 int crth_trace_ao(const CrtAoPoints* points, const CrtAoParams* params, float* out, void* stream)
 {
     if (hostOnly) { hostOnlyError = CRT_E_NOT_INITIALIZED; return 0; }

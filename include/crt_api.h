@@ -284,6 +284,44 @@ int crt_frame_ao(const CrtAoParams* params, void* stream);
 int crt_read_ao(float* dst, size_t floats);                   /* width*height */
 void* crt_ao_device_ptr(void);
 
+/* Shaded ray queries on device buffers (no reference counterpart: upstream shades the camera's rays only): what a frame computes for a
+ * pixel, for any ray that is already on the device -- a fisheye or panoramic camera, a cube-map probe, a stereo pair, a range sensor that
+ * wants intensity, a light-map texel, the next bounce of a path tracer written by the caller. Against the first `numInstances` instances.
+ *   rays      CrtRayBatch as crt_trace_rays takes it. Ray k is (o, d) of the batch; d is not normalised (hazard H6).
+ *   params    CrtShadeParams {sunAngle, flags = 0}: lightDir = (0, (float)sin((double)sunAngle), (float)cos((double)sunAngle)), computed
+ *             on the host as a frame's is from CrtTraceArgs::sunAngle.
+ *   radiance  device-accessible float4[n], or NULL: radiance[k] = (result, 1.0f).
+ *   surface   device-accessible CrtSurfaceHit[n] (48 B each, crt_types.h), or NULL. Not both NULL; with radiance == NULL only the first
+ *             traversal runs.
+ * Definition, one for every ray, float32 without contraction: kernel_main.cl:187-272 exactly as a frame without flags runs it for a pixel
+ * whose ray is (o, d) -- energy (1, 1, 1), atmosphericLight (0.255, 0.25, 0.27), two bounces: the instance loop + IntersectBVH
+ * (kernel_main.cl:189-217), the sky for a ray that found nothing or something beyond InfMinusOne (kernel_main.cl:219-223), else the
+ * material (kernel_main.cl:229), the interpolated normal and uv (kernel_main.cl:232-240), the albedo texel times the material's colour
+ * (kernel_main.cl:242-245), the reflected ray 0.01 off the surface (kernel_main.cl:252-254), ambient, diffuse and specular terms
+ * (kernel_main.cl:260-268) and, after the first bounce, lightDir = the bounce ray's direction and atmosphericLight * 0.4
+ * (kernel_main.cl:269-271). None of the extensions (shadow rays, refraction, supersampling) and none of the stages behind Trace (the RGBA8
+ * target, PostProcess, FXAA): they belong to pixels.
+ * The bound: B = the bound of crt_trace_rays, !(tmax[k] >= 99999.0f) ? tmax[k] : 99999.0f (no tmax array: 99999.0f), for the given ray
+ * only -- besthit.distance starts at B; the bounce ray is unbounded. A ray without a hit inside the bound (a NaN bound: every ray) is a
+ * miss: it ends in the sky as kernel_main.cl:219-223 does and gets the miss record.
+ * The surface record describes what the given ray found. Its first 36 bytes are CrtGBufferPixel -- exactly the three G-buffer planes'
+ * values for a pixel with that ray: hit: record.normal, t, instance, triIndex, u, v, albedo = 0xFF000000 | b << 16 | g << 8 | r of
+ * record.color. material = min(materialStart + triangle.materialIndex, 255), the index the material was read at; texU, texV = the
+ * interpolated uv before SampleTexture's fract. A miss: normal 0, t = 99999, instance -1, everything else 0. A hit beyond InfMinusOne
+ * (t > 99998, shaded as sky) keeps instance, triIndex, u, v and t and has the normal, albedo, material and uv of a miss.
+ * What is promised: for the rays of a frame -- origins = cameraPos with stride 0, dirs = what crt_read_rays returns for that frame --
+ * radiance is, bit for bit, crt_read_output of the frame rendered with flags = 0 and surface the three planes of crt_read_gbuffer of the
+ * CRT_RENDER_GBUFFER frame; for any rays, the CPU oracle's trace of them.
+ * Everything else is crt_trace_rays, word for word: the call ENQUEUES AND RETURNS on the caller's stream, in the ray queries' context --
+ * one query at a time, of any kind; instance tables refreshed behind the query before; a persistent grid (CRT_RAYS_GRID) with an
+ * overflow area per workgroup; the cull decided per 64-ray chunk on the given origins (a chunk without it keeps its scene for its bounce
+ * rays); frames in flight neither waited for nor delayed; whatever waits for a ray query waits for this one; work counters,
+ * crt_get_counters and noCullFrames untouched; n == 0: CRT_OK. While a query runs, radiance[k] also holds ray k's unfinished path.
+ * Errors, all before anything is enqueued: CRT_E_NOT_INITIALIZED; CRT_E_BAD_ARGUMENT (rays, params, origins or dirs NULL; both outputs
+ * NULL; a stride of 1 or 2; a sunAngle that is not finite; flags other than 0; numInstances > 401; an invalid scene); CRT_E_OUT_OF_RANGE
+ * (n > 2^30); CRT_E_UNSUPPORTED (a session of several devices). */
+int crt_shade_rays(const CrtRayBatch* rays, const CrtShadeParams* params, uint32_t numInstances, float* radiance, CrtSurfaceHit* surface, void* stream);
+
 /* Output: the HDR float4 frame (the reference writes a CL-GL RGBA8 texture, Renderer.cpp:63,192). */
 int crt_read_output(float* dstRGBA, size_t floats);           /* full frame, width*height*4 floats */
 int crt_read_output_rows(float* dstRGBA, int row0, int rows); /* rows [row0,row0+rows) */

@@ -58,6 +58,10 @@ int crt_debug_rays_stats(uint64_t out[3]);
  * rows this rank owns), chunks traced without the instance cull (a tracing item's ray origin beyond the cull's proven range, or NaN),
  * workgroups launched } -- the same persistent grid as crt_debug_rays_stats describes, with its own counters. Zeros before the first. */
 int crt_debug_ao_stats(uint64_t out[3]);
+/* Diagnostic: the last crt_shade_rays launch, after waiting for it: out = { 64-ray chunks, chunks traced without the instance cull (an
+ * origin beyond the cull's proven range, or NaN), workgroups launched } -- the same persistent grid as crt_debug_rays_stats describes,
+ * with its own counters. Zeros before the first. */
+int crt_debug_shade_stats(uint64_t out[3]);
 /* Diagnostic: device buffers, pinned host buffers, events and streams the library holds in this process right now (every one is
  * counted when it is created and when it is released). Works without a session: 0 before the first crt_init and again after
  * crt_shutdown -- what the tests use to see that a session leaves nothing behind (tests/test_gpu_resources.py). */

@@ -73,6 +73,9 @@ const float* crth_map_output(void);                          /* Renderer::MapOut
 int crth_trace_rays(const CrtRayBatch* rays, int mode, void* out, void* stream);
 /* Renderer::TraceAmbientOcclusion / ComputeAmbientOcclusion / MapAmbientOcclusion: crt_trace_ao, crt_frame_ao and crt_read_ao (crt_api.h).
  * `out` (n floats) and the point arrays on the device, `stream` a hipStream_t or NULL. 1 (a pointer), or 0 (NULL) on failure (crth_last_error). */
+/* Renderer::ShadeRays: crt_shade_rays (crt_api.h) against the registered instances; `radiance` (float4[n]) or `surface` (CrtSurfaceHit[n]) may be
+ * NULL, not both; they and the batch's arrays on the device, `stream` a hipStream_t or NULL. 1, or 0 on failure (crth_last_error). */
+int crth_shade_rays(const CrtRayBatch* rays, const CrtShadeParams* params, float* radiance, CrtSurfaceHit* surface, void* stream);
 int crth_trace_ao(const CrtAoPoints* points, const CrtAoParams* params, float* out, void* stream);
 int crth_compute_ao(const CrtAoParams* params, void* stream);
 const float* crth_map_ao(void);                              /* width*height floats of the last crth_compute_ao, valid until the next call */

@@ -124,6 +124,24 @@ typedef struct CrtGBufferPixel {
     uint32_t albedo;
 } CrtGBufferPixel;
 
+/* One ray's first-hit surface record of crt_shade_rays (definition in include/crt_api.h): three 16-byte rows; the first 36 bytes are
+ * CrtGBufferPixel, field for field. miss: normal 0, t = 99999, instance -1, everything else 0. */
+typedef struct CrtSurfaceHit {
+    float normal[3];
+    float t;
+    int32_t instance;                 /* -1: miss */
+    uint32_t triIndex;
+    float u, v;
+    uint32_t albedo;                  /* 0xFF000000 | b << 16 | g << 8 | r of record.color (kernel_main.cl:245) */
+    uint32_t material;                /* min(materialStart + triangle.materialIndex, 255): the index the shading reads the material at (kernel_main.cl:229) */
+    float texU, texV;                 /* the interpolated uv of kernel_main.cl:238-240, before SampleTexture's fract */
+} CrtSurfaceHit;
+
+typedef struct CrtShadeParams {
+    float sunAngle;                   /* finite; the sun of CrtTraceArgs::sunAngle */
+    uint32_t flags;                   /* 0 */
+} CrtShadeParams;
+
 /* Compile-time limits of the reference. */
 enum {
     CRT_MAX_INSTANCES   = 401,        /* Renderer.hpp:16 */
@@ -149,6 +167,8 @@ static_assert(sizeof(CrtTraceArgs) == 24, "TraceArgs must be 24 B");
 static_assert(sizeof(CrtGBufferPixel) == 36, "GBufferPixel must be 36 B (16 + 16 + 4, the three planes)");
 static_assert(sizeof(CrtRayHit) == 20 && sizeof(CrtRayBatch) == 40, "RayHit must be 20 B, RayBatch 40 B");
 static_assert(sizeof(CrtAoParams) == 28 && sizeof(CrtAoPoints) == 32, "AoParams must be 28 B, AoPoints 32 B");
+static_assert(sizeof(CrtSurfaceHit) == 48, "SurfaceHit must be 48 B (three 16-B rows)");
+static_assert(sizeof(CrtShadeParams) == 8, "ShadeParams must be 8 B");
 #endif
 #endif
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Compile the translation units of libcrt_hip.so (crt_shim.hip, crt_rays.hip, crt_ao.hip, crt_inclusive.hip, crt_recip.hip) for gfx950 with -Rpass-analysis=kernel-resource-usage and print one
+"""Compile the translation units of libcrt_hip.so (crt_shim.hip, crt_rays.hip, crt_ao.hip, crt_inclusive.hip, crt_recip.hip, crt_shade.hip) for gfx950 with -Rpass-analysis=kernel-resource-usage and print one
 line per kernel: VGPRs, AGPRs, scratch bytes per lane, occupancy, LDS bytes. Runs without a GPU (hipcc cross-compiles).
 
     python tools/kernel_resources.py [filter-substring] [-D...]
@@ -14,7 +14,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
-SOURCES = ("crt_shim.hip", "crt_rays.hip", "crt_ao.hip", "crt_inclusive.hip", "crt_recip.hip")     # the Makefile's units of libcrt_hip.so, in link order
+SOURCES = ("crt_shim.hip", "crt_rays.hip", "crt_ao.hip", "crt_inclusive.hip", "crt_recip.hip", "crt_shade.hip")     # the Makefile's units of libcrt_hip.so, in link order
 
 
 def kernel_resource_rows(defs=(), source=SOURCES[0]):

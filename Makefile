@@ -11,6 +11,12 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fno-slp-vect
 CXXFLAGS = -O2 -std=c++17 -ffp-contract=off -fno-fast-math -fPIC -Wall -Wextra -pthread
 
 HIP_SO = clraytracer_amd/csrc/libcrt_hip.so
+# The translation units of libcrt_hip.so in link order, crt_shim.hip (the C-ABI and every frame kernel) first; each unit's first lines say what it holds.
+# The list is written here only: tools/kernel_resources.py reads it and HIPFLAGS from this file, tools/ab_build.sh and tools/ab_define.sh build their
+# variants through the $(HIP_SO) rule (HIP_SO=<their output> EXTRA_HIPFLAGS="<the variant's flags>"), tests/test_kernel_resources.py checks the rest.
+HIP_UNITS = crt_shim.hip crt_rays.hip crt_ao.hip crt_inclusive.hip crt_recip.hip crt_shade.hip
+HIP_SRC = $(addprefix clraytracer_amd/csrc/,$(HIP_UNITS))
+EXTRA_HIPFLAGS ?=
 HOST_SO = clraytracer_amd/host/libcrt_host.so
 HOST_SRC = $(addprefix clraytracer_amd/host/,AssetManager.cpp MeshCache.cpp JpegDecode.cpp BVH.cpp CPURayTrace.cpp Renderer.cpp ResourceManager.cpp crt_host_c.cpp ShmBarrier.cpp)
 HOST_HDR = $(wildcard clraytracer_amd/host/*.hpp) $(wildcard include/*.h)
@@ -36,11 +42,9 @@ tools/ubench/cumask: tools/ubench/cumask.hip
 $(EXAMPLE): examples/headless_main.cpp $(HOST_SO)
 	$(CXX) $(CXXFLAGS) -o $@ examples/headless_main.cpp -Lclraytracer_amd/host -lcrt_host -Lclraytracer_amd/csrc -lcrt_hip -Wl,-rpath,'$$ORIGIN/../clraytracer_amd/host' -Wl,-rpath,'$$ORIGIN/../clraytracer_amd/csrc'
 
-# six translation units: crt_shim.hip (the C-ABI and every frame kernel), crt_rays.hip (the kernel of crt_trace_rays), crt_ao.hip (the
-# kernels of crt_trace_ao / crt_frame_ao; its direction table crt_ao_table.h is written by tools/make_ao_table.py and committed),
-# crt_inclusive.hip (the kernels of the three queries under the inclusive box test), crt_recip.hip (the kernel of crt_debug_recip_sweep) and crt_shade.hip (the kernel of crt_shade_rays)
-$(HIP_SO): $(wildcard clraytracer_amd/csrc/*.h) clraytracer_amd/csrc/crt_shim.hip clraytracer_amd/csrc/crt_rays.hip clraytracer_amd/csrc/crt_ao.hip clraytracer_amd/csrc/crt_inclusive.hip clraytracer_amd/csrc/crt_recip.hip clraytracer_amd/csrc/crt_shade.hip include/crt_api.h include/crt_debug.h include/crt_types.h
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ clraytracer_amd/csrc/crt_shim.hip clraytracer_amd/csrc/crt_rays.hip clraytracer_amd/csrc/crt_ao.hip clraytracer_amd/csrc/crt_inclusive.hip clraytracer_amd/csrc/crt_recip.hip clraytracer_amd/csrc/crt_shade.hip
+# every unit of HIP_UNITS in one compiler call (crt_ao.hip's direction table crt_ao_table.h is written by tools/make_ao_table.py and committed)
+$(HIP_SO): $(wildcard clraytracer_amd/csrc/*.h) $(HIP_SRC) include/crt_api.h include/crt_debug.h include/crt_types.h
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $(HIP_SRC)
 
 $(HOST_SO): $(HOST_SRC) $(HOST_HDR) $(HIP_SO)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRC) -Lclraytracer_amd/csrc -lcrt_hip -lrt -Wl,-rpath,'$$ORIGIN/../csrc'

@@ -1,5 +1,5 @@
 // crt_shade.h -- shaded ray queries on device buffers (crt_shade_rays): the kernel's arguments, its declaration and its text.
-// The kernel is compiled in a translation unit of its own (crt_shade.hip, the sixth of libcrt_hip.so) and launched from crt_shade_host.h: the device
+// The kernel is compiled in a translation unit of its own (crt_shade.hip, one of the Makefile's HIP_UNITS) and launched from crt_shade_host.h: the device
 // code of the other units is the same with and without it. It is the chunk loop of crt_rays_body (crt_query.h: the persistent grid, the claim,
 // the bound, the cull decision, ctl) around the bounce loop of trace_body (crt_kernels.h) -- the path starts from the batch's (o, d)
 // instead of camera_path, everything behind the closest hit is shade_bounce (crt_device.h), the one text every frame shades with.

@@ -3,15 +3,15 @@
 // Replaces the OpenCL side of the reference's Renderer.cpp / ResourceManager.cpp: device pools,
 // uploads, the per-frame RayGen -> Trace -> PostProcess launch (Renderer.cpp:305-375). Uploads
 // arrive in the reference's struct layouts and are re-laid-out on the device (crt_device.h).
-// One translation unit (and crt_rays.hip, the ray-query kernel, crt_ao.hip, the ambient-occlusion kernels, crt_inclusive.hip, both under the inclusive box test, crt_recip.hip, the reciprocal sweep, and crt_shade.hip, the shaded ray queries, beside it); the parts (round 5 split what used to be one 2,000-line file):
+// The first translation unit of libcrt_hip.so; the list is the Makefile's HIP_UNITS (beside this one crt_rays.hip, crt_ao.hip, crt_inclusive.hip, crt_recip.hip and crt_shade.hip: each says in its first lines which kernels it holds). The parts of this unit (round 5 split what used to be one 2,000-line file):
 //   kernels     crt_device.h (traversal + shading), crt_kernels.h (launches), crt_refill.h (opt-in in-wave compaction forms), crt_ldstop.h (opt-in: tree tops staged in LDS),
-//               crt_relayout.h (upload-time layouts), crt_bvh_build.h (device BuildBVH); crt_rays.h declares the ray-query kernel of the second unit, crt_rays.hip,
-//               crt_ao.h the ambient-occlusion kernels of the third, crt_ao.hip, crt_inclusive.h both under the inclusive box test, the fourth, crt_inclusive.hip, crt_shade.h the shaded ray queries' kernel of the sixth, crt_shade.hip; crt_query.h: the steps those units' kernels share
+//               crt_relayout.h (upload-time layouts), crt_bvh_build.h (device BuildBVH); the kernels of the other units are declared in
+//               crt_rays.h (ray queries), crt_ao.h (ambient occlusion), crt_inclusive.h (both under the inclusive box test), crt_recip.h (the reciprocal sweep) and crt_shade.h (shaded ray queries); crt_query.h: the steps those units' kernels share
 //   host state  crt_own.h (the owners of device / pinned buffers, events and streams), crt_state.h (State / FrameSlot, helpers), crt_instances.h (instance tables, cull bounds, instance tree)
 //   entry impl  crt_upload.h (init, uploads, read-backs), crt_bvh_driver.h (crt_build_bvh), crt_frame.h (crt_render and what a frame
 //               needs), crt_query_host.h (the queries on device buffers: context, launch, statistics; crt_trace_rays), crt_ao_host.h (crt_trace_ao, crt_frame_ao), crt_shade_host.h (crt_shade_rays), crt_multidev.h (several devices behind the same calls)
-// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared crt_shim.hip crt_rays.hip crt_ao.hip crt_inclusive.hip crt_recip.hip crt_shade.hip (the Makefile's rule; a library of this unit
-// alone links but does not load: crt_query_host.h, crt_ao_host.h, crt_shade_host.h and crt_frame.h refer to the kernels the other five define)
+// Build: the Makefile's rule for libcrt_hip.so, one hipcc call with HIPFLAGS over every unit of HIP_UNITS (a library of this unit
+// alone links but does not load: crt_query_host.h, crt_ao_host.h, crt_shade_host.h and crt_frame.h refer to the kernels the other units define)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <cmath>

@@ -96,3 +96,11 @@ def test_only_the_owners_create_and_destroy_hip_objects():
     n = C.c_uint64(99)
     assert _lib.hip().crt_debug_live_resources(C.byref(n)) == 0 and n.value == 0
     assert _lib.hip().crt_debug_live_resources(None) == _lib.CRT_E_BAD_ARGUMENT
+
+
+def test_ssaa_flags_and_binding():
+    api = open(os.path.join(ROOT, "include/crt_api.h")).read()
+    assert re.search(r"CRT_RENDER_SSAA2\s*=\s*2048\b", api)
+    assert re.search(r"CRT_RENDER_SSAA4\s*=\s*4096\b", api)
+    assert "void crth_set_supersampling(int factor);" in open(os.path.join(ROOT, "include/crt_host.h")).read()
+    assert "crth_set_supersampling" in _lib.HOST_API

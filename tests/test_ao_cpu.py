@@ -64,17 +64,6 @@ def test_abi_declares_the_ao_entry_points_and_they_refuse_before_init():
     assert ao_ref.table().shape == (256, 3)                                   # the table needs no session
 
 
-def test_every_build_recipe_links_the_ao_unit():
-    found = 0
-    for rel in ("Makefile", "INTEGRATION.md", os.path.join("tools", "ab_build.sh"), os.path.join("tools", "ab_define.sh")):
-        text = open(os.path.join(ROOT, rel)).read().replace("\\\n", " ")
-        for line in text.splitlines():
-            if "-shared" in line and "crt_shim.hip" in line:
-                found += 1
-                assert "crt_ao.hip" in line, (rel, line)
-    assert found >= 4
-
-
 def test_session_refuses_tensors_and_parameters_it_cannot_hand_to_the_device():
     import torch
     with driver.Session(64, 48, host_only=True) as s:

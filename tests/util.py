@@ -9,6 +9,7 @@ _spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(
 _kernel_resources = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(_kernel_resources)
 kernel_resources, kernel_resource_rows, resource_line = _kernel_resources.kernel_resources, _kernel_resources.kernel_resource_rows, _kernel_resources.resource_line
+HIP_UNITS = _kernel_resources.HIP_UNITS
 
 
 def seeded_rays(scene_arenas, cam_pos, n, seed):

@@ -2,7 +2,7 @@
 # Build-container side of an A/B: compile libcrt_hip.so variants (extra compiler flags each) into build/ab/<name>/.
 # The built files travel to the GPU box with the snapshot; tools/ab_run.sh benches them there.
 # Usage: tools/ab_build.sh name1 "flags1" name2 "flags2" ...
-# All translation units of the library (the Makefile's list: crt_shim.hip, crt_rays.hip, crt_ao.hip, crt_inclusive.hip, crt_recip.hip, crt_shade.hip) are compiled with the variant's flags.
+# Each variant is the Makefile's own rule for the library (its units, its flags) with the variant's flags in EXTRA_HIPFLAGS.
 # A variant whose build fails leaves NO library behind (the target is deleted first), so a stale one is never benchmarked.
 cd "$(dirname "$0")/.."
 fail=0
@@ -11,10 +11,9 @@ names=()
 while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
   mkdir -p build/ab/$name
-  rm -f build/ab/$name/libcrt_hip.so
+  rm -f build/ab/$name/libcrt_hip.so build/ab/$name/libcrt_hip.so.tmp
   echo "$flags" > build/ab/$name/flags.txt
-  ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -Wall -Wno-unused-function $flags \
-      -shared -o build/ab/$name/libcrt_hip.so.tmp clraytracer_amd/csrc/crt_shim.hip clraytracer_amd/csrc/crt_rays.hip clraytracer_amd/csrc/crt_ao.hip clraytracer_amd/csrc/crt_inclusive.hip clraytracer_amd/csrc/crt_recip.hip clraytracer_amd/csrc/crt_shade.hip > build/ab/$name/build.log 2>&1 \
+  ( make HIP_SO=build/ab/$name/libcrt_hip.so.tmp EXTRA_HIPFLAGS="$flags" build/ab/$name/libcrt_hip.so.tmp > build/ab/$name/build.log 2>&1 \
       && mv build/ab/$name/libcrt_hip.so.tmp build/ab/$name/libcrt_hip.so ) &
   pids+=($!); names+=($name)
 done

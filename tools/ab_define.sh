@@ -17,8 +17,8 @@ variant=$(mktemp /tmp/libcrt_hip.variant.XXXXXX.so) || exit 1
 log=$(mktemp /tmp/ab_define.XXXXXX.log)
 for def in "$@"; do
   rm -f "$variant"
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -Wall -Wno-unused-function $def \
-      -shared -o "$variant" clraytracer_amd/csrc/crt_shim.hip clraytracer_amd/csrc/crt_rays.hip clraytracer_amd/csrc/crt_ao.hip clraytracer_amd/csrc/crt_inclusive.hip clraytracer_amd/csrc/crt_recip.hip clraytracer_amd/csrc/crt_shade.hip > "$log" 2>&1 || { echo "[$def] BUILD FAILED"; grep error "$log" | head -3; continue; }
+  # the Makefile's own rule for the library, into the variant's path (removed above: make never finds it up to date)
+  make HIP_SO="$variant" EXTRA_HIPFLAGS="$def" "$variant" > "$log" 2>&1 || { echo "[$def] BUILD FAILED"; grep error "$log" | head -3; continue; }
   cp "$variant" clraytracer_amd/csrc/libcrt_hip.so
   r=$(python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras $BENCH_ARGS 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['kernel_ms'])")
   echo "[$def] Mrays/s, ms/frame, kernel: $r"

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""Compile the translation units of libcrt_hip.so (crt_shim.hip, crt_rays.hip, crt_ao.hip, crt_inclusive.hip, crt_recip.hip, crt_shade.hip) for gfx950 with -Rpass-analysis=kernel-resource-usage and print one
+"""Compile the translation units of libcrt_hip.so (the Makefile's HIP_UNITS, with its HIPFLAGS) for gfx950 with -Rpass-analysis=kernel-resource-usage and print one
 line per kernel: VGPRs, AGPRs, scratch bytes per lane, occupancy, LDS bytes. Runs without a GPU (hipcc cross-compiles).
 
     python tools/kernel_resources.py [filter-substring] [-D...]
+    python tools/kernel_resources.py --record        writes tests/golden/kernel_resources.json, the ledger tests/test_kernel_resources.py compares with
 
 The tests read the same figures through kernel_resources() / kernel_resource_rows() (tests/util.py imports this file by path): one compile per unit and process.
 """
 import functools
+import json
 import os
 import re
 import subprocess
@@ -14,10 +16,19 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
-SOURCES = ("crt_shim.hip", "crt_rays.hip", "crt_ao.hip", "crt_inclusive.hip", "crt_recip.hip", "crt_shade.hip")     # the Makefile's units of libcrt_hip.so, in link order
+LEDGER = os.path.join(ROOT, "tests", "golden", "kernel_resources.json")
 
 
-def kernel_resource_rows(defs=(), source=SOURCES[0]):
+def makefile_words(variable):
+    """the words of the Makefile's `variable = ...` line, $(ARCH) expanded"""
+    value = re.search(rf"^{variable} = (.*)$", open(os.path.join(ROOT, "Makefile")).read(), re.M).group(1)
+    return value.replace("$(ARCH)", "gfx950").split()
+
+
+HIP_UNITS = tuple(makefile_words("HIP_UNITS"))     # the units of libcrt_hip.so, in link order
+
+
+def kernel_resource_rows(defs=(), source=HIP_UNITS[0]):
     """[(demangled kernel name, {remark field: int})] of one unit (default: crt_shim.hip) built with the Makefile's HIPFLAGS (+ defs), one entry per
     remark block in the compiler's order. (The two kernels in an anonymous namespace both demangle to the empty name here: a list keeps both.)"""
     return _compile(tuple(defs), source)
@@ -25,9 +36,7 @@ def kernel_resource_rows(defs=(), source=SOURCES[0]):
 
 @functools.lru_cache(maxsize=None)
 def _compile(defs, source):
-    flags = re.search(r"^HIPFLAGS = (.*)$", open(os.path.join(ROOT, "Makefile")).read(), re.M).group(1)
-    flags = flags.replace("$(ARCH)", "gfx950").split()
-    cmd = [HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "clraytracer_amd/csrc", source), "-o", os.devnull] + list(defs)
+    cmd = [HIPCC] + makefile_words("HIPFLAGS") + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "clraytracer_amd/csrc", source), "-o", os.devnull] + list(defs)
     p = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True, timeout=900)
     if p.returncode:
         raise RuntimeError(f"hipcc failed ({p.returncode}):\n{p.stderr[-2000:]}")
@@ -48,7 +57,7 @@ def _compile(defs, source):
 def kernel_resources(defs=()):
     """{demangled kernel name: {remark field: int}} of every unit of the library, over the same (memoised) compiles."""
     rows = {}
-    for source in SOURCES:
+    for source in HIP_UNITS:
         for name, r in kernel_resource_rows(defs, source):
             rows.setdefault(name, {}).update(r)
     return rows
@@ -59,11 +68,23 @@ def resource_line(name, r):
             f"LDS {r.get('LDS Size', -1):6d} SGPR {r.get('TotalSGPRs', -1):3d} spillV {r.get('VGPRs Spill', -1):3d}")
 
 
+def record():
+    """{unit: [[kernel name, {remark field: int}], ...]} of every unit into LEDGER: one row per line, fields in the compiler's order, so a re-record diffs row by row"""
+    units = []
+    for source in HIP_UNITS:
+        rows = ",\n".join("  " + json.dumps([name, r]) for name, r in kernel_resource_rows(source=source))
+        units.append(f" {json.dumps(source)}: [\n{rows}\n ]")
+    with open(LEDGER, "w") as f:
+        f.write("{\n" + ",\n".join(units) + "\n}\n")
+
+
 def main():
     flt = [a for a in sys.argv[1:] if not a.startswith("-")]
     defs = [a for a in sys.argv[1:] if a.startswith("-")]
     try:
-        rows = [row for source in SOURCES for row in kernel_resource_rows(defs, source)]
+        if defs == ["--record"] and not flt:
+            return record()
+        rows = [row for source in HIP_UNITS for row in kernel_resource_rows(defs, source)]
     except RuntimeError as e:
         sys.stderr.write(str(e) + "\n")
         raise SystemExit(1)

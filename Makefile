@@ -23,7 +23,7 @@ HOST_HDR = $(wildcard clraytracer_amd/host/*.hpp) $(wildcard include/*.h)
 
 EXAMPLE = examples/crt_headless
 
-UBENCH = tools/ubench/gather tools/ubench/chain tools/ubench/cumask
+UBENCH = tools/ubench/gather tools/ubench/chain tools/ubench/cumask tools/ubench/sky_index
 
 all: $(HIP_SO) $(HOST_SO) $(EXAMPLE) $(UBENCH) oracle
 
@@ -37,6 +37,11 @@ tools/ubench/chain: tools/ubench/chain.hip
 # CU-mask probe: hipExtStreamCreateWithCUMask on this part, and which CU each mask bit names (round 4's reserved-CU experiment)
 tools/ubench/cumask: tools/ubench/cumask.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -Wno-unused-value -o $@ $<
+
+# device self-check of the guarded float skybox index (crt_device.h: sample_skybox_guarded) over the library's own header, with the library's flags:
+# a program of its own, so that its two kernels are no rows of the library's resource ledger (tests/test_gpu_sky_index.py runs it)
+tools/ubench/sky_index: tools/ubench/sky_index.hip clraytracer_amd/csrc/crt_device.h include/crt_api.h include/crt_types.h
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -Wno-unused-value -o $@ $<
 
 # the reference's EngineMain loop over the mirrored C++ API
 $(EXAMPLE): examples/headless_main.cpp $(HOST_SO)

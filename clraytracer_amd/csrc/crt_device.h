@@ -903,6 +903,132 @@ __device__ __noinline__ int sample_skybox(v3 d, int texW, int texH)
     return (int)((uint32_t)phi * (uint32_t)texW + (uint32_t)(theta + 2));
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same index decided in single precision where that is provably safe (sample_skybox_guarded); sample_skybox above stays the
+// definition and serves every lane the float decision leaves open. No claim that a float function equals the double one: the float
+// values only have to land in the same texel, and a lane whose value comes near a texel edge is not decided by them.
+//  1. at~ (sky_index_float): q = min(|x|, |z|) / max(|x|, |z|), p = q * A(q * q) with A of degree 8 fitted to atan(q) / (pi q) on [0, 1],
+//     then the octant fix-ups 0.5 - p (|x| > |z|), 1 - a (-z < 0), -a (x < 0). ac~: c = sqrt(1 - |y|) * C(|y|) with C of degree 7 fitted to
+//     acos(t) / (pi sqrt(1 - t)) on [0, 1], then 1 - c (y < 0). Only IEEE single-precision + - * / sqrt, compares and selects, each written
+//     as one operation (the library is built with -ffp-contract=off): tests/sky_fast_ref.py (numpy) and tools/sky_index_bounds.c (C)
+//     restate the sequence and get the device's bits.
+//  2. E_c = max |ac~ - acos(y) / pi| over ALL float y with CRT_SKY_MIN_COMPONENT <= |y| < 1 (every other pattern is never decided, 5.),
+//     E_p = max |p - atan(q) / pi| over EVERY float q in [0, 1], both against glibc's double functions: tools/sky_index_bounds.c,
+//     recorded in profiles/sky_index_bounds.txt (E_p = 5.08e-8, E_c = 9.85e-8). p is taken at the rounded q: the true quotient is within
+//     2^-25 of it (q <= 1) and atan' <= 1, so 2^-24 / pi covers the division generously; each of the two fix-up subtractions rounds by at
+//     most 2^-25 (results <= 1). E_a = E_p + 2^-24 / pi + 2 * 2^-25.
+//  3. The definition's own roundings: (float) of the double quotient moves at, ac by at most 2^-25 (|at|, |ac| <= 1); two correct double
+//     libraries differ by a few 1e-16 before that (1e-15 taken). at * 0.5f is exact; the product with (float)texW rounds by at most half
+//     an ulp of a value of magnitude <= texW / 2, that is (texW / 2) 2^-24 -- once in the definition, once in the float form; the same with
+//     texH for phi.
+//  4. So with T the real-number value atan2(x, -z) / pi * texW / 2: |s_def - T| <= (texW / 2)(2^-25 + 1e-15 + 2^-24) and
+//     |s - T| <= (texW / 2)(E_a + 2^-24). If no integer lies within mW = (texW / 2) K_a of s, K_a = E_a + 2^-25 + 2^-23 + 1e-15, s and s_def
+//     lie strictly between the same two integers, and truncation towards zero -- whose only steps are at integers -- gives the same theta.
+//     Likewise mH = texH K_c, K_c = E_c + 2^-25 + 2^-23 + 1e-15, for phi (K_a = 2.784e-7, K_c = 2.475e-7). CRT_SKY_KA and CRT_SKY_KC are K_a and K_c times the
+//     safety factor 1.25, rounded up (the factor also covers the rounding of the float products that form mW and mH); a larger factor only sends more
+//     lanes to the double form.
+//  5. A lane is decided iff |s - rint(s)| > mW and |sv - rint(sv)| > mH, |s| and sv are below CRT_SKY_MAX_SCALED (2^22: rint, the difference
+//     and (int) are exact there), min(|x|, |z|) and |y| are at least CRT_SKY_MIN_COMPONENT (the smallest normal: zeros and denormals out),
+//     max(|x|, |z|) is at most CRT_SKY_MAX_COMPONENT (infinities out) and |y| < 1. Every compare is written so that a NaN fails it.
+//     Never decided, then: NaN, infinite, zero and denormal components, d.y in {0, +-1}, |d.y| > 1, texW or texH = 0 -- the arguments at
+//     which the definition returns special values -- and every value within the margin of a texel edge.
+//  6. The decision is taken for the wave, like recip's: if any lane of the call is undecided, those lanes, and only those, run the double
+//     form; otherwise it is a block the wave jumps over with one not-taken branch.
+// SKY_DOUBLE (shade_bounce): the double form alone, no float decision -- the counted instantiations and the kernels listed in DESIGN.md 4a
+// (kSkyDouble, crt_kernels.h), and everything under -DCRT_SKY_DOUBLE (A/B builds). tools/ubench/sky_index checks all of this on the device.
+// ------------------------------------------------------------------------------------------------
+#ifdef CRT_SKY_DOUBLE
+#define CRT_SKY_IS_DOUBLE(SKY_DOUBLE) true
+#else
+#define CRT_SKY_IS_DOUBLE(SKY_DOUBLE) (SKY_DOUBLE)
+#endif
+#define CRT_SKY_A0 3.183098733e-01f
+#define CRT_SKY_A1 -1.061023548e-01f
+#define CRT_SKY_A2 6.363610178e-02f
+#define CRT_SKY_A3 -4.519299418e-02f
+#define CRT_SKY_A4 3.379932418e-02f
+#define CRT_SKY_A5 -2.373590693e-02f
+#define CRT_SKY_A6 1.341282204e-02f
+#define CRT_SKY_A7 -5.007412285e-03f
+#define CRT_SKY_A8 8.805354009e-04f
+#define CRT_SKY_C0 5.000000000e-01f
+#define CRT_SKY_C1 -6.830871105e-02f
+#define CRT_SKY_C2 2.831966616e-02f
+#define CRT_SKY_C3 -1.595187746e-02f
+#define CRT_SKY_C4 9.779155254e-03f
+#define CRT_SKY_C5 -5.360673647e-03f
+#define CRT_SKY_C6 2.066315385e-03f
+#define CRT_SKY_C7 -3.857081174e-04f
+#define CRT_SKY_KA 3.48e-07f
+#define CRT_SKY_KC 3.10e-07f
+#define CRT_SKY_MIN_COMPONENT 1.17549435e-38f
+#define CRT_SKY_MAX_COMPONENT 3.40282347e+38f
+#define CRT_SKY_MAX_SCALED 4194304.0f
+// the float decision of one lane: theta and phi are the definition's iff it returns true (1.-5. above)
+__device__ __forceinline__ bool sky_index_float(v3 d, int texW, int texH, int& theta, int& phi)
+{
+    const float fW = (float)texW, fH = (float)texH;
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    const bool steep = ax > az;
+    const float mn = steep ? az : ax, mx = steep ? ax : az;
+    const float q = mn / mx;
+    const float u = q * q;
+    float p = CRT_SKY_A8;
+    p = p * u; p = p + CRT_SKY_A7;
+    p = p * u; p = p + CRT_SKY_A6;
+    p = p * u; p = p + CRT_SKY_A5;
+    p = p * u; p = p + CRT_SKY_A4;
+    p = p * u; p = p + CRT_SKY_A3;
+    p = p * u; p = p + CRT_SKY_A2;
+    p = p * u; p = p + CRT_SKY_A1;
+    p = p * u; p = p + CRT_SKY_A0;
+    p = p * q;
+    float a = steep ? 0.5f - p : p;
+    a = d.z > 0.0f ? 1.0f - a : a;
+    a = d.x < 0.0f ? -a : a;
+    const float r = __builtin_sqrtf(1.0f - ay);
+    float c = CRT_SKY_C7;
+    c = c * ay; c = c + CRT_SKY_C6;
+    c = c * ay; c = c + CRT_SKY_C5;
+    c = c * ay; c = c + CRT_SKY_C4;
+    c = c * ay; c = c + CRT_SKY_C3;
+    c = c * ay; c = c + CRT_SKY_C2;
+    c = c * ay; c = c + CRT_SKY_C1;
+    c = c * ay; c = c + CRT_SKY_C0;
+    c = c * r;
+    c = d.y < 0.0f ? 1.0f - c : c;
+    const float s = (a * 0.5f) * fW, sv = c * fH;
+    const float es = fabsf(s - __builtin_rintf(s)), ev = fabsf(sv - __builtin_rintf(sv));
+    const float mW = CRT_SKY_KA * fabsf(0.5f * fW), mH = CRT_SKY_KC * fabsf(fH);      // |texW|, |texH|: 4. holds for either sign
+    theta = (int)s;
+    phi = (int)sv;
+    return es > mW && ev > mH && fabsf(s) < CRT_SKY_MAX_SCALED && sv < CRT_SKY_MAX_SCALED
+        && mn >= CRT_SKY_MIN_COMPONENT && mx <= CRT_SKY_MAX_COMPONENT && ay >= CRT_SKY_MIN_COMPONENT && ay < 1.0f;
+}
+// Out of line like sample_skybox, whose body it holds a second time behind the wave's decision (a call from here would make this a
+// function with a frame of its own).
+__device__ __noinline__ int sample_skybox_guarded(v3 d, int texW, int texH)
+{
+    int theta, phi;
+    const bool decided = sky_index_float(d, texW, texH, theta, phi);
+    int idx = (int)((uint32_t)phi * (uint32_t)texW + (uint32_t)(theta + 2));
+    if (__builtin_expect(__ballot(!decided) != 0, 0)) {
+        if (!decided) {
+            const double PI = 3.14159265358979323846;
+            float at = (float)(atan2((double)d.x, (double)(-d.z)) / PI);
+            float ac = (float)(acos((double)d.y) / PI);
+            idx = (int)((uint32_t)f2i(ac * (float)texH) * (uint32_t)texW + (uint32_t)(f2i((at * 0.5f) * (float)texW) + 2));
+        }
+    }
+    return idx;
+}
+template <bool SKY_DOUBLE>
+__device__ __forceinline__ int sky_index(v3 d, int texW, int texH)
+{
+    if constexpr (CRT_SKY_IS_DOUBLE(SKY_DOUBLE)) return sample_skybox(d, texW, texH);
+    else return sample_skybox_guarded(d, texW, texH);
+}
+
 // MathAndSTL.cl:260-266
 __device__ __forceinline__ int sample_texture(const CrtTexture& tex, float u, float v)
 {
@@ -970,7 +1096,8 @@ struct NoSink { };
 template <class SINK, class = void> struct SinkTakesSurface : std::false_type { };
 template <class SINK>
 struct SinkTakesSurface<SINK, std::void_t<decltype(std::declval<const SINK&>().hit(std::declval<const Closest&>(), v3(), 0u, 0u, 0.0f, 0.0f))>> : std::true_type { };
-template <bool DEFER_ENERGY = false, bool REFRACT = false, class SINK = NoSink>
+// SKY_DOUBLE: the skybox index in its double form alone (sample_skybox; see sample_skybox_guarded)
+template <bool DEFER_ENERGY = false, bool REFRACT = false, class SINK = NoSink, bool SKY_DOUBLE = false>
 __device__ __forceinline__ int shade_bounce(const CrtDevScene& S, const Closest& c, PathState& ps, int bounce, float lightY, float lightZ,
                                             float* ndlOut = nullptr, const SINK* sink = nullptr)
 {
@@ -980,7 +1107,7 @@ __device__ __forceinline__ int shade_bounce(const CrtDevScene& S, const Closest&
         if constexpr (kSink) { if (bounce == 0) sink->miss(c); }
         // textures[2] for every lane: a scalar load (constant address space, see crt_const_f32x4_ptr)
         const crt_f32x4 skyHdr = ((crt_const_f32x4_ptr)S.textures)[2];
-        int idx = clamp_texel(sample_skybox(ps.d, __float_as_int(skyHdr.x), __float_as_int(skyHdr.y)), S.numTexels);
+        int idx = clamp_texel(sky_index<SKY_DOUBLE>(ps.d, __float_as_int(skyHdr.x), __float_as_int(skyHdr.y)), S.numTexels);
         uint32_t px = S.texels[idx];
         v3 skyc = scale3(mk3((float)(px & 0xffu), (float)((px >> 8) & 0xffu), (float)((px >> 16) & 0xffu)), UcharToFloat01);
         ps.result = add3(ps.result, scale3(skyc, ps.energy));

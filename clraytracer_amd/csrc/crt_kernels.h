@@ -385,6 +385,11 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
     // the reciprocals as divisions (crt_device.h: recip): the counted launches, and the one G-buffer kernel that sits at its 64 VGPRs so
     // tightly that the short form's branch costs it 8 spilled registers (shadow rays + instance tree without refraction)
     constexpr bool kDivide = COUNT || (GBUFFER && SHADOW && TLAS && !REFRACT);
+    // the skybox index in its double form alone (crt_device.h: sample_skybox_guarded): the counted launches, and every uncounted instantiation whose
+    // row of the kernel-resource ledger the second out-of-line function would move -- the G-buffer kernels with shadow rays and an
+    // instance tree or refraction (<shadow, tree, no refraction> spills 8 registers to 32 B of scratch, the other two move an SGPR or an SGPR spill)
+    // and the shadow-ray kernels without tree and refraction, plain and supersampled (SGPR spills)
+    constexpr bool kSkyDouble = COUNT || (GBUFFER && SHADOW && (TLAS || REFRACT)) || (!GBUFFER && SHADOW && !TLAS && !REFRACT);
     LaneCounters lc; zero_counters(lc);
     WaveStampStart t0 = { 0, 0 };
     if (STAMP) t0 = wave_stamp_start();
@@ -405,10 +410,10 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
             if (SHADOW || GBUFFER) ps.energy = __uint_as_float(stack.parked(kParkNdl));
             float ndl = 0.0f;
             int cont;
-            if constexpr (!GBUFFER) cont = shade_bounce<SHADOW, REFRACT>(S, c, ps, bounce, F.lightY, F.lightZ, &ndl);
+            if constexpr (!GBUFFER) cont = shade_bounce<SHADOW, REFRACT, NoSink, kSkyDouble>(S, c, ps, bounce, F.lightY, F.lightZ, &ndl);
             else {
                 const GBufferSink sink = { gb, &F, b, lane };
-                cont = shade_bounce<SHADOW, REFRACT, GBufferSink>(S, c, ps, bounce, F.lightY, F.lightZ, &ndl, &sink);
+                cont = shade_bounce<SHADOW, REFRACT, GBufferSink, kSkyDouble>(S, c, ps, bounce, F.lightY, F.lightZ, &ndl, &sink);
             }
             if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
             if (!cont) break;
@@ -538,7 +543,7 @@ __global__ __launch_bounds__(CRT_BLOCK, COUNT ? CRT_WAVES_PER_SIMD_COUNT : CRT_W
         ps.d = raygen_dir(F, px, py);
         if (COUNT) { lc.rays++; lc.primary++; }
         Closest c = closest_hit<COUNT>(S, ps.o, ps.d, stack, lc);
-        cont = shade_bounce(S, c, ps, 0, F.lightY, F.lightZ) != 0;
+        cont = shade_bounce<false, false, NoSink, COUNT>(S, c, ps, 0, F.lightY, F.lightZ) != 0;
         if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
         out[(size_t)py * (size_t)F.width + (size_t)px] = make_float4(ps.result.x, ps.result.y, ps.result.z, 1.0f);
     }
@@ -597,7 +602,7 @@ __global__ __launch_bounds__(CRT_BLOCK, COUNT ? CRT_WAVES_PER_SIMD_COUNT : CRT_W
         if (COUNT) { lc.rays++; lc.secondary++; }
         // (the reciprocals as divisions, crt_device.h: recip -- this opt-in form's kernel is recorded register for register, and stays that)
         Closest c = closest_hit<COUNT, false, false, false, false, false, true>(S, ps.o, ps.d, stack, lc);
-        const bool cont = shade_bounce(S, c, ps, 1, F.lightY, F.lightZ) != 0;
+        const bool cont = shade_bounce<false, false, NoSink, COUNT>(S, c, ps, 1, F.lightY, F.lightZ) != 0;
         if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
         out[r.pixel] = make_float4(ps.result.x, ps.result.y, ps.result.z, 1.0f);
     }

@@ -88,7 +88,7 @@ void crt_trace_refill_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out
                     const uint32_t st = stack.parked(0);
                     const int bounce = (int)(st >> 31);
                     ps.energy = __uint_as_float(stack.parked(1));      // (waits in LDS through the traversals, as in the megakernel's SHADOW instantiations)
-                    const int cont = shade_bounce(S, c, ps, bounce, F.lightY, F.lightZ);
+                    const int cont = shade_bounce<false, false, NoSink, COUNT>(S, c, ps, bounce, F.lightY, F.lightZ);
                     c = no_hit();
                     if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
                     if (cont != 0 && bounce == 0) {           // kernel_main.cl:187: the second iteration of the bounce loop
@@ -200,7 +200,7 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
                 if (cand == 0 && S.numInstances <= 64u) {
                     // no instance can be hit: closest_hit would return the initial miss (kernel_main.cl:219-224: skybox, break)
                     if (COUNT) { lc.rays++; lc.primary++; lc.misses++; count_culled(lc, cnt); }
-                    (void)shade_bounce(S, no_hit(), ps, 0, F.lightY, F.lightZ);
+                    (void)shade_bounce<false, false, NoSink, true>(S, no_hit(), ps, 0, F.lightY, F.lightZ);
                     out[(size_t)py * (size_t)F.width + (size_t)px] = make_float4(ps.result.x, ps.result.y, ps.result.z, 1.0f);
                 } else listed = true;
             }
@@ -222,7 +222,7 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
                 }
                 if (COUNT) { lc.rays++; lc.primary++; }
                 const Closest c = closest_hit<COUNT, STAMP>(S, ps.o, ps.d, stack, lc);
-                cont = shade_bounce(S, c, ps, 0, F.lightY, F.lightZ) != 0;
+                cont = shade_bounce<false, false, NoSink, true>(S, c, ps, 0, F.lightY, F.lightZ) != 0;
                 if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
             }
             uint32_t base2 = base, lane2 = lane;
@@ -256,7 +256,7 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
                 const uint32_t pixel = q[base2 + lane2].pixel;
                 const float4 partial = out[pixel];
                 ps.result = mk3(partial.x, partial.y, partial.z);
-                const bool cont = shade_bounce(S, c, ps, 1, F.lightY, F.lightZ) != 0;
+                const bool cont = shade_bounce<false, false, NoSink, true>(S, c, ps, 1, F.lightY, F.lightZ) != 0;
                 if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
                 out[pixel] = make_float4(ps.result.x, ps.result.y, ps.result.z, 1.0f);
             }

@@ -277,7 +277,9 @@ int crt1_upload_texels(const void* rgb8, size_t byteOffset, size_t bytes)
     HIPCHK(hipMemcpyAsync(g.rawTexels + byteOffset, rgb8, bytes, hipMemcpyHostToDevice, g.stream));
     if (byteOffset + bytes > g.texelBytesHigh) g.texelBytesHigh = byteOffset + bytes;
     const size_t firstTexel = byteOffset / 3;
-    const size_t endTexel = (byteOffset + bytes) / 3;       // whole texels only; a trailing partial texel waits for its bytes
+    // Every texel the span touches whose three bytes are in the pool. At the pool's end that is whole texels only (a trailing partial texel waits for
+    // its bytes); a span that ends inside a texel uploaded before must redo that texel as well, or its word keeps the bytes it was made from.
+    const size_t endTexel = std::min((byteOffset + bytes + 2) / 3, g.texelBytesHigh / 3);
     if (endTexel > firstTexel) {
         const size_t count = endTexel - firstTexel;
         crt_relayout_texels<<<(unsigned)((count + 255) / 256), 256, 0, g.stream>>>(g.rawTexels, firstTexel, count, g.texels);

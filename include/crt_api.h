@@ -150,7 +150,8 @@ int crt_upload_bvh_roots(const uint32_t* roots, size_t firstMesh, size_t count);
 int crt_upload_materials(const void* materials, size_t first, size_t count);
 /* ResourceManager.cpp:236 */
 int crt_upload_texture_table(const void* textures, size_t count);
-/* ResourceManager.cpp:177,203 -- packed RGB8 bytes at a byte offset into the texel pool. */
+/* ResourceManager.cpp:177,203 -- packed RGB8 bytes at a byte offset into the texel pool. Any offset and length: the span need not begin or
+ * end on a texel; every texel it touches whose three bytes have been uploaded (now or earlier) shows its new bytes in the next frame. */
 int crt_upload_texels(const void* rgb8, size_t byteOffset, size_t bytes);
 /* Renderer.cpp:245,314. Host-side only: the instance table is versioned, frames already submitted keep the version they were
  * submitted with and every later frame refreshes its slot's device copy on its own stream -- no waiting for frames in flight. */

@@ -107,7 +107,7 @@ __device__ __forceinline__ bool ao_item(const CrtAoArgs& A, const CrtFrame& F, u
 
 // The kernel's text, written once: crt_ao_kernel (crt_ao.hip) and crt_ao_inclusive_kernel (crt_inclusive.hip) are one-line wrappers that
 // own the LDS stack and pass it in. (Arguments by value, as the kernels take them: by reference the same text allocates registers differently.)
-//   INCLUSIVE  closest_hit's: intersect_aabb<true> for every box test; nothing else differs.
+//   INCLUSIVE  closest_hit's TR_INCLUSIVE: intersect_aabb<true> for every box test; nothing else differs.
 template <int SOURCE, bool TLAS, bool INCLUSIVE>
 __device__ __forceinline__ void crt_ao_body(CrtDevScene S0, CrtAoArgs A, CrtFrame F, crt_lds_u32_ptr s_stack)
 {
@@ -141,10 +141,9 @@ __device__ __forceinline__ void crt_ao_body(CrtDevScene S0, CrtAoArgs A, CrtFram
                     if (dot3(d, n2) < 0.0f) d = neg3(d);
                     const float w = dot3(d, n2);
                     const CrtStackT<TLAS ? CRT_TLAS_PARK : 0> stack = { s_stack + lane2, S0.stackOverflow };
-                    // (kDivide: the G-buffer source without an instance tree keeps the reciprocals as divisions, crt_device.h: recip -- with the
-                    // short form's branch in the triangle loop it spills one register)
-                    constexpr bool kDivide = SOURCE == CRT_AO_FRAME && !TLAS;
-                    const Closest c = closest_hit<false, false, true, TLAS, INCLUSIVE, false, kDivide>(S, o, d, stack, lc, best0, noCull);
+                    constexpr unsigned kOcclusion = TR_ANYHIT | opt_if(TLAS, TR_TLAS) | opt_if(INCLUSIVE, TR_INCLUSIVE)
+                                                  | opt_if(policy::ao_divides(SOURCE == CRT_AO_FRAME, TLAS), TR_DIVIDE);
+                    const Closest c = closest_hit<kOcclusion>(S, o, d, stack, lc, best0, noCull);
                     const float occ = c.anyHit ? 1.0f : 0.0f;
                     num += w * occ; den += w;
                 }

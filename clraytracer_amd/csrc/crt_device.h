@@ -259,9 +259,8 @@ __device__ __forceinline__ float intersect_aabb(v3 o, v3 inv, float4 bmin, float
 // -125 ... 126 for everything the short sequence gets right -- so "outside -125 ... 126" is exactly the set that needs the division.
 // The decision is taken for the WAVE (one compare mask against zero, a uniform branch the wave falls through): if any lane active at
 // this step needs the division, every lane of the step takes the division's result, otherwise the division is a block no lane enters.
-// DIVIDE: the division as written, no guard. The counted instantiations (Traversal<COUNT = true>: diagnostics, never the frame a user
-// waits for) keep it, so that a counted launch runs the same instructions whatever the uncounted ones do; so does everything under
-// -DCRT_IEEE_RECIP (A/B builds).
+// DIVIDE (the traversal's TR_DIVIDE): the division as written, no guard -- the kernels of policy's "who keeps the division" below, and
+// everything under -DCRT_IEEE_RECIP (A/B builds).
 // ------------------------------------------------------------------------------------------------
 #ifdef CRT_IEEE_RECIP
 #define CRT_RECIP_DIVIDES(DIVIDE) true
@@ -358,7 +357,7 @@ __device__ __forceinline__ Closest no_hit(float distance = 99999.0f)
 }
 
 
-// diagnostic (ITERS builds only): true in exactly one active lane, so summing over lanes counts wave-level loop trips
+// diagnostic (TR_ITERS instantiations only): true in exactly one active lane, so summing over lanes counts wave-level loop trips
 __device__ __forceinline__ bool first_active_lane() { return (int)__lane_id() == __ffsll((long long)__ballot(1)) - 1; }
 
 // Device-side instance record (64 B, built at upload): the 3 used columns of inverseTransform
@@ -407,6 +406,78 @@ __device__ __forceinline__ CrtDevInstance load_instance(const CrtDevInstance* __
 }
 
 // ------------------------------------------------------------------------------------------------
+// Compile-time options of the traversal, the instance cull and the shading: one `unsigned` of named bits per function, spelled at the
+// call site -- closest_hit<TR_ANYHIT | opt_if(TLAS, TR_TLAS)>(...). An option that is not named is off, and none follows from another.
+// ------------------------------------------------------------------------------------------------
+enum : unsigned {               // closest_hit, trip_steps, Traversal
+    TR_COUNT = 1u << 0,         // per-ray work counters (LaneCounters)
+    TR_ITERS = 1u << 1,         // stamped diagnostic launches: the counters record wave-level trips instead of per-ray work
+    TR_ANYHIT = 1u << 2,        // shadow rays, occlusion: stop at the first triangle that passes
+    TR_TLAS = 1u << 3,          // candidates from the instance tree
+    TR_INCLUSIVE = 1u << 4,     // intersect_aabb's inclusive rule for every box test (the device queries only)
+    TR_STAGE = 1u << 5,         // the camera bounce's cull terms once per wave (staged_candidate_mask)
+    TR_DIVIDE = 1u << 6,        // the reciprocals as divisions (recip)
+    TR_ALL = (1u << 7) - 1u
+};
+enum : unsigned { CM_COUNT = 1u << 0, CM_DEFER_COUNT = 1u << 1, CM_ALL = (1u << 2) - 1u };                        // candidate_mask
+enum : unsigned { SB_DEFER_ENERGY = 1u << 0, SB_REFRACT = 1u << 1, SB_SKY_DOUBLE = 1u << 2, SB_ALL = (1u << 3) - 1u };   // shade_bounce
+constexpr unsigned opt_if(bool on, unsigned bit) { return on ? bit : 0u; }
+constexpr bool has_opt(unsigned opts, unsigned bit) { return (opts & bit) != 0u; }
+
+// ------------------------------------------------------------------------------------------------
+// Which kernel keeps the division (TR_DIVIDE), which the double-only skybox index (SB_SKY_DOUBLE), which stages the camera bounce's cull
+// terms (TR_STAGE): decided here and nowhere else, by kernel family, and passed by name at the call sites. DESIGN.md 4a ("Who keeps the
+// division", "Who keeps the double-only form", the staged cull) lists the same items in the same order. Every choice is pinned by a row
+// of the kernel-resource ledger (tests/golden/kernel_resources.json): 64 VGPRs, no scratch, 8 waves/SIMD for the plain kernels.
+// A counted launch (diagnostics, never the frame a user waits for) keeps the division and the double-only form in every family: it runs
+// the same instructions whatever the uncounted ones do, and is the independent path the frame tests compare with.
+// ------------------------------------------------------------------------------------------------
+namespace policy {
+// ---- who keeps the division ----
+// trace_body (crt_trace_kernel, its SSAA, G-buffer and ldstop forms): the counted launches, and the one G-buffer kernel that sits at its 64 VGPRs
+// so tightly that the short form's branch costs it 8 spilled registers (shadow rays + instance tree without refraction)
+constexpr bool trace_divides(bool COUNT, bool GBUFFER, bool SHADOW, bool TLAS, bool REFRACT) { return COUNT || (GBUFFER && SHADOW && TLAS && !REFRACT); }
+// crt_ao_body (crt_ao_kernel and its inclusive twin): the G-buffer source without an instance tree -- with the short form's branch in the
+// triangle loop it spills one register
+constexpr bool ao_divides(bool FRAME, bool TLAS) { return FRAME && !TLAS; }
+// the wavefront form: crt_primary_kernel when counted; crt_bounce_kernel always -- this opt-in form's kernel is recorded register for
+// register, and stays that
+constexpr bool primary_divides(bool COUNT) { return COUNT; }
+constexpr bool kBounceDivides = true;
+// crt_trace_refill_kernel, crt_trace_block_kernel: when counted
+constexpr bool refill_block_divides(bool COUNT) { return COUNT; }
+// crt_query_kernel (hit-record parity on the host's rays): a counted kernel
+constexpr bool kQueryDivides = true;
+// the queries on device buffers (crt_rays_kernel and its inclusive twin, crt_shade_kernel): the short form at the plain budget
+constexpr bool kDeviceQueryDivides = false;
+
+// ---- who keeps the double-only skybox index ----
+// trace_body: the counted launches, and every uncounted instantiation whose row of the ledger the second out-of-line function would move --
+// the G-buffer kernels with shadow rays and an instance tree or refraction (<shadow, tree, no refraction> spills 8 registers to 32 B of
+// scratch, the other two move an SGPR or an SGPR spill) and the shadow-ray kernels without tree and refraction, plain and supersampled
+// (SGPR spills)
+constexpr bool trace_sky_double(bool COUNT, bool GBUFFER, bool SHADOW, bool TLAS, bool REFRACT)
+{
+    return COUNT || (GBUFFER && SHADOW && (TLAS || REFRACT)) || (!GBUFFER && SHADOW && !TLAS && !REFRACT);
+}
+// the wavefront form (crt_primary_kernel, crt_bounce_kernel) and crt_trace_refill_kernel: when counted
+constexpr bool wavefront_sky_double(bool COUNT) { return COUNT; }
+constexpr bool refill_sky_double(bool COUNT) { return COUNT; }
+// crt_trace_block_kernel: always -- the guarded form moves the uncounted kernel's SGPR spills (61 -> 63)
+constexpr bool kBlockSkyDouble = true;
+// crt_shade_kernel: the guarded form
+constexpr bool kShadeSkyDouble = false;
+
+// ---- who stages the camera bounce's cull terms ----
+// trace_body alone: uncounted, unstamped, without an instance tree, on a one-wave workgroup's stack (not ldstop's) -- at the camera bounce
+// every ray of the wave starts at F.camPos, so the cull's origin-only terms are computed once per wave (closest_hit's sharedOrigin says
+// which bounce that is). Every other kernel compiles to what it compiled to before the staged form existed.
+constexpr bool trace_stages_cull(bool COUNT, bool STAMP, bool TLAS, bool TOP) { return !COUNT && !STAMP && !TLAS && !TOP; }
+// crt_shade_kernel: the origins of a batch are not shared
+constexpr bool kShadeStagesCull = false;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Per-lane traversal state machine: the instance loop + IntersectBVH of kernel_main.cl:124-160,198-217.
 //
 // Upstream (and a literal port) runs `for instance { while pop { descend } }` in lock-step: a wave pays, for
@@ -417,8 +488,12 @@ __device__ __forceinline__ CrtDevInstance load_instance(const CrtDevInstance* __
 // so results are bit-identical; only the interleaving between lanes differs.
 // The stack lives in LDS/scratch (CRT_STACK_*); slot indices wrap modulo 32 where upstream's array would overflow.
 // ------------------------------------------------------------------------------------------------
-template <bool COUNT, bool DIVIDE = COUNT>
+// OPTS: the TR_* options of the closest_hit (or the kernel's own loop, crt_refill.h) that owns it, carried in the type: trip_steps reads them
+// back from it. The members read TR_COUNT and TR_DIVIDE; inner and leaf take the box rule and any-hit from the options of the trip that calls them.
+template <unsigned OPTS>
 struct Traversal {
+    static_assert((OPTS & ~TR_ALL) == 0u, "unknown traversal option");
+    static constexpr bool COUNT = has_opt(OPTS, TR_COUNT), DIVIDE = has_opt(OPTS, TR_DIVIDE);
     v3 mo, md, inv;               // ray in the current instance's object space (direction not renormalised, hazard H6)
     Triout tr;                    // running best of the current instance (kernel_main.cl:200-202)
     int sp, prot, inters;         // stack pointer, pop counter (kernel_main.cl:131), OR of the `passed` flags
@@ -472,10 +547,11 @@ struct Traversal {
         if (COUNT) { lc.traversals++; lc.pops++; }
     }
     // kernel_main.cl:142-157: fetch the child pair, two slab tests, near child first, far child pushed
-    // (INCLUSIVE: intersect_aabb's; two boxes that both hold the origin return 0 and 0, `dist1 > dist2` is false: left first)
-    template <bool INCLUSIVE = false, class STK>
+    // (TR_INCLUSIVE of the trip's options: intersect_aabb's; two boxes that both hold the origin return 0 and 0, `dist1 > dist2` is false: left first)
+    template <unsigned TRIP, class STK>
     __device__ __forceinline__ void inner(const CrtDevScene& S, const STK& stack, Closest& c, LaneCounters& lc)
     {
+        constexpr bool INCLUSIVE = has_opt(TRIP, TR_INCLUSIVE);
         // every lane of this step on the same node (the top of a tree under a coherent packet): one scalar load instead of four
         // vector loads, the boxes as scalar operands. (Round 2 measured the same idea as a wash -- the uniformity test costs every
         // step -- but with the instance bounds and records on the scalar path the node fetches are 3/4 of the vector-memory
@@ -532,10 +608,11 @@ struct Traversal {
         else ref = nearRef;
     }
     // kernel_main.cl:135-140: every triangle of the leaf, then the next pop.
-    // ANYHIT (shadow rays): the traversal ends at the first triangle that passes.
-    template <bool ANYHIT, class STK>
+    // TR_ANYHIT of the trip's options (shadow rays): the traversal ends at the first triangle that passes.
+    template <unsigned TRIP, class STK>
     __device__ __forceinline__ void leaf(const CrtDevScene& S, const STK& stack, Closest& c, LaneCounters& lc)
     {
+        constexpr bool ANYHIT = has_opt(TRIP, TR_ANYHIT);
         const uint32_t first = ref & 0x00FFFFFFu;
         uint32_t n = (ref >> 24) & 0x7Fu;
         if (n == 0) n = S.bigLeaf[first];
@@ -619,9 +696,12 @@ __device__ __forceinline__ bool sphere_culls(const float4 bs, v3 o, v3 d, float 
 // pointer -- a member of a by-value kernel argument carries no noalias/readonly information -- rounds 1-2 issued one VECTOR
 // load per instance, bounce and wave here: 12 % of the trace kernel's vector-memory instructions, on the pipeline that
 // bounds it. The table is written by the host before the launch and never by a kernel.
-template <bool COUNT, bool DEFER_COUNT = false>
+// OPTS: CM_COUNT: the culled instances are counted; CM_DEFER_COUNT: ... by the caller (closest_hit's any-hit form), not here.
+template <unsigned OPTS = 0u>
 __device__ __forceinline__ unsigned long long candidate_mask(const CrtDevScene& S, v3 o, v3 d, uint32_t base, uint32_t cnt, LaneCounters& lc)
 {
+    static_assert((OPTS & ~CM_ALL) == 0u, "unknown cull option");
+    constexpr bool COUNT = has_opt(OPTS, CM_COUNT), DEFER_COUNT = has_opt(OPTS, CM_DEFER_COUNT);
     const float dd = dot3(d, d);
     unsigned long long cand = 0;
     const crt_const_f32x4_ptr bounds = (crt_const_f32x4_ptr)S.instBounds;
@@ -776,12 +856,15 @@ __device__ __forceinline__ bool tlas_candidates(const CrtDevScene& S, v3 o, v3 d
 // for all later instances. `anyHit` is the same boolean the full closest-hit loop would return, because until the
 // first passing triangle both visit the same nodes in the same order; only the work (and the counters) shrink.
 // ITERS (stamped diagnostic launches): the counters record wave-level trips instead of per-ray work.
-template <bool COUNT, bool ITERS, bool ANYHIT, bool INCLUSIVE = false, bool DIVIDE, class STK>
-__device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stack, Traversal<COUNT, DIVIDE>& T, Closest& c, LaneCounters& lc, bool done)
+// OPTS (TR_*): the trip's options -- its traversal's, except that a trip may leave the stamps out (closest_hit's instance-tree path).
+template <unsigned OPTS, unsigned OWNER, class STK>
+__device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stack, Traversal<OWNER>& T, Closest& c, LaneCounters& lc, bool done)
 {
+    static_assert((OPTS & ~TR_ALL) == 0u && ((OPTS ^ OWNER) & ~TR_ITERS) == 0u, "a trip runs under its traversal's options");
+    constexpr bool ITERS = has_opt(OPTS, TR_ITERS);
     if (!done && T.at_inner()) {
         if (ITERS) { lc.rays++; if (first_active_lane()) lc.innerVisits++; }
-        T.template inner<INCLUSIVE>(S, stack, c, lc);
+        T.template inner<OPTS>(S, stack, c, lc);
     }
     if (!done && T.at_leaf()) {
         if (ITERS) {
@@ -791,11 +874,11 @@ __device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stac
             for (int off = 32; off > 0; off >>= 1) { const uint32_t o2 = (uint32_t)__shfl_xor((int)n, off, 64); n = o2 > n ? o2 : n; }
             if (first_active_lane()) lc.misses += n;
         }
-        T.template leaf<ANYHIT>(S, stack, c, lc);
+        T.template leaf<OPTS>(S, stack, c, lc);
     }
     if (!done && T.at_inner()) {
         if (ITERS) { if (first_active_lane()) lc.hits++; }
-        T.template inner<INCLUSIVE>(S, stack, c, lc);      // lanes that just popped an inner node go on at once
+        T.template inner<OPTS>(S, stack, c, lc);           // lanes that just popped an inner node go on at once
     }
 }
 
@@ -804,18 +887,22 @@ __device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stac
 // chunkedOnly (TLAS only, wave-uniform): take the chunked candidate loop although an instance tree exists -- what a wave of the TLAS
 // instantiation does anyway when a lane's candidates do not fit its list; crt_rays_kernel forces it for a wave with an origin beyond
 // the cull's proven range, whose scene then has the all-never bounds table. Both are defaulted and constant for every other caller.
-// INCLUSIVE (the device queries only): intersect_aabb's rule for every box test, threaded down through trip_steps and Traversal::inner as a
-// template parameter -- no run-time branch in a step; the instance cull stays on (sphere_culls' derivation, "Inclusive pass").
-// STAGE (the uncounted Trace kernels without an instance tree only) + sharedOrigin (wave-uniform, run time: the camera bounce): the
+// OPTS: the TR_* options, by name (COUNT ... DIVIDE below are their bits).
+// INCLUSIVE (the device queries only): intersect_aabb's rule for every box test, threaded down through trip_steps and Traversal::inner in the
+// trip's options -- no run-time branch in a step; the instance cull stays on (sphere_culls' derivation, "Inclusive pass").
+// STAGE (policy::trace_stages_cull) + sharedOrigin (wave-uniform, run time: the camera bounce): the
 // chunk's mask comes from staged_candidate_mask -- the same mask, bit for bit. A run-time value, not a second instantiation: the trip
 // loop below exists once per kernel.
-template <bool COUNT, bool ITERS = false, bool ANYHIT = false, bool TLAS = false, bool INCLUSIVE = false, bool STAGE = false, bool DIVIDE = COUNT, class STK = CrtStack>
+template <unsigned OPTS, class STK>
 __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d, const STK& stack, LaneCounters& lc, float best0 = 99999.0f,
                                                bool chunkedOnly = false, bool sharedOrigin = false)
 {
+    constexpr bool COUNT = has_opt(OPTS, TR_COUNT), ITERS = has_opt(OPTS, TR_ITERS), ANYHIT = has_opt(OPTS, TR_ANYHIT), TLAS = has_opt(OPTS, TR_TLAS),
+                   STAGE = has_opt(OPTS, TR_STAGE);
+    static_assert((OPTS & ~TR_ALL) == 0u, "unknown traversal option");
     static_assert(!STAGE || (!COUNT && !ITERS && !ANYHIT && !TLAS && !STK::kTop), "staged cull terms: uncounted closest-hit traversals of one-wave workgroups");
     Closest c = no_hit(best0);
-    Traversal<COUNT, DIVIDE> T; T.reset();
+    Traversal<OPTS> T; T.reset();
 
     if constexpr (TLAS) {
         // Many instances: every lane collects its (few) candidates from the instance tree and walks them in ascending
@@ -844,7 +931,7 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
                         T.template enter<STK::kTop>(S, k, o, d, c.distance, lc);
                     }
                 }
-                trip_steps<COUNT, false, ANYHIT, INCLUSIVE>(S, stack, T, c, lc, done);
+                trip_steps<OPTS & ~TR_ITERS>(S, stack, T, c, lc, done);      // (this path records no wave-level trips)
             }
             return c;
         }
@@ -853,8 +940,8 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
     for (uint32_t base = 0; base < S.numInstances; base += 64) {
         const uint32_t cnt = (S.numInstances - base) < 64u ? (S.numInstances - base) : 64u;
         unsigned long long cand;
-        if constexpr (STAGE) cand = sharedOrigin ? staged_candidate_mask(S, o, d, base, cnt, stack) : candidate_mask<false>(S, o, d, base, cnt, lc);
-        else cand = candidate_mask<COUNT, ANYHIT>(S, o, d, base, cnt, lc);
+        if constexpr (STAGE) cand = sharedOrigin ? staged_candidate_mask(S, o, d, base, cnt, stack) : candidate_mask(S, o, d, base, cnt, lc);
+        else cand = candidate_mask<opt_if(COUNT, CM_COUNT) | opt_if(ANYHIT, CM_DEFER_COUNT)>(S, o, d, base, cnt, lc);
         // ANYHIT + COUNT: a culled instance is only "visited" (one pop, one inner visit upstream) if the ray gets that
         // far, so culled instances are counted when a later candidate is entered or the chunk ends without a hit
         unsigned long long culledLeft = (COUNT && ANYHIT) ? (~cand & (cnt == 64u ? ~0ull : ((1ull << cnt) - 1ull))) : 0ull;
@@ -882,7 +969,7 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
                     T.template enter<STK::kTop>(S, base + k, o, d, c.distance, lc);
                 }
             }
-            trip_steps<COUNT, ITERS, ANYHIT, INCLUSIVE>(S, stack, T, c, lc, done);
+            trip_steps<OPTS>(S, stack, T, c, lc, done);
         }
     }
     return c;
@@ -934,8 +1021,8 @@ __device__ __noinline__ int sample_skybox(v3 d, int texW, int texH)
 //     which the definition returns special values -- and every value within the margin of a texel edge.
 //  6. The decision is taken for the wave, like recip's: if any lane of the call is undecided, those lanes, and only those, run the double
 //     form; otherwise it is a block the wave jumps over with one not-taken branch.
-// SKY_DOUBLE (shade_bounce): the double form alone, no float decision -- the counted instantiations and the kernels listed in DESIGN.md 4a
-// (kSkyDouble, crt_kernels.h), and everything under -DCRT_SKY_DOUBLE (A/B builds). tools/ubench/sky_index checks all of this on the device.
+// SKY_DOUBLE (shade_bounce's SB_SKY_DOUBLE): the double form alone, no float decision -- the kernels of policy's "who keeps the double-only
+// skybox index" above, and everything under -DCRT_SKY_DOUBLE (A/B builds). tools/ubench/sky_index checks all of this on the device.
 // ------------------------------------------------------------------------------------------------
 #ifdef CRT_SKY_DOUBLE
 #define CRT_SKY_IS_DOUBLE(SKY_DOUBLE) true
@@ -1097,10 +1184,13 @@ template <class SINK, class = void> struct SinkTakesSurface : std::false_type { 
 template <class SINK>
 struct SinkTakesSurface<SINK, std::void_t<decltype(std::declval<const SINK&>().hit(std::declval<const Closest&>(), v3(), 0u, 0u, 0.0f, 0.0f))>> : std::true_type { };
 // SKY_DOUBLE: the skybox index in its double form alone (sample_skybox; see sample_skybox_guarded)
-template <bool DEFER_ENERGY = false, bool REFRACT = false, class SINK = NoSink, bool SKY_DOUBLE = false>
+// OPTS: the SB_* options, by name (DEFER_ENERGY, REFRACT, SKY_DOUBLE are their bits); SINK is deduced from `sink`.
+template <unsigned OPTS = 0u, class SINK = NoSink>
 __device__ __forceinline__ int shade_bounce(const CrtDevScene& S, const Closest& c, PathState& ps, int bounce, float lightY, float lightZ,
                                             float* ndlOut = nullptr, const SINK* sink = nullptr)
 {
+    static_assert((OPTS & ~SB_ALL) == 0u, "unknown shading option");
+    constexpr bool DEFER_ENERGY = has_opt(OPTS, SB_DEFER_ENERGY), REFRACT = has_opt(OPTS, SB_REFRACT), SKY_DOUBLE = has_opt(OPTS, SB_SKY_DOUBLE);
     constexpr bool kSink = !std::is_same<SINK, NoSink>::value;
     const float UcharToFloat01 = 1.0f / 255.0f;
     if (c.distance > 99998.0f) {

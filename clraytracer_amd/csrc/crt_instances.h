@@ -198,7 +198,7 @@ void recompute_scene_limit()
     g.cullOriginLimit = lo;
 }
 
-// Instance tree for scenes with many instances (closest_hit<..., TLAS>): median-split binary tree over the cullable
+// Instance tree for scenes with many instances (closest_hit<TR_TLAS>): median-split binary tree over the cullable
 // instances' spheres, node sphere = centre and half diagonal of the box around its children's spheres. Instances
 // that are never culled go to a separate ascending list.
 // REFIT: the same partition, boxes bottom-up (children are numbered after their parent) -- the spheres a rebuild with this partition would give.

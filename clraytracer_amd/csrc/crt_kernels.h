@@ -288,7 +288,7 @@ __device__ __forceinline__ void add_tile_cost(const CrtFrame& F, int costSlot, u
 }
 
 // STAMP (diagnostic build only, CRT_RENDER_STAMPS): every wave records start/end s_memrealtime (100 MHz), its s_memtime cycle
-// count, XCC/HW ids and its wave-level step counts (closest_hit's ITERS) into 8 words of a buffer nothing else reads
+// count, XCC/HW ids and its wave-level step counts (closest_hit's TR_ITERS) into 8 words of a buffer nothing else reads
 // (tools/wave_timeline.py). Every lane of the wave must call write_wave_stamp.
 struct WaveStampStart { unsigned long long rt, c; };
 __device__ __forceinline__ WaveStampStart wave_stamp_start() { return { __builtin_amdgcn_s_memrealtime(), __builtin_amdgcn_s_memtime() }; }
@@ -381,15 +381,11 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
 {
     constexpr bool SSAA = CASE == CRT_TRACE_SSAA, GBUFFER = CASE == CRT_TRACE_GBUFFER;
     constexpr int kParkNdl = TLAS ? CRT_TLAS_PARK : 0;
-    constexpr bool kStage = !COUNT && !STAMP && !TLAS && !STK::kTop;      // staged_candidate_mask (crt_device.h)
-    // the reciprocals as divisions (crt_device.h: recip): the counted launches, and the one G-buffer kernel that sits at its 64 VGPRs so
-    // tightly that the short form's branch costs it 8 spilled registers (shadow rays + instance tree without refraction)
-    constexpr bool kDivide = COUNT || (GBUFFER && SHADOW && TLAS && !REFRACT);
-    // the skybox index in its double form alone (crt_device.h: sample_skybox_guarded): the counted launches, and every uncounted instantiation whose
-    // row of the kernel-resource ledger the second out-of-line function would move -- the G-buffer kernels with shadow rays and an
-    // instance tree or refraction (<shadow, tree, no refraction> spills 8 registers to 32 B of scratch, the other two move an SGPR or an SGPR spill)
-    // and the shadow-ray kernels without tree and refraction, plain and supersampled (SGPR spills)
-    constexpr bool kSkyDouble = COUNT || (GBUFFER && SHADOW && (TLAS || REFRACT)) || (!GBUFFER && SHADOW && !TLAS && !REFRACT);
+    // what both traversals share, the primary one's own options, and the shading's (division, double-only sky index, staged cull: crt_device.h, policy)
+    constexpr unsigned kRay = opt_if(COUNT, TR_COUNT) | opt_if(TLAS, TR_TLAS) | opt_if(policy::trace_divides(COUNT, GBUFFER, SHADOW, TLAS, REFRACT), TR_DIVIDE);
+    constexpr unsigned kPrimary = kRay | opt_if(STAMP, TR_ITERS) | opt_if(policy::trace_stages_cull(COUNT, STAMP, TLAS, STK::kTop), TR_STAGE);
+    constexpr unsigned kShade = opt_if(SHADOW, SB_DEFER_ENERGY) | opt_if(REFRACT, SB_REFRACT)
+                              | opt_if(policy::trace_sky_double(COUNT, GBUFFER, SHADOW, TLAS, REFRACT), SB_SKY_DOUBLE);
     LaneCounters lc; zero_counters(lc);
     WaveStampStart t0 = { 0, 0 };
     if (STAMP) t0 = wave_stamp_start();
@@ -405,15 +401,14 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
             // would otherwise spill to scratch); the shadow ray's n.l uses the same slot later, when the energy is dead
             // (GBUFFER: the same -- the plane stores' addresses take the register the plain kernel keeps the energy in)
             if (SHADOW || GBUFFER) stack.park(kParkNdl, __float_as_uint(ps.energy));
-            // kStage: at the camera bounce every ray of the wave starts at F.camPos -- the cull's origin-only terms are computed once per wave
-            Closest c = closest_hit<COUNT, STAMP, false, TLAS, false, kStage, kDivide>(S, ps.o, ps.d, stack, lc, 99999.0f, false, bounce == 0);
+            Closest c = closest_hit<kPrimary>(S, ps.o, ps.d, stack, lc, 99999.0f, false, bounce == 0);
             if (SHADOW || GBUFFER) ps.energy = __uint_as_float(stack.parked(kParkNdl));
             float ndl = 0.0f;
             int cont;
-            if constexpr (!GBUFFER) cont = shade_bounce<SHADOW, REFRACT, NoSink, kSkyDouble>(S, c, ps, bounce, F.lightY, F.lightZ, &ndl);
+            if constexpr (!GBUFFER) cont = shade_bounce<kShade>(S, c, ps, bounce, F.lightY, F.lightZ, &ndl);
             else {
                 const GBufferSink sink = { gb, &F, b, lane };
-                cont = shade_bounce<SHADOW, REFRACT, GBufferSink, kSkyDouble>(S, c, ps, bounce, F.lightY, F.lightZ, &ndl, &sink);
+                cont = shade_bounce<kShade>(S, c, ps, bounce, F.lightY, F.lightZ, &ndl, &sink);
             }
             if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
             if (!cont) break;
@@ -426,7 +421,7 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
                     if (ndl > 0.0f) {
                         if (COUNT) { lc.rays++; lc.shadowRays++; }
                         stack.park(kParkNdl, __float_as_uint(ndl));
-                        const Closest sc = closest_hit<COUNT, false, true, TLAS, false, false, kDivide>(S, ps.o, neg3(mk3(0.0f, F.lightY, F.lightZ)), stack, lc);
+                        const Closest sc = closest_hit<kRay | TR_ANYHIT>(S, ps.o, neg3(mk3(0.0f, F.lightY, F.lightZ)), stack, lc);
                         if (sc.anyHit) { shadow = 0.0f; if (COUNT) lc.shadowHits++; }
                         ndl = __uint_as_float(stack.parked(kParkNdl));
                     }
@@ -542,8 +537,8 @@ __global__ __launch_bounds__(CRT_BLOCK, COUNT ? CRT_WAVES_PER_SIMD_COUNT : CRT_W
     if (active) {
         ps.d = raygen_dir(F, px, py);
         if (COUNT) { lc.rays++; lc.primary++; }
-        Closest c = closest_hit<COUNT>(S, ps.o, ps.d, stack, lc);
-        cont = shade_bounce<false, false, NoSink, COUNT>(S, c, ps, 0, F.lightY, F.lightZ) != 0;
+        Closest c = closest_hit<opt_if(COUNT, TR_COUNT) | opt_if(policy::primary_divides(COUNT), TR_DIVIDE)>(S, ps.o, ps.d, stack, lc);
+        cont = shade_bounce<opt_if(policy::wavefront_sky_double(COUNT), SB_SKY_DOUBLE)>(S, c, ps, 0, F.lightY, F.lightZ) != 0;
         if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
         out[(size_t)py * (size_t)F.width + (size_t)px] = make_float4(ps.result.x, ps.result.y, ps.result.z, 1.0f);
     }
@@ -600,9 +595,8 @@ __global__ __launch_bounds__(CRT_BLOCK, COUNT ? CRT_WAVES_PER_SIMD_COUNT : CRT_W
         const float4 partial = out[r.pixel];
         PathState ps = unpack_bounce(r, mk3(partial.x, partial.y, partial.z));
         if (COUNT) { lc.rays++; lc.secondary++; }
-        // (the reciprocals as divisions, crt_device.h: recip -- this opt-in form's kernel is recorded register for register, and stays that)
-        Closest c = closest_hit<COUNT, false, false, false, false, false, true>(S, ps.o, ps.d, stack, lc);
-        const bool cont = shade_bounce<false, false, NoSink, COUNT>(S, c, ps, 1, F.lightY, F.lightZ) != 0;
+        Closest c = closest_hit<opt_if(COUNT, TR_COUNT) | opt_if(policy::kBounceDivides, TR_DIVIDE)>(S, ps.o, ps.d, stack, lc);
+        const bool cont = shade_bounce<opt_if(policy::wavefront_sky_double(COUNT), SB_SKY_DOUBLE)>(S, c, ps, 1, F.lightY, F.lightZ) != 0;
         if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
         out[r.pixel] = make_float4(ps.result.x, ps.result.y, ps.result.z, 1.0f);
     }
@@ -739,7 +733,7 @@ __global__ __launch_bounds__(CRT_BLOCK, CRT_WAVES_PER_SIMD_COUNT) void crt_query
         v3 o = mk3(origins[3 * k], origins[3 * k + 1], origins[3 * k + 2]);
         v3 d = mk3(dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]);
         lc.rays++;
-        Closest c = closest_hit<true, false, false, TLAS>(S, o, d, stack, lc);
+        Closest c = closest_hit<TR_COUNT | opt_if(TLAS, TR_TLAS) | opt_if(policy::kQueryDivides, TR_DIVIDE)>(S, o, d, stack, lc);
         CrtRayHit h;
         if (c.anyHit) { h.t = c.hit.t; h.u = c.hit.u; h.v = c.hit.v; h.triIndex = c.hit.tri; h.instance = c.hitInstance; lc.hits++; }
         else { h.t = c.distance; h.u = 0.0f; h.v = 0.0f; h.triIndex = 0; h.instance = -1; lc.misses++; }

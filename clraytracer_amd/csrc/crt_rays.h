@@ -23,11 +23,12 @@ template <bool ANYHIT, bool TLAS> __global__ void crt_rays_kernel(CrtDevScene S0
 // The kernel's text, written once: crt_rays_kernel (crt_rays.hip) and crt_rays_inclusive_kernel (crt_inclusive.hip, the box test of
 // CRT_RAYS_INCLUSIVE) are one-line wrappers that own the LDS stack and pass it in. (Arguments by value, as the kernels take them: by reference the same
 // text allocates registers differently.)
-//   INCLUSIVE  closest_hit's: intersect_aabb<true> for every box test; nothing else differs.
+//   INCLUSIVE  closest_hit's TR_INCLUSIVE: intersect_aabb<true> for every box test; nothing else differs.
 template <bool ANYHIT, bool TLAS, bool INCLUSIVE>
 __device__ __forceinline__ void crt_rays_body(CrtDevScene S0, CrtRaysArgs A, crt_lds_u32_ptr s_stack)
 {
-    LaneCounters lc = {};                        // COUNT = false: never read
+    constexpr unsigned kRay = opt_if(ANYHIT, TR_ANYHIT) | opt_if(TLAS, TR_TLAS) | opt_if(INCLUSIVE, TR_INCLUSIVE) | opt_if(policy::kDeviceQueryDivides, TR_DIVIDE);
+    LaneCounters lc = {};                        // no TR_COUNT: never read
     for (;;) {
         uint32_t chunk;
         if (claim_chunk(A.q, A.chunks, chunk)) break;
@@ -41,7 +42,7 @@ __device__ __forceinline__ void crt_rays_body(CrtDevScene S0, CrtRaysArgs A, crt
             if (A.tmax) best0 = query_bound(A.tmax[k]);
             CrtDevScene S = S0;
             const bool noCull = cull_decision(A.q, o, lane, S);
-            const Closest c = closest_hit<false, false, ANYHIT, TLAS, INCLUSIVE>(S, o, d, stack, lc, best0, noCull);
+            const Closest c = closest_hit<kRay>(S, o, d, stack, lc, best0, noCull);
             // the ray's index once more, behind the traversal (as lane_pixel_again does for the pixel)
             uint32_t chunk2 = chunk, lane2;
             chunk_lane_again(chunk2, lane2);

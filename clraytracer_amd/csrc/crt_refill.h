@@ -65,7 +65,8 @@ void crt_trace_refill_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out
         uint32_t cursor = 0;                                 // next pixel of the block nobody has taken yet (wave-uniform)
         PathState ps = camera_path(F, mk3(0.f, 0.f, 0.f));
         Closest c = no_hit();
-        Traversal<COUNT> T; T.reset();
+        constexpr unsigned kTrip = opt_if(COUNT, TR_COUNT) | opt_if(STAMP, TR_ITERS) | opt_if(policy::refill_block_divides(COUNT), TR_DIVIDE);
+        Traversal<kTrip> T; T.reset();
         unsigned long long cand = 0;
         bool havePath = false;
         const uint32_t cnt = S.numInstances < 64u ? S.numInstances : 64u;
@@ -88,7 +89,7 @@ void crt_trace_refill_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out
                     const uint32_t st = stack.parked(0);
                     const int bounce = (int)(st >> 31);
                     ps.energy = __uint_as_float(stack.parked(1));      // (waits in LDS through the traversals, as in the megakernel's SHADOW instantiations)
-                    const int cont = shade_bounce<false, false, NoSink, COUNT>(S, c, ps, bounce, F.lightY, F.lightZ);
+                    const int cont = shade_bounce<opt_if(policy::refill_sky_double(COUNT), SB_SKY_DOUBLE)>(S, c, ps, bounce, F.lightY, F.lightZ);
                     c = no_hit();
                     if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
                     if (cont != 0 && bounce == 0) {           // kernel_main.cl:187: the second iteration of the bounce loop
@@ -126,7 +127,7 @@ void crt_trace_refill_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out
                         }
                     }
                 }
-                if (newRay) cand = candidate_mask<COUNT>(S, ps.o, ps.d, 0u, cnt, lc);
+                if (newRay) cand = candidate_mask<opt_if(COUNT, CM_COUNT)>(S, ps.o, ps.d, 0u, cnt, lc);
             }
             // one traversal trip (closest_hit's: enter -> inner -> leaf -> inner) for the lanes that have something to traverse
             if (havePath && !T.active && cand != 0) {
@@ -135,7 +136,7 @@ void crt_trace_refill_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out
                 cand &= cand - 1;
                 T.enter(S, k, ps.o, ps.d, c.distance, lc);
             }
-            trip_steps<COUNT, STAMP, false>(S, stack, T, c, lc, false);
+            trip_steps<kTrip>(S, stack, T, c, lc, false);
         }
     }
     if (valid) finish_block_pixels(F, tx0, tileRow, CRT_REFILL_PIXELS, out);   // upstream's per-pixel stages behind Trace
@@ -182,6 +183,8 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
     const unsigned long long tc0 = tile_cost_start(F);
     int tx0 = 0, tileRow = 0, costSlot = -1;
     const bool valid = refill_block(F, blockIdx.x, tx0, tileRow, costSlot, CRT_BLOCK_TILES);
+    constexpr unsigned kRay = opt_if(COUNT, TR_COUNT) | opt_if(STAMP, TR_ITERS) | opt_if(policy::refill_block_divides(COUNT), TR_DIVIDE);
+    constexpr unsigned kShade = opt_if(policy::kBlockSkyDouble, SB_SKY_DOUBLE);
     if (valid) {
         const uint32_t cnt = S.numInstances < 64u ? S.numInstances : 64u;
         CrtBounceRay* __restrict__ q = queue + (size_t)costSlot * CRT_BLOCK_PIXELS;
@@ -196,11 +199,11 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
             if (inFrame) {
                 PathState ps = camera_path(F, raygen_dir(F, px, py));
                 LaneCounters none;
-                const unsigned long long cand = candidate_mask<false>(S, ps.o, ps.d, 0u, cnt, none);
+                const unsigned long long cand = candidate_mask(S, ps.o, ps.d, 0u, cnt, none);
                 if (cand == 0 && S.numInstances <= 64u) {
                     // no instance can be hit: closest_hit would return the initial miss (kernel_main.cl:219-224: skybox, break)
                     if (COUNT) { lc.rays++; lc.primary++; lc.misses++; count_culled(lc, cnt); }
-                    (void)shade_bounce<false, false, NoSink, true>(S, no_hit(), ps, 0, F.lightY, F.lightZ);
+                    (void)shade_bounce<kShade>(S, no_hit(), ps, 0, F.lightY, F.lightZ);
                     out[(size_t)py * (size_t)F.width + (size_t)px] = make_float4(ps.result.x, ps.result.y, ps.result.z, 1.0f);
                 } else listed = true;
             }
@@ -221,8 +224,8 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
                     ps.d = raygen_dir(F, px, py);
                 }
                 if (COUNT) { lc.rays++; lc.primary++; }
-                const Closest c = closest_hit<COUNT, STAMP>(S, ps.o, ps.d, stack, lc);
-                cont = shade_bounce<false, false, NoSink, true>(S, c, ps, 0, F.lightY, F.lightZ) != 0;
+                const Closest c = closest_hit<kRay>(S, ps.o, ps.d, stack, lc);
+                cont = shade_bounce<kShade>(S, c, ps, 0, F.lightY, F.lightZ) != 0;
                 if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
             }
             uint32_t base2 = base, lane2 = lane;
@@ -249,14 +252,14 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
             if (base + lane < nQueue) {
                 PathState ps = unpack_bounce(q[base + lane]);
                 if (COUNT) { lc.rays++; lc.secondary++; }
-                const Closest c = closest_hit<COUNT, STAMP>(S, ps.o, ps.d, stack, lc);
+                const Closest c = closest_hit<kRay>(S, ps.o, ps.d, stack, lc);
                 // the partial radiance and the pixel index are fetched behind the traversal (nothing kept alive through it)
                 uint32_t base2 = base, lane2 = lane;
                 asm volatile("" : "+s"(base2), "+v"(lane2));
                 const uint32_t pixel = q[base2 + lane2].pixel;
                 const float4 partial = out[pixel];
                 ps.result = mk3(partial.x, partial.y, partial.z);
-                const bool cont = shade_bounce<false, false, NoSink, true>(S, c, ps, 1, F.lightY, F.lightZ) != 0;
+                const bool cont = shade_bounce<kShade>(S, c, ps, 1, F.lightY, F.lightZ) != 0;
                 if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
                 out[pixel] = make_float4(ps.result.x, ps.result.y, ps.result.z, 1.0f);
             }

@@ -74,7 +74,9 @@ template <int WHAT, bool TLAS>
 __device__ __forceinline__ void crt_shade_body(CrtDevScene S0, CrtShadeArgs A, crt_lds_u32_ptr s_stack)
 {
     constexpr bool kRadiance = (WHAT & CRT_SHADE_RADIANCE) != 0, kSurface = (WHAT & CRT_SHADE_SURFACE) != 0;
-    LaneCounters lc = {};                        // COUNT = false: never read
+    constexpr unsigned kRay = opt_if(TLAS, TR_TLAS) | opt_if(policy::kDeviceQueryDivides, TR_DIVIDE) | opt_if(policy::kShadeStagesCull, TR_STAGE);
+    constexpr unsigned kShade = opt_if(policy::kShadeSkyDouble, SB_SKY_DOUBLE);
+    LaneCounters lc = {};                        // no TR_COUNT: never read
     for (;;) {
         uint32_t chunk;
         if (claim_chunk(A.q, A.chunks, chunk)) break;
@@ -93,8 +95,7 @@ __device__ __forceinline__ void crt_shade_body(CrtDevScene S0, CrtShadeArgs A, c
             CrtDevScene S = S0;
             const bool noCull = cull_decision(A.q, ps.o, lane, S);
             for (int bounce = 0;; ++bounce) {
-                // kStage = false: the origins are not shared
-                Closest c = closest_hit<false, false, false, TLAS, false, false>(S, ps.o, ps.d, stack, lc, bound, noCull);
+                Closest c = closest_hit<kRay>(S, ps.o, ps.d, stack, lc, bound, noCull);
                 bound = 99999.0f;                // the given ray's alone: the bounce ray is unbounded
                 if (!c.anyHit) c = no_hit();
                 // (the record's row of ids is put together behind the traversal: left to the compiler, <SURFACE, true> carries it through
@@ -114,10 +115,10 @@ __device__ __forceinline__ void crt_shade_body(CrtDevScene S0, CrtShadeArgs A, c
                     ps.result = mk3(partial.x, partial.y, partial.z); ps.energy = partial.w;
                 }
                 int cont;
-                if constexpr (!kSurface) cont = shade_bounce(S, c, ps, bounce, A.lightY, A.lightZ);
+                if constexpr (!kSurface) cont = shade_bounce<kShade>(S, c, ps, bounce, A.lightY, A.lightZ);
                 else {
                     const SurfaceSink sink = { A.surface, chunk };
-                    cont = shade_bounce<false, false, SurfaceSink>(S, c, ps, bounce, A.lightY, A.lightZ, nullptr, &sink);
+                    cont = shade_bounce<kShade>(S, c, ps, bounce, A.lightY, A.lightZ, nullptr, &sink);
                 }
                 if constexpr (!kRadiance) break;
                 const bool last = !cont || bounce == 1;

@@ -417,7 +417,8 @@ enum : unsigned {               // closest_hit, trip_steps, Traversal
     TR_INCLUSIVE = 1u << 4,     // intersect_aabb's inclusive rule for every box test (the device queries only)
     TR_STAGE = 1u << 5,         // the camera bounce's cull terms once per wave (staged_candidate_mask)
     TR_DIVIDE = 1u << 6,        // the reciprocals as divisions (recip)
-    TR_ALL = (1u << 7) - 1u
+    TR_WAVE_CULL = 1u << 7,     // ... and one test per instance and wave against the tile's ray cone before the per-lane loop (cone_rejects)
+    TR_ALL = (1u << 8) - 1u
 };
 enum : unsigned { CM_COUNT = 1u << 0, CM_DEFER_COUNT = 1u << 1, CM_ALL = (1u << 2) - 1u };                        // candidate_mask
 enum : unsigned { SB_DEFER_ENERGY = 1u << 0, SB_REFRACT = 1u << 1, SB_SKY_DOUBLE = 1u << 2, SB_ALL = (1u << 3) - 1u };   // shade_bounce
@@ -475,6 +476,15 @@ constexpr bool kShadeSkyDouble = false;
 constexpr bool trace_stages_cull(bool COUNT, bool STAMP, bool TLAS, bool TOP) { return !COUNT && !STAMP && !TLAS && !TOP; }
 // crt_shade_kernel: the origins of a batch are not shared
 constexpr bool kShadeStagesCull = false;
+
+// ---- who rejects instances per wave against the tile's ray cone (cone_rejects, before the staged per-lane loop) ----
+// trace_body: the kernels of trace_stages_cull, except the two whose row of the ledger the wave test would move -- the G-buffer kernel with shadow
+// rays and refraction (one more SGPR: 77 -> 78) and the plain kernel with shadow rays and without refraction (SGPR spills 53 -> 47). They keep
+// the staged loop over all instances.
+constexpr bool trace_wave_culls(bool STAGES, bool PLAIN, bool GBUFFER, bool SHADOW, bool REFRACT)
+{
+    return STAGES && !(GBUFFER && SHADOW && REFRACT) && !(PLAIN && SHADOW && !REFRACT);
+}
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -733,12 +743,94 @@ __device__ __forceinline__ unsigned long long candidate_mask(const CrtDevScene& 
 // A lane's own stack entries lie in these rows, so every lane of the wave has finished reading before any lane pushes: the loop below
 // is wave-uniform and the trip loop starts behind it; the next 64-chunk restages after the trip loop has ended for the whole wave
 // (every lane's stack empty).
+// ------------------------------------------------------------------------------------------------
+// The wave test (TR_WAVE_CULL, policy::trace_wave_culls): one test per instance and WAVE in front of the per-lane loop. The 64 primary rays
+// of a tile share their origin o and lie in a narrow cone; an instance whose grown sphere lies outside that cone is rejected for every lane
+// at once, and the per-lane loop runs over the survivors only (multi-1M, 1920x1080: 2.06 of 16 per tile, profiles/wave_cull_counts.txt).
+// This clears bits candidate_mask would keep, which is legitimate through the lemma below -- it continues the derivation above sphere_culls.
+//
+// (6) Lemma. If cone_rejects returns true for instance k, then for EVERY lane of the wave, with its fp32 d and the shared o, in exact arithmetic
+//         |o + t d - fl(c)|^2 > 1.02 w^2 + 2.8e-6 x^2   for all t > 0        (x = |fl(c) - o|)
+//     -- the conclusion of (2). (3)-(5) use nothing else of the predicate, so the cull range O_i, the all-never table and the never-culled
+//     instances (w < 0: not rejected here either) hold as they stand: a rejected instance is one the traversal would have left at its root.
+// (6a) Geometry. N^2 = 1.02 w^2 + 2.8e-6 x^2, oc = fl(c) - o, a = the direction of lane 0, and the exact angles theta >= angle(d, a) for every lane,
+//     phi = angle(oc, a), psi = asin(N / x) (N < x below). If phi > theta + psi then angle(d, oc) >= phi - angle(d, a) > psi for every lane (the
+//     triangle inequality on the sphere; theta + psi < pi because theta < pi/3, psi <= pi/2). For angle(d, oc) < pi/2 the distance from fl(c)
+//     to the line is x sin(angle(d, oc)) > x sin psi = N; for angle(d, oc) >= pi/2 the closest point of the ray t > 0 is its origin, at x > N.
+// (6b) The computed test implies phi > theta + psi. The test is  cphi < ct cpsi - st spsi - m2  with ct, st, spsi, cpsi >= 0. The right side
+//     is decreasing in st and spsi and increasing in ct and cpsi, so it is enough that each computed value errs to its safe side (or by
+//     an amount m2 absorbs); cos is decreasing on [0, pi]. u = 2^-24; v_rsq_f32 and v_sqrt_f32 are good to 1 ulp (<= 2u relative).
+//       ct   = min over the lanes of fl(d.a) rsq(dd), times rsq(aa), minus m0. fl(d.a): 3u |d||a|; dd, aa: 3u relative, each rsq then 3.5u;
+//              two products and the subtraction 3u: ct + m0 is within 13u = 7.7e-7 of cos theta, so with m0 = 4e-6 (5 x that), ct <= cos theta - 3.2e-6.
+//              The guard admits the wave only when every lane has 0.999 <= dd <= 1.001 and d.a > 0 as computed (a NaN fails each compare; a lane that
+//              fails contributes 0 to the minimum) and ct >= 0.5: the unsigned minimum of the bit patterns is the minimum of non-negative floats.
+//       st   = sqrt(max(0, 1 - ct ct)): 1 - ct^2 >= sin^2 theta + 2 ct 3.2e-6 >= sin^2 theta + 3.2e-6 (ct >= 0.5); the roundings of the square, the
+//              subtraction and the root take at most 3.6e-7 of that (9 x to spare): st >= sin theta.
+//       spsi = sqrt(R2) rsq(oc2), R2 = r2 (1 + m1), r2 candidate_mask's: r2 >= N^2 (1 + 9e-5) by (2)'s own bounds (1.0201 against 1.02, 4e-6 against
+//              2.8e-6), which is NOT counted here. Root 2u, rsq 3.5u, oc against x 1u, the product and R2's 1.5u: 8u, against sqrt(1 + m1) = 1 + 66u for
+//              m1 = 8e-6 (8 x): spsi >= N / x = sin psi. The test requires oc2 > R2 as computed, hence x^2 (1 + 5u) > N^2 (1 + 9e-5): x > N; and
+//              1e-30 < oc2 < 1e30 keeps both special functions away from denormals and overflow.
+//       cpsi = sqrt(max(0, 1 - spsi spsi)) <= cos psi + 2.6u: for spsi^2 >= 0.01 the surplus of spsi outweighs the roundings (cpsi <= cos psi outright up
+//              to the root's 2u), below that cpsi > 0.99 and the roundings move it by 0.6u + 2u.
+//       cphi = (fl(oc.a) rsq(oc2)) rsq(aa): 3u for the dot product, 2u for oc's own rounding, 3.5u for each rsq, 2u for the products: 14u.
+//       The right side's own products and subtractions: 4u. Together 14u + 2.6u + 4u = 21u = 1.25e-6 against m2 = 8e-6 (6 x).
+//     So every margin has more than a factor of 4 to spare. Any NaN (a NaN w, camera or centre) makes a compare false: the instance survives.
+// ------------------------------------------------------------------------------------------------
+#ifdef CRT_NO_WAVE_CULL
+#define CRT_WAVE_CULLS(WAVE) false        // A/B builds: the staged loop over all instances everywhere
+#else
+#define CRT_WAVE_CULLS(WAVE) (WAVE)
+#endif
+#define CRT_WAVE_CULL_MIN 8u              // fewest instances of a scene whose full waves take the wave test (staged_candidate_mask says why)
+#define CRT_CONE_M0 4e-6f
+#define CRT_CONE_M1 8e-6f
+#define CRT_CONE_M2 8e-6f
+// wave-uniform: the axis (lane 0's direction), rsq(a.a), cos and sin of the half-angle. ct >= 0.5 is the guard.
+struct WaveCone { v3 a; float ra, ct, st; };
+__device__ __forceinline__ bool cone_admits(const WaveCone& c) { return c.ct >= 0.5f; }
+// min(v, v of another lane of the row of 16) as DPP moves: CTRL = quad_perm [1,0,3,2] 0xB1, [2,3,0,1] 0x4E, row_half_mirror 0x141, row_mirror 0x140
+template <int CTRL> __device__ __forceinline__ uint32_t row_min_step(uint32_t v)
+{
+    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false);
+    return o < v ? o : v;
+}
+// The cone of a FULL wave (every lane active: a DPP move never reads an inactive lane's register); d, dd = d.d per lane
+__device__ __forceinline__ WaveCone wave_cone(v3 d, float dd)
+{
+    WaveCone c;
+    c.a = mk3(__uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(d.x))),
+              __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(d.y))),
+              __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(d.z))));
+    c.ra = __builtin_amdgcn_rsqf(__uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(dd))));
+    const float q = dot3(d, c.a);
+    const bool admitted = (dd >= 0.999f) & (dd <= 1.001f) & (q > 0.0f);
+    uint32_t m = admitted ? __float_as_uint(q * __builtin_amdgcn_rsqf(dd)) : 0u;
+    m = row_min_step<0xB1>(m); m = row_min_step<0x4E>(m); m = row_min_step<0x141>(m); m = row_min_step<0x140>(m);
+    const uint32_t m0 = (uint32_t)__builtin_amdgcn_readlane((int)m, 0), m1 = (uint32_t)__builtin_amdgcn_readlane((int)m, 16),
+                   m2 = (uint32_t)__builtin_amdgcn_readlane((int)m, 32), m3 = (uint32_t)__builtin_amdgcn_readlane((int)m, 48);
+    const uint32_t m01 = m0 < m1 ? m0 : m1, m23 = m2 < m3 ? m2 : m3;
+    c.ct = __uint_as_float(m01 < m23 ? m01 : m23) * c.ra - CRT_CONE_M0;
+    c.st = __builtin_amdgcn_sqrtf(fmaxf(0.0f, 1.0f - c.ct * c.ct));
+    return c;
+}
+// The wave test of one instance, from the terms its staging lane holds (oc, oc2, r2, `w >= 0`): (6) above
+__device__ __forceinline__ bool cone_rejects(const WaveCone& c, v3 oc, float oc2, float r2, bool cullable)
+{
+    const float R2 = r2 * (1.0f + CRT_CONE_M1);
+    const float rs = __builtin_amdgcn_rsqf(oc2);
+    const float cphi = (dot3(oc, c.a) * rs) * c.ra;
+    const float spsi = __builtin_amdgcn_sqrtf(R2) * rs;
+    const float cpsi = __builtin_amdgcn_sqrtf(fmaxf(0.0f, 1.0f - spsi * spsi));
+    const float rhs = (c.ct * cpsi - c.st * spsi) - CRT_CONE_M2;
+    return cullable & (oc2 > R2) & (oc2 > 1e-30f) & (oc2 < 1e30f) & (cphi < rhs);
+}
+
 typedef uint32_t crt_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t crt_u32x2 __attribute__((ext_vector_type(2)));
 typedef crt_u32x4 __attribute__((address_space(3)))* crt_lds_u32x4_ptr;
 typedef crt_u32x2 __attribute__((address_space(3)))* crt_lds_u32x2_ptr;
 #define CRT_STAGE_ROWS 6
-template <class STK>
+template <bool WAVE, class STK>
 __device__ __forceinline__ unsigned long long staged_candidate_mask(const CrtDevScene& S, v3 o, v3 d, uint32_t base, uint32_t cnt, const STK& stack)
 {
     static_assert(STK::kLds >= CRT_STAGE_ROWS && CRT_BLOCK == 64, "the staged cull terms take six stack rows of a one-wave workgroup");
@@ -779,9 +871,44 @@ __device__ __forceinline__ unsigned long long staged_candidate_mask(const CrtDev
     };
     // the mask in two 32-bit halves: one select and one OR per instance instead of two of each
     uint32_t lo = 0, hi = 0;
-    const uint32_t nLo = cnt < 32u ? cnt : 32u;
-    for (uint32_t k = 0; k < nLo; ++k) lo |= culls(k) ? 0u : 1u << k;
-    for (uint32_t k = 32; k < cnt; ++k) hi |= culls(k) ? 0u : 1u << (k - 32u);
+    if constexpr (CRT_WAVE_CULLS(WAVE)) {
+        // The wave test: in a full wave (rank == lane, one staging pass) lane k tests instance k on the record it staged -- `thr == 0` is
+        // `w >= 0 && oc2 > r2`, and r2' = +inf fails `oc2 > R2`. Every other wave -- a partial tile, a quadrant wave -- rejects nothing.
+        // (Behind the barrier, not inside the staging loop: there its operands cost a VGPR spill in every kernel.)
+        // (Opaque copies of the direction: the cone does not change from one 64-chunk of instances to the next, and hoisted out of closest_hit's
+        // chunk loop it lives through the traversal -- a spilled VGPR and two more spilled SGPRs in every kernel.)
+        // Scenes of CRT_WAVE_CULL_MIN ... 64 instances only. Below: the cone and the test cost about 80 VALU instructions per wave
+        // (profiles/wave_cull_summary.md: 144 saved with 14 of 16 rejected at 16 each), what five rejected instances save -- a scene of two
+        // instances lost 1 % with the test. Above: the scene reaches this loop only as the fallback of the instance tree (CRT_TLAS=0, a lane whose
+        // candidates do not fit its list); it takes no wave test and its loops below run over all `cnt` bits. (An opaque copy: the compare's
+        // result, hoisted out of the bounce loop, is two more spilled SGPRs in every kernel.)
+        bool reject = false;
+        const uint32_t n = cnt;
+        uint32_t all = S.numInstances;
+        asm volatile("" : "+s"(all));
+        if (act == ~0ull && all - CRT_WAVE_CULL_MIN <= 64u - CRT_WAVE_CULL_MIN) {
+            v3 dc = d; float ddc = dd; uint32_t lane = rank;
+            asm volatile("" : "+v"(dc.x), "+v"(dc.y), "+v"(dc.z), "+v"(ddc), "+v"(lane));
+            const WaveCone cone = wave_cone(dc, ddc);
+            if (cone_admits(cone) && lane < n) {
+                const crt_u32x4 a = rowA[lane]; const crt_u32x2 t = rowB[lane];
+                reject = cone_rejects(cone, mk3(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z)), __uint_as_float(a.w), __uint_as_float(t.x), t.y == 0u);
+            }
+        }
+        // `touch`: the instances the wave test leaves. The loops run over its set bits only (a scalar find-first-set per survivor); a bit
+        // outside it stays clear in every lane's mask
+        const unsigned long long touch = (n == 64u ? ~0ull : (1ull << n) - 1ull) & ~__ballot(reject);
+        // (the halves as opaque scalars: `(touch >> 32) != 0` is otherwise compiled as a 64-bit compare, which only the vector unit has -- against
+        // a constant in a VGPR pair that then lives through the whole kernel)
+        uint32_t touchLo = (uint32_t)touch, touchHi = (uint32_t)(touch >> 32);
+        asm volatile("" : "+s"(touchLo), "+s"(touchHi));
+        for (uint32_t m = touchLo; m != 0u; m &= m - 1u) { const uint32_t k = (uint32_t)__builtin_ctz(m); lo |= culls(k) ? 0u : 1u << k; }
+        for (uint32_t m = touchHi; m != 0u; m &= m - 1u) { const uint32_t k = (uint32_t)__builtin_ctz(m); hi |= culls(k + 32u) ? 0u : 1u << k; }
+    } else {
+        const uint32_t nLo = cnt < 32u ? cnt : 32u;
+        for (uint32_t k = 0; k < nLo; ++k) lo |= culls(k) ? 0u : 1u << k;
+        for (uint32_t k = 32; k < cnt; ++k) hi |= culls(k) ? 0u : 1u << (k - 32u);
+    }
     const unsigned long long cand = ((unsigned long long)hi << 32) | lo;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -901,6 +1028,7 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
                    STAGE = has_opt(OPTS, TR_STAGE);
     static_assert((OPTS & ~TR_ALL) == 0u, "unknown traversal option");
     static_assert(!STAGE || (!COUNT && !ITERS && !ANYHIT && !TLAS && !STK::kTop), "staged cull terms: uncounted closest-hit traversals of one-wave workgroups");
+    static_assert(STAGE || !has_opt(OPTS, TR_WAVE_CULL), "the wave test lives in the staged cull");
     Closest c = no_hit(best0);
     Traversal<OPTS> T; T.reset();
 
@@ -940,7 +1068,7 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
     for (uint32_t base = 0; base < S.numInstances; base += 64) {
         const uint32_t cnt = (S.numInstances - base) < 64u ? (S.numInstances - base) : 64u;
         unsigned long long cand;
-        if constexpr (STAGE) cand = sharedOrigin ? staged_candidate_mask(S, o, d, base, cnt, stack) : candidate_mask(S, o, d, base, cnt, lc);
+        if constexpr (STAGE) cand = sharedOrigin ? staged_candidate_mask<has_opt(OPTS, TR_WAVE_CULL)>(S, o, d, base, cnt, stack) : candidate_mask(S, o, d, base, cnt, lc);
         else cand = candidate_mask<opt_if(COUNT, CM_COUNT) | opt_if(ANYHIT, CM_DEFER_COUNT)>(S, o, d, base, cnt, lc);
         // ANYHIT + COUNT: a culled instance is only "visited" (one pop, one inner visit upstream) if the ray gets that
         // far, so culled instances are counted when a later candidate is entered or the chunk ends without a hit

@@ -289,7 +289,7 @@ __device__ __forceinline__ float recip(float x)
     }
 }
 // the three of an instance entry under one decision: the largest and the smallest exponent stand for all three
-template <bool DIVIDE = false>
+template <bool DIVIDE = false, bool ONE_COMPARE = false>
 __device__ __forceinline__ v3 recip3(v3 d)
 {
     if constexpr (CRT_RECIP_DIVIDES(DIVIDE)) return mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
@@ -297,7 +297,10 @@ __device__ __forceinline__ v3 recip3(v3 d)
         const int ex = __builtin_amdgcn_frexp_expf(d.x), ey = __builtin_amdgcn_frexp_expf(d.y), ez = __builtin_amdgcn_frexp_expf(d.z);
         const int hi = max(max(ex, ey), ez), lo = min(min(ex, ey), ez);
         v3 r = mk3(recip_short(d.x), recip_short(d.y), recip_short(d.z));
-        if (__builtin_expect(__ballot(hi > 126 || lo < -125) != 0, 0)) r = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+        // ONE_COMPARE (root_pretest_misses): the same predicate as one compare against zero -- exponents are small integers, nothing wraps --
+        // where the two compares' constants, kept in SGPRs from the top of the kernel, are registers the caller does not have
+        if constexpr (ONE_COMPARE) { if (__builtin_expect(__ballot(max(hi - 126, -125 - lo) > 0) != 0, 0)) r = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z); }
+        else if (__builtin_expect(__ballot(hi > 126 || lo < -125) != 0, 0)) r = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
         return r;
     }
 }
@@ -418,7 +421,8 @@ enum : unsigned {               // closest_hit, trip_steps, Traversal
     TR_STAGE = 1u << 5,         // the camera bounce's cull terms once per wave (staged_candidate_mask)
     TR_DIVIDE = 1u << 6,        // the reciprocals as divisions (recip)
     TR_WAVE_CULL = 1u << 7,     // ... and one test per instance and wave against the tile's ray cone before the per-lane loop (cone_rejects)
-    TR_ALL = (1u << 8) - 1u
+    TR_ROOT_PRETEST = 1u << 8,  // ... and the exact root step per surviving instance and wave behind it (root_pretest_misses)
+    TR_ALL = (1u << 9) - 1u
 };
 enum : unsigned { CM_COUNT = 1u << 0, CM_DEFER_COUNT = 1u << 1, CM_ALL = (1u << 2) - 1u };                        // candidate_mask
 enum : unsigned { SB_DEFER_ENERGY = 1u << 0, SB_REFRACT = 1u << 1, SB_SKY_DOUBLE = 1u << 2, SB_ALL = (1u << 3) - 1u };   // shade_bounce
@@ -484,6 +488,15 @@ constexpr bool kShadeStagesCull = false;
 constexpr bool trace_wave_culls(bool STAGES, bool PLAIN, bool GBUFFER, bool SHADOW, bool REFRACT)
 {
     return STAGES && !(GBUFFER && SHADOW && REFRACT) && !(PLAIN && SHADOW && !REFRACT);
+}
+
+// ---- who takes the exact root step per wave for the camera bounce's surviving instances (root_pretest_misses, behind the staged per-lane loop) ----
+// trace_body: the kernels of trace_wave_culls (the pre-test runs over the wave test's survivors, in the waves that take the wave test), except the four
+// whose row of the ledger it would move -- the plain and the supersampled kernel with shadow rays and refraction (SGPR spills 53 -> 55 and 54 -> 56)
+// and the two G-buffer kernels without shadow rays (SGPR spills 50 -> 53). They keep the wave test alone.
+constexpr bool trace_root_pretests(bool WAVE_CULLS, bool GBUFFER, bool SHADOW, bool REFRACT)
+{
+    return WAVE_CULLS && !(SHADOW && REFRACT) && !(GBUFFER && !SHADOW);
 }
 }
 
@@ -825,13 +838,83 @@ __device__ __forceinline__ bool cone_rejects(const WaveCone& c, v3 oc, float oc2
     return cullable & (oc2 > R2) & (oc2 > 1e-30f) & (oc2 < 1e30f) & (cphi < rhs);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The root pre-test (TR_ROOT_PRETEST, policy::trace_root_pretests): behind the per-lane loop, once per instance the wave test left and WAVE,
+// the lanes whose mask still holds the instance compute the step the traversal would start it with -- Traversal::enter and the root's inner
+// step -- and clear the bit when both child boxes are missed. Half of the primary rays' entries end that way (multi-1M, 1920x1080: 2.03 M of
+// 4.02 M, profiles/camera_cull_counts.txt), each of them as a part-occupied enter block and root step somewhere in the wave's trip loop; here the
+// instance index is wave-uniform, so the instance record and the root's pair record come through the scalar cache and every lane of the tile works.
+// This clears bits the sphere cull keeps, which is legitimate through (7) -- it continues the numbering of the cull's derivation.
+//
+// (7) Claim. If root_pretest_misses returns true for a lane's ray (o, d) and instance k, then entering k changes nothing for that ray: the
+//     Closest every later instance sees, and the one closest_hit returns, are bit for bit what they are when k is skipped.
+// (7a) Same bits. The values are the traversal's own, from the traversal's own functions: load_instance's uniform path, xform_xyz for mo (w = 1) and
+//     md (w = 0), recip3<DIVIDE> with the kernel's DIVIDE, the pair record S.pairs[4 root ..] as the scalar path of Traversal::inner reads it, and
+//     intersect_aabb<false> on both children -- the same operations in the same order under -ffp-contract=off. recip3 decides division or short form
+//     for whichever lanes run it together, and both forms return the bits of 1.0f / x wherever the short one is taken (crt_recip.h: crt_debug_recip_sweep
+//     checks exactly that, on the division and the short sequence), so the company of lanes, which differs from the trip loop's, does not matter.
+//     The guard here is recip3's ONE_COMPARE form, `max(hi - 126, -125 - lo) > 0`: for integers it is `hi > 126 || lo < -125` (the maximum is positive
+//     iff one of its operands is; exponents lie in -149 ... 128, nothing wraps). The sweep instantiates the two-compare form only; the one-compare form
+//     is covered by this argument and by the frames of tests/test_gpu_root_pretest.py, not by the sweep. Only the bound differs: closest_hit's best0
+//     here, tr.t = c.distance there.
+// (7b) Monotone. The plain slab test passes only if tnear < minSoFar besides conditions that do not read the bound. closest_hit starts at
+//     c.distance = best0 (99999 in trace_body, the only caller of the staged form; the pre-test takes the caller's value, whatever it is) and
+//     c.distance only decreases: it is assigned tr.t of an instance with a passing triangle, and intersect_triangle requires t < out.t. So the
+//     bound the traversal holds when it reaches k is <= best0, and a box missed at best0 is missed at that bound: `tnear < bound` false at the
+//     larger bound is false at the smaller. A NaN tnear, tfar or best0 fails a compare whatever the bound.
+// (7c) No state leaves a wasted entry. enter sets curInst, mo, md, inv, tr, ref, sp = 0, prot = 1, inters = 0 -- all of it set again by the next
+//     enter before it is read. The root's inner step with both distances 1e30 pushes nothing (dist2 == 1e30) and calls pop_next with sp == 0:
+//     no pop, prot unchanged, and `keep = inters != 0` is false, so every field of c stays as it was and the lane is inactive again. Nothing else
+//     is written: the stack rows are untouched, the uncounted kernels keep no counters.
+// (7d) Single-leaf meshes (hazard H3). A root ref with CRT_LEAF_BIT names triangles, not a pair record: there is no box to test, the traversal tests
+//     the triangles at once, and the bit stays.
+// (7e) Who does not take it. Counted and stamped launches, the instance tree, the ldstop form and bounce 1 (sharedOrigin false) never reach
+//     staged_candidate_mask and compile to what they compiled to before; the counters of the wasted visits belong to the counted launch, which still
+//     makes them, and stay exact. Of the staged kernels, the waves that take no wave test (partial tiles, quadrant waves, scenes outside
+//     CRT_WAVE_CULL_MIN ... 64 instances) keep the path they had; a kernel the policy leaves out, and every kernel
+//     under -DCRT_NO_ROOT_PRETEST, compiles to the instructions of the wave test alone (the unit's assembly compared: no difference).
+// ------------------------------------------------------------------------------------------------
+#ifdef CRT_NO_ROOT_PRETEST
+#define CRT_ROOT_PRETESTS(PRETEST) false  // A/B builds: the instructions of the wave test alone, everywhere
+#else
+#define CRT_ROOT_PRETESTS(PRETEST) (PRETEST)
+#endif
+// `inst`: wave-uniform. Every lane of the wave runs it with the shared origin o; the lanes whose mask holds the instance use the answer.
+// The shape is what the ledger's rows allow (the benchmark kernel's: 64 VGPRs, 43 spilled SGPRs); each item below moved rows when left out:
+//  - recip3 takes its guard as one compare against zero (ONE_COMPARE): the two compares' constants 126 and -125 otherwise sit in SGPRs from the top
+//    of the kernel through both traversals (four more spilled SGPRs in every kernel that takes the pre-test);
+//  - the bound (best0: 99999 once inlined) is an opaque VGPR copy for the same reason (a v_mov per call instead of an SGPR per kernel).
+// (Asking for the records 16 bytes at a time, each piece consumed before the next, held the same rows and no more, and measured no better.)
+template <bool DIVIDE>
+__device__ __forceinline__ bool root_pretest_misses(const CrtDevScene& S, v3 o, v3 d, uint32_t inst, float best0)
+{
+    const crt_const_f32x4_ptr p = (crt_const_f32x4_ptr)(S.devInstances + inst);         // load_instance's uniform path
+    const crt_f32x4 r0 = p[0];
+    const uint32_t root = __float_as_uint(r0.w);
+    if (root & CRT_LEAF_BIT) return false;
+    const crt_f32x4 r1 = p[1], r2 = p[2], r3 = p[3];
+    CrtDevInstance I;
+    I.r0 = make_float4(r0.x, r0.y, r0.z, r0.w); I.r1 = make_float4(r1.x, r1.y, r1.z, r1.w);
+    I.r2 = make_float4(r2.x, r2.y, r2.z, r2.w); I.r3 = make_float4(r3.x, r3.y, r3.z, r3.w);
+    float bound = best0;
+    asm volatile("" : "+v"(bound));
+    const v3 mo = xform_xyz(I, o.x, o.y, o.z, 1.0f);
+    const v3 md = xform_xyz(I, d.x, d.y, d.z, 0.0f);
+    const v3 inv = recip3<DIVIDE, true>(md);
+    const crt_const_f32x4_ptr q = (crt_const_f32x4_ptr)(S.pairs + (size_t)root * 4);            // the scalar path of Traversal::inner
+    const crt_f32x4 a = q[0], b = q[1], c4 = q[2], e = q[3];
+    const float dist1 = intersect_aabb<false>(mo, inv, make_float4(a.x, a.y, a.z, a.w), make_float4(b.x, b.y, b.z, b.w), bound);
+    const float dist2 = intersect_aabb<false>(mo, inv, make_float4(c4.x, c4.y, c4.z, c4.w), make_float4(e.x, e.y, e.z, e.w), bound);
+    return (dist1 == 1e30f) & (dist2 == 1e30f);
+}
+
 typedef uint32_t crt_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t crt_u32x2 __attribute__((ext_vector_type(2)));
 typedef crt_u32x4 __attribute__((address_space(3)))* crt_lds_u32x4_ptr;
 typedef crt_u32x2 __attribute__((address_space(3)))* crt_lds_u32x2_ptr;
 #define CRT_STAGE_ROWS 6
-template <bool WAVE, class STK>
-__device__ __forceinline__ unsigned long long staged_candidate_mask(const CrtDevScene& S, v3 o, v3 d, uint32_t base, uint32_t cnt, const STK& stack)
+template <bool WAVE, bool PRETEST, bool DIVIDE, class STK>
+__device__ __forceinline__ unsigned long long staged_candidate_mask(const CrtDevScene& S, v3 o, v3 d, uint32_t base, uint32_t cnt, const STK& stack, float best0)
 {
     static_assert(STK::kLds >= CRT_STAGE_ROWS && CRT_BLOCK == 64, "the staged cull terms take six stack rows of a one-wave workgroup");
     // the wave's row 0. One-wave workgroups: lds = s_stack + threadIdx.x, so this folds to the array's address (the kernel's only LDS
@@ -883,10 +966,14 @@ __device__ __forceinline__ unsigned long long staged_candidate_mask(const CrtDev
         // candidates do not fit its list); it takes no wave test and its loops below run over all `cnt` bits. (An opaque copy: the compare's
         // result, hoisted out of the bounce loop, is two more spilled SGPRs in every kernel.)
         bool reject = false;
+        // `pre` (kernels that take the root pre-test only; without it no instruction differs from the wave test alone): all ones in a wave that takes
+        // the wave test -- the pre-test's loops run in those. An opaque scalar below: as a bool it is a 64-bit lane mask that lives through both cull loops.
+        [[maybe_unused]] uint32_t pre = 0u;
         const uint32_t n = cnt;
         uint32_t all = S.numInstances;
         asm volatile("" : "+s"(all));
         if (act == ~0ull && all - CRT_WAVE_CULL_MIN <= 64u - CRT_WAVE_CULL_MIN) {
+            if constexpr (CRT_ROOT_PRETESTS(PRETEST)) pre = ~0u;
             v3 dc = d; float ddc = dd; uint32_t lane = rank;
             asm volatile("" : "+v"(dc.x), "+v"(dc.y), "+v"(dc.z), "+v"(ddc), "+v"(lane));
             const WaveCone cone = wave_cone(dc, ddc);
@@ -902,8 +989,22 @@ __device__ __forceinline__ unsigned long long staged_candidate_mask(const CrtDev
         // a constant in a VGPR pair that then lives through the whole kernel)
         uint32_t touchLo = (uint32_t)touch, touchHi = (uint32_t)(touch >> 32);
         asm volatile("" : "+s"(touchLo), "+s"(touchHi));
+        if constexpr (CRT_ROOT_PRETESTS(PRETEST)) asm volatile("" : "+s"(pre));
         for (uint32_t m = touchLo; m != 0u; m &= m - 1u) { const uint32_t k = (uint32_t)__builtin_ctz(m); lo |= culls(k) ? 0u : 1u << k; }
         for (uint32_t m = touchHi; m != 0u; m &= m - 1u) { const uint32_t k = (uint32_t)__builtin_ctz(m); hi |= culls(k + 32u) ? 0u : 1u << k; }
+        if constexpr (CRT_ROOT_PRETESTS(PRETEST)) {
+            // The root pre-test, (7) above: over the same survivors, in the waves that took the wave test (`pre`; the others have all `cnt` bits in
+            // `touch` and keep the path they had). A survivor no lane kept is skipped. The branch is the wave's, not the lanes': every lane computes
+            // and a lane without the bit clears nothing -- one compare and a scalar branch instead of a saved and restored exec mask.
+            for (uint32_t m = touchLo & pre; m != 0u; m &= m - 1u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(m), bit = 1u << k;
+                if (__ballot((lo & bit) != 0u) != 0) lo &= root_pretest_misses<DIVIDE>(S, o, d, base + k, best0) ? ~bit : ~0u;
+            }
+            for (uint32_t m = touchHi & pre; m != 0u; m &= m - 1u) {
+                const uint32_t k = (uint32_t)__builtin_ctz(m), bit = 1u << k;
+                if (__ballot((hi & bit) != 0u) != 0) hi &= root_pretest_misses<DIVIDE>(S, o, d, base + k + 32u, best0) ? ~bit : ~0u;
+            }
+        }
     } else {
         const uint32_t nLo = cnt < 32u ? cnt : 32u;
         for (uint32_t k = 0; k < nLo; ++k) lo |= culls(k) ? 0u : 1u << k;
@@ -1029,6 +1130,7 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
     static_assert((OPTS & ~TR_ALL) == 0u, "unknown traversal option");
     static_assert(!STAGE || (!COUNT && !ITERS && !ANYHIT && !TLAS && !STK::kTop), "staged cull terms: uncounted closest-hit traversals of one-wave workgroups");
     static_assert(STAGE || !has_opt(OPTS, TR_WAVE_CULL), "the wave test lives in the staged cull");
+    static_assert(has_opt(OPTS, TR_WAVE_CULL) || !has_opt(OPTS, TR_ROOT_PRETEST), "the root pre-test runs over the wave test's survivors");
     Closest c = no_hit(best0);
     Traversal<OPTS> T; T.reset();
 
@@ -1068,7 +1170,8 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
     for (uint32_t base = 0; base < S.numInstances; base += 64) {
         const uint32_t cnt = (S.numInstances - base) < 64u ? (S.numInstances - base) : 64u;
         unsigned long long cand;
-        if constexpr (STAGE) cand = sharedOrigin ? staged_candidate_mask<has_opt(OPTS, TR_WAVE_CULL)>(S, o, d, base, cnt, stack) : candidate_mask(S, o, d, base, cnt, lc);
+        if constexpr (STAGE) cand = sharedOrigin ? staged_candidate_mask<has_opt(OPTS, TR_WAVE_CULL), has_opt(OPTS, TR_ROOT_PRETEST), has_opt(OPTS, TR_DIVIDE)>(S, o, d, base, cnt, stack, best0)
+                                                 : candidate_mask(S, o, d, base, cnt, lc);
         else cand = candidate_mask<opt_if(COUNT, CM_COUNT) | opt_if(ANYHIT, CM_DEFER_COUNT)>(S, o, d, base, cnt, lc);
         // ANYHIT + COUNT: a culled instance is only "visited" (one pop, one inner visit upstream) if the ray gets that
         // far, so culled instances are counted when a later candidate is entered or the chunk ends without a hit

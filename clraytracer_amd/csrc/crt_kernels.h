@@ -384,8 +384,9 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
     // what both traversals share, the primary one's own options, and the shading's (division, double-only sky index, staged cull: crt_device.h, policy)
     constexpr unsigned kRay = opt_if(COUNT, TR_COUNT) | opt_if(TLAS, TR_TLAS) | opt_if(policy::trace_divides(COUNT, GBUFFER, SHADOW, TLAS, REFRACT), TR_DIVIDE);
     constexpr bool kStages = policy::trace_stages_cull(COUNT, STAMP, TLAS, STK::kTop);
-    constexpr unsigned kPrimary = kRay | opt_if(STAMP, TR_ITERS) | opt_if(kStages, TR_STAGE)
-                                | opt_if(policy::trace_wave_culls(kStages, CASE == CRT_TRACE_PLAIN, GBUFFER, SHADOW, REFRACT), TR_WAVE_CULL);
+    constexpr bool kWaveCulls = policy::trace_wave_culls(kStages, CASE == CRT_TRACE_PLAIN, GBUFFER, SHADOW, REFRACT);
+    constexpr unsigned kPrimary = kRay | opt_if(STAMP, TR_ITERS) | opt_if(kStages, TR_STAGE) | opt_if(kWaveCulls, TR_WAVE_CULL)
+                                | opt_if(policy::trace_root_pretests(kWaveCulls, GBUFFER, SHADOW, REFRACT), TR_ROOT_PRETEST);
     constexpr unsigned kShade = opt_if(SHADOW, SB_DEFER_ENERGY) | opt_if(REFRACT, SB_REFRACT)
                               | opt_if(policy::trace_sky_double(COUNT, GBUFFER, SHADOW, TLAS, REFRACT), SB_SKY_DOUBLE);
     LaneCounters lc; zero_counters(lc);

@@ -1,5 +1,6 @@
-# Builds the three in-tree shared libraries:
+# Builds the in-tree shared libraries:
 #   clraytracer_amd/csrc/libcrt_hip.so   HIP kernels + C-ABI (include/crt_api.h), gfx950 only
+#   clraytracer_amd/denoise/libcrt_denoise.so   the a-trous denoiser on device buffers (include/crt_denoise.h), gfx950 only, stateless
 #   clraytracer_amd/host/libcrt_host.so  C++ host mirror of Renderer/ResourceManager/AssetManager (+ include/crt_host.h)
 #   oracle/libcrt_oracle.so              CPU oracle (test infrastructure only)
 HIPCC ?= /opt/rocm/bin/hipcc
@@ -21,11 +22,14 @@ HOST_SO = clraytracer_amd/host/libcrt_host.so
 HOST_SRC = $(addprefix clraytracer_amd/host/,AssetManager.cpp MeshCache.cpp JpegDecode.cpp BVH.cpp CPURayTrace.cpp Renderer.cpp ResourceManager.cpp crt_host_c.cpp ShmBarrier.cpp)
 HOST_HDR = $(wildcard clraytracer_amd/host/*.hpp) $(wildcard include/*.h)
 
+# a library of its own: a pure function of device buffers, and its kernels are no rows of libcrt_hip.so's resource ledger
+DENOISE_SO = clraytracer_amd/denoise/libcrt_denoise.so
+
 EXAMPLE = examples/crt_headless
 
 UBENCH = tools/ubench/gather tools/ubench/chain tools/ubench/cumask tools/ubench/sky_index
 
-all: $(HIP_SO) $(HOST_SO) $(EXAMPLE) $(UBENCH) oracle
+all: $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(EXAMPLE) $(UBENCH) oracle
 
 # vector-L1 gather microbenchmark (profiles/r01_ubench_gather.txt)
 tools/ubench/gather: tools/ubench/gather.hip
@@ -51,6 +55,9 @@ $(EXAMPLE): examples/headless_main.cpp $(HOST_SO)
 $(HIP_SO): $(wildcard clraytracer_amd/csrc/*.h) $(HIP_SRC) include/crt_api.h include/crt_debug.h include/crt_types.h
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $(HIP_SRC)
 
+$(DENOISE_SO): clraytracer_amd/denoise/crt_denoise.hip include/crt_denoise.h
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $<
+
 $(HOST_SO): $(HOST_SRC) $(HOST_HDR) $(HIP_SO)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRC) -Lclraytracer_amd/csrc -lcrt_hip -lrt -Wl,-rpath,'$$ORIGIN/../csrc'
 
@@ -58,7 +65,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(HIP_SO) $(HOST_SO) $(EXAMPLE) $(UBENCH)
+	rm -f $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(EXAMPLE) $(UBENCH)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

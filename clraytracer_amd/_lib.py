@@ -3,6 +3,7 @@
 * ``libcrt_hip.so``  -- the C-ABI drop-in boundary (``include/crt_api.h``): HIP kernels for gfx950.
 * ``libcrt_host.so`` -- C linkage over the C++ host mirror of the reference's
   Renderer / ResourceManager / AssetManager / CPU_RayCast (``include/crt_host.h``).
+* ``libcrt_denoise.so`` -- the stateless a-trous denoiser on device buffers (``include/crt_denoise.h``): HIP kernels for gfx950.
 
 Loading fails loudly (``ImportError``) when a library has not been built: there is no Python or
 CPU fallback for the ray-trace path. Build with ``make`` at the repo root or
@@ -22,6 +23,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(_HERE)
 HIP_SO = os.path.join(_HERE, "csrc", "libcrt_hip.so")
 HOST_SO = os.path.join(_HERE, "host", "libcrt_host.so")
+DENOISE_SO = os.path.join(_HERE, "denoise", "libcrt_denoise.so")
 
 
 class CrtTraceArgs(C.Structure):
@@ -98,6 +100,24 @@ assert GBUFFER_GEOMETRY_DTYPE.itemsize == 16 and GBUFFER_IDS_DTYPE.itemsize == 1
 # one ray's first-hit surface record of crt_shade_rays (CrtSurfaceHit): the G-buffer pixel, then the material index and the interpolated uv
 SURFACE_HIT_DTYPE = np.dtype(GBUFFER_PIXEL_DTYPE.descr + [("material", "<u4"), ("texU", "<f4"), ("texV", "<f4")])
 assert SURFACE_HIT_DTYPE.itemsize == 48 and C.sizeof(CrtShadeParams) == 8
+
+
+
+class CrtdFrame(C.Structure):
+    """The buffers of one crtd_denoise call (include/crt_denoise.h): pointers as integers; `guides` says how geometry / ids / albedo lie."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("color", C.c_void_p), ("guides", C.c_int32), ("geometry", C.c_void_p),
+                ("ids", C.c_void_p), ("albedo", C.c_void_p)]
+
+
+class CrtdParams(C.Structure):
+    """Parameters of crtd_denoise: iterations 1..6, CRTD_* flags, depthTol >= 0 (relative), a finite normalCos, lumaTol >= 0 under CRTD_LUMA_STOP."""
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_uint32), ("depthTol", C.c_float), ("normalCos", C.c_float), ("lumaTol", C.c_float)]
+
+
+assert C.sizeof(CrtdFrame) == 48 and C.sizeof(CrtdParams) == 20      # static_asserts of the same figures: denoise/crt_denoise.hip
+CRTD_OK, CRTD_E_BAD_ARGUMENT, CRTD_E_OUT_OF_RANGE = 0, -2, -3
+CRTD_GUIDES_PLANES, CRTD_GUIDES_SURFACE = 0, 1
+CRTD_DEMODULATE, CRTD_MATCH_INSTANCE, CRTD_LUMA_STOP = 1, 2, 4      # CrtdParams.flags
 
 _f = C.c_float
 _fp = C.POINTER(C.c_float)
@@ -250,6 +270,13 @@ HOST_API = {
     "crth_shm_barrier_close": (None, [_vp]),
 }
 
+# name -> (restype, argtypes); kept in sync with include/crt_denoise.h (tests/test_denoise_cpu.py checks it)
+DENOISE_API = {
+    "crtd_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "crtd_denoise": (C.c_int, [C.POINTER(CrtdFrame), C.POINTER(CrtdParams), _vp, _vp, _vp]),
+    "crtd_error_string": (C.c_char_p, [C.c_int]),
+}
+
 
 def _bind(path, table):
     if not os.path.exists(path):
@@ -265,6 +292,7 @@ def _bind(path, table):
 
 _hip = None
 _host = None
+_denoise = None
 
 
 def hip():
@@ -282,6 +310,14 @@ def host():
         hip()
         _host = _bind(HOST_SO, HOST_API)
     return _host
+
+
+def denoise():
+    """libcrt_denoise.so (include/crt_denoise.h). Stateless and independent of the other two; loading does not touch the GPU."""
+    global _denoise
+    if _denoise is None:
+        _denoise = _bind(DENOISE_SO, DENOISE_API)
+    return _denoise
 
 
 # include/crt_api.h: CrtStatus

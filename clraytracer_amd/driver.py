@@ -65,6 +65,9 @@ class Session:
         self.host_only = bool(host_only)
         self.device = int(devices[0]) if devices is not None else int(device)
         self.scene = None
+        self.multi_device = devices is not None and len(devices) > 1
+        self._last_frame = None     # what the most recent frame came from: "render", "render+gbuffer" or "render_raw" (denoise() asks)
+        self._row_bands = False
         if host_only:
             ok = self.h.crth_initialize_host_only(self.width, self.height)
         elif devices is not None:
@@ -135,6 +138,7 @@ class Session:
         self._check("OnWindowResize")
         if width >= 16 and height >= 16:
             self.width, self.height = int(width), int(height)
+        self._last_frame = None
 
     # ---- rendering through the mirrored Renderer ----
     def render(self, sun_angle=None, postprocess=False, shadows=False, pipelined=False, refraction=False, fxaa=False, ssaa=1, gbuffer=False):
@@ -151,6 +155,7 @@ class Session:
         if frame == 0:
             self._check("Renderer::Render")
             raise CrtError("Renderer::Render failed")
+        self._last_frame = "render+gbuffer" if gbuffer else "render"
         return frame
 
     def output(self):
@@ -201,6 +206,7 @@ class Session:
         if view is not None:
             iv, ip = np.ascontiguousarray(view[0], np.float32).reshape(16), np.ascontiguousarray(view[1], np.float32).reshape(16)
             a.cameraPos[0], a.cameraPos[1], a.cameraPos[2] = (float(x) for x in view[2])
+        self._last_frame = "render_raw"
         _lib.check(self.hip.crt_render(C.byref(a), iv.ctypes.data_as(C.POINTER(C.c_float)), ip.ctypes.data_as(C.POINTER(C.c_float)), int(flags)), "crt_render")
 
     def sync(self):
@@ -413,9 +419,78 @@ class Session:
         _lib.check(self.hip.crt_debug_ao_stats(out), "crt_debug_ao_stats")
         return int(out[0]), int(out[1]), int(out[2])
 
+    # ---- denoising on device buffers (libcrt_denoise.so: crtd_denoise; stateless, so there is no Renderer method to mirror) ----
+    def denoise(self, color=None, *, iterations=4, depth_tol=0.05, normal_cos=0.9, luma_tol=None, demodulate=True, match_instance=False,
+                surface=None, out=None):
+        """The edge-avoiding a-trous filter of include/crt_denoise.h: `iterations` passes (1..6) of 5 x 5 taps at steps 1, 2, 4, ..., a tap
+        counting when it is a hit whose distance is within depth_tol (relative, times the step) and whose normal's cosine is at least
+        normal_cos; luma_tol: also within that luminance of the centre (None: no such stop); demodulate: filter colour / albedo;
+        match_instance: taps of the centre's instance only. Returns an (height, width, 4) float32 tensor on the session's device (`out`, when
+        given), enqueued on torch.cuda.current_stream() without synchronising.
+        color=None: the float frame of the last render(gbuffer=True), guided by its planes (waits for the frames in flight first).
+        color given, a contiguous (height, width, 4) float32 tensor on the session's device -- samples accumulated over shade_rays, say --:
+        guided by the planes of the last render(gbuffer=True), or by surface=, a SurfaceHits of height * width records from
+        shade_rays(surface=True) in pixel order. ValueError: no such frame (none yet, or a later render without gbuffer, a render_raw or a
+        resize), a session under row bands or of several devices."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        H, W = self.height, self.width
+
+        def image(name, x):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+                raise ValueError(f"{name}: a float32 torch tensor is required, not {getattr(x, 'dtype', type(x))}")
+            if tuple(x.shape) != (H, W, 4) or not x.is_contiguous():
+                raise ValueError(f"{name}: a contiguous tensor of shape ({H}, {W}, 4) is required, not shape {tuple(x.shape)}, strides {x.stride()}")
+            if x.device.type != "cuda" or x.device.index != self.device:
+                raise ValueError(f"{name}: the tensor is on {x.device}, the session on cuda:{self.device}")
+            return x
+
+        if self.host_only or self.multi_device:
+            raise ValueError("denoise: the buffers belong to one GPU; not available in a host-only session or one of several devices")
+        frame = _lib.CrtdFrame(W, H, None, _lib.CRTD_GUIDES_PLANES, None, None, None)
+        if surface is not None:
+            if color is None:
+                raise ValueError("surface=: guides for a colour tensor; the frame form (color=None) is guided by the frame's own planes")
+            rec = surface.records if isinstance(surface, SurfaceHits) else None
+            if rec is None or tuple(rec.shape) != (H * W, 12) or not rec.is_contiguous():
+                raise ValueError(f"surface: a SurfaceHits of {H * W} records (height * width, in pixel order) is required")
+            if rec.device.type != "cuda" or rec.device.index != self.device:
+                raise ValueError(f"surface: the records are on {rec.device}, the session on cuda:{self.device}")
+            frame.guides, frame.geometry = _lib.CRTD_GUIDES_SURFACE, rec.data_ptr()
+        else:
+            if self._row_bands:
+                raise ValueError("denoise: the session is under row bands; the frame and its planes hold this rank's rows only")
+            if self._last_frame != "render+gbuffer":
+                raise ValueError("denoise: the last frame is no render(gbuffer=True) frame"
+                                 + {None: " (none has been rendered since the session began or was resized)", "render": " (it was rendered without gbuffer=True)",
+                                    "render_raw": " (it came from render_raw)"}[self._last_frame])
+            self.sync()
+            planes = [self.hip.crt_gbuffer_device_ptr(p) for p in (_lib.CRT_GBUFFER_GEOMETRY, _lib.CRT_GBUFFER_IDS, _lib.CRT_GBUFFER_ALBEDO)]
+            if not all(planes):
+                raise CrtError("crt_gbuffer_device_ptr returned null")
+            frame.geometry, frame.ids, frame.albedo = planes
+        if color is None:
+            frame.color = self.hip.crt_output_device_ptr()
+            if not frame.color:
+                raise CrtError("crt_output_device_ptr returned null")
+        else:
+            frame.color = image("color", color).data_ptr()
+        result = torch.empty((H, W, 4), dtype=torch.float32, device=dev) if out is None else image("out", out)
+        params = _lib.CrtdParams(int(iterations), (_lib.CRTD_DEMODULATE if demodulate else 0) | (_lib.CRTD_MATCH_INSTANCE if match_instance else 0)
+                                 | (_lib.CRTD_LUMA_STOP if luma_tol is not None else 0), float(depth_tol), float(normal_cos),
+                                 float(luma_tol) if luma_tol is not None else 0.0)
+        lib = _lib.denoise()
+        scratch = torch.empty((H, W, 4), dtype=torch.float32, device=dev) if lib.crtd_scratch_bytes(W, H, params.iterations) else None
+        rc = lib.crtd_denoise(C.byref(frame), C.byref(params), result.data_ptr(), scratch.data_ptr() if scratch is not None else None,
+                              torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise CrtError(f"crtd_denoise failed with {rc}: {lib.crtd_error_string(rc).decode()}")
+        return result       # (scratch goes back to torch's allocator, which hands a block out again in the order of the stream it was made on)
+
     def set_row_bands(self, band_rows, rank, n_ranks):
         self.h.crth_set_row_bands(int(band_rows), int(rank), int(n_ranks))
         self._check("SetRowBands")
+        self._row_bands = int(n_ranks) > 1
 
     def owned_rows(self):
         return int(self.hip.crt_owned_rows())

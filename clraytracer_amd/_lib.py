@@ -4,6 +4,7 @@
 * ``libcrt_host.so`` -- C linkage over the C++ host mirror of the reference's
   Renderer / ResourceManager / AssetManager / CPU_RayCast (``include/crt_host.h``).
 * ``libcrt_denoise.so`` -- the stateless a-trous denoiser on device buffers (``include/crt_denoise.h``): HIP kernels for gfx950.
+* ``libcrt_temporal.so`` -- stateless temporal reprojection and accumulation on device buffers (``include/crt_temporal.h``): HIP for gfx950.
 
 Loading fails loudly (``ImportError``) when a library has not been built: there is no Python or
 CPU fallback for the ray-trace path. Build with ``make`` at the repo root or
@@ -24,6 +25,7 @@ ROOT = os.path.dirname(_HERE)
 HIP_SO = os.path.join(_HERE, "csrc", "libcrt_hip.so")
 HOST_SO = os.path.join(_HERE, "host", "libcrt_host.so")
 DENOISE_SO = os.path.join(_HERE, "denoise", "libcrt_denoise.so")
+TEMPORAL_SO = os.path.join(_HERE, "temporal", "libcrt_temporal.so")
 
 
 class CrtTraceArgs(C.Structure):
@@ -118,6 +120,38 @@ assert C.sizeof(CrtdFrame) == 48 and C.sizeof(CrtdParams) == 20      # static_as
 CRTD_OK, CRTD_E_BAD_ARGUMENT, CRTD_E_OUT_OF_RANGE = 0, -2, -3
 CRTD_GUIDES_PLANES, CRTD_GUIDES_SURFACE = 0, 1
 CRTD_DEMODULATE, CRTD_MATCH_INSTANCE, CRTD_LUMA_STOP = 1, 2, 4      # CrtdParams.flags
+
+
+
+class CrttCamera(C.Structure):
+    """One frame's camera as crtt_accumulate sees it (include/crt_temporal.h; made by crtt_camera): row-major 3 x 3 maps from (i, j, 1) to the
+    unnormalised ray direction and from a world-space vector from `pos` back to (u.x / u.z, u.y / u.z) pixel coordinates."""
+    _fields_ = [("pos", C.c_float * 3), ("toRay", C.c_float * 9), ("toScreen", C.c_float * 9)]
+
+
+class CrttFrame(C.Structure):
+    """The current frame of one crtt_accumulate call: pointers as integers; `guides` says how geometry / ids lie (as CrtdFrame)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("color", C.c_void_p), ("guides", C.c_int32), ("geometry", C.c_void_p),
+                ("ids", C.c_void_p), ("camera", CrttCamera)]
+
+
+class CrttHistory(C.Structure):
+    """One set of history planes: color, moments {m1, m2, N, variance}, geometry {n, t} (float4 each), instance (int32) and their camera."""
+    _fields_ = [("color", C.c_void_p), ("moments", C.c_void_p), ("geometry", C.c_void_p), ("instance", C.c_void_p), ("camera", CrttCamera)]
+
+
+class CrttParams(C.Structure):
+    """Parameters of crtt_accumulate: CRTT_* flags, alpha and momentsAlpha in (0, 1], a finite maxHistory >= 1, depthTol >= 0, a finite normalCos."""
+    _fields_ = [("flags", C.c_uint32), ("alpha", C.c_float), ("momentsAlpha", C.c_float), ("maxHistory", C.c_float), ("depthTol", C.c_float),
+                ("normalCos", C.c_float)]
+
+
+# static_asserts of the same figures: temporal/crt_temporal.hip
+assert C.sizeof(CrttCamera) == 84 and C.sizeof(CrttFrame) == 128 and C.sizeof(CrttHistory) == 120 and C.sizeof(CrttParams) == 24
+CRTT_OK, CRTT_E_BAD_ARGUMENT, CRTT_E_OUT_OF_RANGE = 0, -2, -3
+CRTT_GUIDES_PLANES, CRTT_GUIDES_SURFACE = 0, 1
+CRTT_MATCH_INSTANCE, CRTT_CLAMP = 1, 2                              # CrttParams.flags
+CRTT_PLANE_COLOR, CRTT_PLANE_MOMENTS, CRTT_PLANE_GEOMETRY, CRTT_PLANE_INSTANCE = 0, 1, 2, 3     # crtt_history_bytes
 
 _f = C.c_float
 _fp = C.POINTER(C.c_float)
@@ -277,6 +311,14 @@ DENOISE_API = {
     "crtd_error_string": (C.c_char_p, [C.c_int]),
 }
 
+# name -> (restype, argtypes); kept in sync with include/crt_temporal.h (tests/test_temporal_cpu.py checks it)
+TEMPORAL_API = {
+    "crtt_camera": (C.c_int, [_fp, _fp, _fp, C.c_int32, C.c_int32, C.POINTER(CrttCamera)]),
+    "crtt_history_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int]),
+    "crtt_accumulate": (C.c_int, [C.POINTER(CrttFrame), C.POINTER(CrttHistory), C.POINTER(CrttHistory), C.POINTER(CrttParams), _vp]),
+    "crtt_error_string": (C.c_char_p, [C.c_int]),
+}
+
 
 def _bind(path, table):
     if not os.path.exists(path):
@@ -293,6 +335,7 @@ def _bind(path, table):
 _hip = None
 _host = None
 _denoise = None
+_temporal = None
 
 
 def hip():
@@ -318,6 +361,24 @@ def denoise():
     if _denoise is None:
         _denoise = _bind(DENOISE_SO, DENOISE_API)
     return _denoise
+
+
+def temporal():
+    """libcrt_temporal.so (include/crt_temporal.h). Stateless and independent of the other three; loading does not touch the GPU."""
+    global _temporal
+    if _temporal is None:
+        _temporal = _bind(TEMPORAL_SO, TEMPORAL_API)
+    return _temporal
+
+
+def crtt_camera(inv_view, inv_proj, pos, width, height):
+    """crtt_camera: the CrttCamera of a frame shot with these matrices (as Session.camera() returns them); CrtError when it refuses them."""
+    (a, k1), (b, k2), (c, k3) = fptr(np.asarray(inv_view).reshape(16)), fptr(np.asarray(inv_proj).reshape(16)), fptr(np.asarray(pos).reshape(3))
+    cam = CrttCamera()
+    rc = temporal().crtt_camera(a, b, c, int(width), int(height), C.byref(cam))
+    if rc != 0:
+        raise CrtError(f"crtt_camera failed with {rc}: {temporal().crtt_error_string(rc).decode()}")
+    return cam
 
 
 # include/crt_api.h: CrtStatus

@@ -55,6 +55,40 @@ class SurfaceHits:
         return self.records.cpu().numpy().view(_lib.SURFACE_HIT_DTYPE).reshape(-1)
 
 
+class TemporalHistory:
+    """The history of Session.accumulate: two sets of planes (color, moments {m1, m2, N, variance}, geometry {n, t}: (height, width, 4) float32;
+    with match_instance=True also instance: (height, width) int32) as torch tensors on the session's device, of which each accumulate reads
+    one and writes the other, and the CrttCamera of the set last written. color, moments, geometry, instance: the set last written; frames:
+    how many frames went in since the last reset. A history belongs to the session's size at its making: after a resize make a new one."""
+
+    def __init__(self, session, match_instance=False):
+        import torch
+        if session.host_only or session.multi_device:
+            raise ValueError("TemporalHistory: the buffers belong to one GPU; not available in a host-only session or one of several devices")
+        self.width, self.height, self.device, self.match_instance = session.width, session.height, session.device, bool(match_instance)
+        dev = torch.device("cuda", self.device)
+        lib = _lib.temporal()
+        planes = [("color", _lib.CRTT_PLANE_COLOR, (4,), torch.float32), ("moments", _lib.CRTT_PLANE_MOMENTS, (4,), torch.float32),
+                  ("geometry", _lib.CRTT_PLANE_GEOMETRY, (4,), torch.float32)] + ([("instance", _lib.CRTT_PLANE_INSTANCE, (), torch.int32)] if match_instance else [])
+        self.sets = []
+        for _ in range(2):
+            one = {name: torch.zeros((self.height, self.width) + tail, dtype=dtype, device=dev) for name, _, tail, dtype in planes}
+            for name, plane, _, _ in planes:
+                assert one[name].numel() * one[name].element_size() == lib.crtt_history_bytes(self.width, self.height, plane), name
+            self.sets.append(one)
+        self.current, self.camera, self.frames = 0, None, 0
+
+    def _struct(self, which, camera):
+        s = self.sets[which]
+        return _lib.CrttHistory(s["color"].data_ptr(), s["moments"].data_ptr(), s["geometry"].data_ptr(),
+                                s["instance"].data_ptr() if "instance" in s else None, camera if camera is not None else _lib.CrttCamera())
+
+    color = property(lambda self: self.sets[self.current]["color"])
+    moments = property(lambda self: self.sets[self.current]["moments"])
+    geometry = property(lambda self: self.sets[self.current]["geometry"])
+    instance = property(lambda self: self.sets[self.current].get("instance"))
+
+
 class Session:
     def __init__(self, width, height, device=0, host_only=False, devices=None):
         """device: one HIP ordinal; devices: a list of ordinals -> several GPUs in this process (Renderer::InitializeDevices;
@@ -419,6 +453,54 @@ class Session:
         _lib.check(self.hip.crt_debug_ao_stats(out), "crt_debug_ao_stats")
         return int(out[0]), int(out[1]), int(out[2])
 
+    # ---- what denoise() and accumulate() take: a colour image and the guides beside it ----
+    def _image(self, name, x):
+        import torch
+        H, W = self.height, self.width
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+            raise ValueError(f"{name}: a float32 torch tensor is required, not {getattr(x, 'dtype', type(x))}")
+        if tuple(x.shape) != (H, W, 4) or not x.is_contiguous():
+            raise ValueError(f"{name}: a contiguous tensor of shape ({H}, {W}, 4) is required, not shape {tuple(x.shape)}, strides {x.stride()}")
+        if x.device.type != "cuda" or x.device.index != self.device:
+            raise ValueError(f"{name}: the tensor is on {x.device}, the session on cuda:{self.device}")
+        return x
+
+    def _guided_frame(self, what, color, surface):
+        """(color, guide layout, geometry, ids, albedo) as device addresses for `what` = "denoise" / "accumulate": color=None is the float
+        frame of the last render(gbuffer=True) (waits for the frames in flight first); the guides are that frame's planes, or surface=, a
+        SurfaceHits of height * width records. ValueError: see Session.denoise."""
+        H, W = self.height, self.width
+        if self.host_only or self.multi_device:
+            raise ValueError(f"{what}: the buffers belong to one GPU; not available in a host-only session or one of several devices")
+        guides, geometry, ids, albedo = _lib.CRTD_GUIDES_PLANES, None, None, None
+        if surface is not None:
+            if color is None:
+                raise ValueError("surface=: guides for a colour tensor; the frame form (color=None) is guided by the frame's own planes")
+            rec = surface.records if isinstance(surface, SurfaceHits) else None
+            if rec is None or tuple(rec.shape) != (H * W, 12) or not rec.is_contiguous():
+                raise ValueError(f"surface: a SurfaceHits of {H * W} records (height * width, in pixel order) is required")
+            if rec.device.type != "cuda" or rec.device.index != self.device:
+                raise ValueError(f"surface: the records are on {rec.device}, the session on cuda:{self.device}")
+            guides, geometry = _lib.CRTD_GUIDES_SURFACE, rec.data_ptr()
+        else:
+            if self._row_bands:
+                raise ValueError(f"{what}: the session is under row bands; the frame and its planes hold this rank's rows only")
+            if self._last_frame != "render+gbuffer":
+                raise ValueError(f"{what}: the last frame is no render(gbuffer=True) frame"
+                                 + {None: " (none has been rendered since the session began or was resized)", "render": " (it was rendered without gbuffer=True)",
+                                    "render_raw": " (it came from render_raw)"}[self._last_frame])
+            self.sync()
+            geometry, ids, albedo = [self.hip.crt_gbuffer_device_ptr(p) for p in (_lib.CRT_GBUFFER_GEOMETRY, _lib.CRT_GBUFFER_IDS, _lib.CRT_GBUFFER_ALBEDO)]
+            if not (geometry and ids and albedo):
+                raise CrtError("crt_gbuffer_device_ptr returned null")
+        if color is None:
+            ptr = self.hip.crt_output_device_ptr()
+            if not ptr:
+                raise CrtError("crt_output_device_ptr returned null")
+        else:
+            ptr = self._image("color", color).data_ptr()
+        return ptr, guides, geometry, ids, albedo
+
     # ---- denoising on device buffers (libcrt_denoise.so: crtd_denoise; stateless, so there is no Renderer method to mirror) ----
     def denoise(self, color=None, *, iterations=4, depth_tol=0.05, normal_cos=0.9, luma_tol=None, demodulate=True, match_instance=False,
                 surface=None, out=None):
@@ -435,47 +517,9 @@ class Session:
         import torch
         dev = torch.device("cuda", self.device)
         H, W = self.height, self.width
-
-        def image(name, x):
-            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
-                raise ValueError(f"{name}: a float32 torch tensor is required, not {getattr(x, 'dtype', type(x))}")
-            if tuple(x.shape) != (H, W, 4) or not x.is_contiguous():
-                raise ValueError(f"{name}: a contiguous tensor of shape ({H}, {W}, 4) is required, not shape {tuple(x.shape)}, strides {x.stride()}")
-            if x.device.type != "cuda" or x.device.index != self.device:
-                raise ValueError(f"{name}: the tensor is on {x.device}, the session on cuda:{self.device}")
-            return x
-
-        if self.host_only or self.multi_device:
-            raise ValueError("denoise: the buffers belong to one GPU; not available in a host-only session or one of several devices")
         frame = _lib.CrtdFrame(W, H, None, _lib.CRTD_GUIDES_PLANES, None, None, None)
-        if surface is not None:
-            if color is None:
-                raise ValueError("surface=: guides for a colour tensor; the frame form (color=None) is guided by the frame's own planes")
-            rec = surface.records if isinstance(surface, SurfaceHits) else None
-            if rec is None or tuple(rec.shape) != (H * W, 12) or not rec.is_contiguous():
-                raise ValueError(f"surface: a SurfaceHits of {H * W} records (height * width, in pixel order) is required")
-            if rec.device.type != "cuda" or rec.device.index != self.device:
-                raise ValueError(f"surface: the records are on {rec.device}, the session on cuda:{self.device}")
-            frame.guides, frame.geometry = _lib.CRTD_GUIDES_SURFACE, rec.data_ptr()
-        else:
-            if self._row_bands:
-                raise ValueError("denoise: the session is under row bands; the frame and its planes hold this rank's rows only")
-            if self._last_frame != "render+gbuffer":
-                raise ValueError("denoise: the last frame is no render(gbuffer=True) frame"
-                                 + {None: " (none has been rendered since the session began or was resized)", "render": " (it was rendered without gbuffer=True)",
-                                    "render_raw": " (it came from render_raw)"}[self._last_frame])
-            self.sync()
-            planes = [self.hip.crt_gbuffer_device_ptr(p) for p in (_lib.CRT_GBUFFER_GEOMETRY, _lib.CRT_GBUFFER_IDS, _lib.CRT_GBUFFER_ALBEDO)]
-            if not all(planes):
-                raise CrtError("crt_gbuffer_device_ptr returned null")
-            frame.geometry, frame.ids, frame.albedo = planes
-        if color is None:
-            frame.color = self.hip.crt_output_device_ptr()
-            if not frame.color:
-                raise CrtError("crt_output_device_ptr returned null")
-        else:
-            frame.color = image("color", color).data_ptr()
-        result = torch.empty((H, W, 4), dtype=torch.float32, device=dev) if out is None else image("out", out)
+        frame.color, frame.guides, frame.geometry, frame.ids, frame.albedo = self._guided_frame("denoise", color, surface)
+        result = torch.empty((H, W, 4), dtype=torch.float32, device=dev) if out is None else self._image("out", out)
         params = _lib.CrtdParams(int(iterations), (_lib.CRTD_DEMODULATE if demodulate else 0) | (_lib.CRTD_MATCH_INSTANCE if match_instance else 0)
                                  | (_lib.CRTD_LUMA_STOP if luma_tol is not None else 0), float(depth_tol), float(normal_cos),
                                  float(luma_tol) if luma_tol is not None else 0.0)
@@ -486,6 +530,40 @@ class Session:
         if rc != 0:
             raise CrtError(f"crtd_denoise failed with {rc}: {lib.crtd_error_string(rc).decode()}")
         return result       # (scratch goes back to torch's allocator, which hands a block out again in the order of the stream it was made on)
+
+    # ---- temporal accumulation on device buffers (libcrt_temporal.so: crtt_accumulate; stateless: the history is a TemporalHistory) ----
+    def accumulate(self, history, color=None, *, surface=None, camera=None, alpha=0.2, moments_alpha=0.2, max_history=32, depth_tol=0.05,
+                   normal_cos=0.9, clamp=False, reset=False):
+        """One frame into `history` (a TemporalHistory of this session's size), by the definition of include/crt_temporal.h: the history is
+        fetched where each pixel's surface was in the previous frame -- four taps, each counting when it is a hit whose distance is within
+        depth_tol (relative) of the reprojected one and whose normal's cosine is at least normal_cos (and, for a history made with
+        match_instance=True, of the pixel's instance) -- and blended with the frame: the new frame's share is max(alpha, 1 / N), N counting
+        the frames accumulated up to max_history; moments_alpha: the same for the luminance moments; clamp: the history colour is first
+        clamped to the frame's 3 x 3 neighbourhood. reset=True (or a history nothing was written to yet) starts over from this frame.
+        color, surface: as Session.denoise takes them (None: the float frame of the last render(gbuffer=True), guided by its planes), with the
+        same ValueErrors. camera=(invView, invProj, pos): the matrices the frame was shot with; default: self.camera().
+        Enqueues on torch.cuda.current_stream() without synchronising, swaps the history's two sets and returns (color, moments): two
+        (height, width, 4) float32 tensors, moments = {m1, m2, N, variance} of the luminance. They are the history's own planes: valid until
+        the next accumulate but one into it; color is a valid color= for Session.denoise."""
+        import torch
+        H, W = self.height, self.width
+        if not isinstance(history, TemporalHistory) or (history.width, history.height, history.device) != (W, H, self.device):
+            raise ValueError(f"history: a TemporalHistory of {W} x {H} on cuda:{self.device} is required")
+        ptr, guides, geometry, ids, _ = self._guided_frame("accumulate", color, surface)
+        iv, ip, pos = self.camera() if camera is None else camera
+        cam = _lib.crtt_camera(iv, ip, pos, W, H)
+        frame = _lib.CrttFrame(W, H, ptr, guides, geometry, ids, cam)
+        prev = None if reset or history.camera is None else history._struct(history.current, history.camera)
+        nxt = history._struct(1 - history.current, cam)
+        params = _lib.CrttParams((_lib.CRTT_MATCH_INSTANCE if history.match_instance else 0) | (_lib.CRTT_CLAMP if clamp else 0), float(alpha),
+                                 float(moments_alpha), float(max_history), float(depth_tol), float(normal_cos))
+        lib = _lib.temporal()
+        rc = lib.crtt_accumulate(C.byref(frame), None if prev is None else C.byref(prev), C.byref(nxt), C.byref(params),
+                                 torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+        if rc != 0:
+            raise CrtError(f"crtt_accumulate failed with {rc}: {lib.crtt_error_string(rc).decode()}")
+        history.current, history.camera, history.frames = 1 - history.current, cam, (1 if prev is None else history.frames + 1)
+        return history.color, history.moments
 
     def set_row_bands(self, band_rows, rank, n_ranks):
         self.h.crth_set_row_bands(int(band_rows), int(rank), int(n_ranks))

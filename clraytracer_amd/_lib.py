@@ -5,6 +5,7 @@
   Renderer / ResourceManager / AssetManager / CPU_RayCast (``include/crt_host.h``).
 * ``libcrt_denoise.so`` -- the stateless a-trous denoiser on device buffers (``include/crt_denoise.h``): HIP kernels for gfx950.
 * ``libcrt_temporal.so`` -- stateless temporal reprojection and accumulation on device buffers (``include/crt_temporal.h``): HIP for gfx950.
+* ``libcrt_vfilter.so`` -- the stateless variance-guided a-trous filter on device buffers (``include/crt_vfilter.h``): HIP for gfx950.
 
 Loading fails loudly (``ImportError``) when a library has not been built: there is no Python or
 CPU fallback for the ray-trace path. Build with ``make`` at the repo root or
@@ -26,6 +27,7 @@ HIP_SO = os.path.join(_HERE, "csrc", "libcrt_hip.so")
 HOST_SO = os.path.join(_HERE, "host", "libcrt_host.so")
 DENOISE_SO = os.path.join(_HERE, "denoise", "libcrt_denoise.so")
 TEMPORAL_SO = os.path.join(_HERE, "temporal", "libcrt_temporal.so")
+VFILTER_SO = os.path.join(_HERE, "vfilter", "libcrt_vfilter.so")
 
 
 class CrtTraceArgs(C.Structure):
@@ -152,6 +154,27 @@ CRTT_OK, CRTT_E_BAD_ARGUMENT, CRTT_E_OUT_OF_RANGE = 0, -2, -3
 CRTT_GUIDES_PLANES, CRTT_GUIDES_SURFACE = 0, 1
 CRTT_MATCH_INSTANCE, CRTT_CLAMP = 1, 2                              # CrttParams.flags
 CRTT_PLANE_COLOR, CRTT_PLANE_MOMENTS, CRTT_PLANE_GEOMETRY, CRTT_PLANE_INSTANCE = 0, 1, 2, 3     # crtt_history_bytes
+
+
+
+class CrtvFrame(C.Structure):
+    """The buffers of one crtv_filter call (include/crt_vfilter.h): pointers as integers; color and moments as crtt_accumulate writes them; `guides`
+    says how geometry / ids / albedo lie (as CrtdFrame)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("color", C.c_void_p), ("moments", C.c_void_p), ("guides", C.c_int32),
+                ("geometry", C.c_void_p), ("ids", C.c_void_p), ("albedo", C.c_void_p)]
+
+
+class CrtvParams(C.Structure):
+    """Parameters of crtv_filter: iterations 1..5, CRTV_* flags, depthTol >= 0 (relative), a finite normalCos, finite lumaSigma and lumaFloor >= 0,
+    a minHistory that is no NaN."""
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_uint32), ("depthTol", C.c_float), ("normalCos", C.c_float), ("lumaSigma", C.c_float),
+                ("lumaFloor", C.c_float), ("minHistory", C.c_float)]
+
+
+assert C.sizeof(CrtvFrame) == 56 and C.sizeof(CrtvParams) == 28      # static_asserts of the same figures: vfilter/crt_vfilter.hip
+CRTV_OK, CRTV_E_BAD_ARGUMENT, CRTV_E_OUT_OF_RANGE = 0, -2, -3
+CRTV_GUIDES_PLANES, CRTV_GUIDES_SURFACE = 0, 1
+CRTV_DEMODULATE, CRTV_MATCH_INSTANCE = 1, 2                          # CrtvParams.flags
 
 _f = C.c_float
 _fp = C.POINTER(C.c_float)
@@ -319,6 +342,13 @@ TEMPORAL_API = {
     "crtt_error_string": (C.c_char_p, [C.c_int]),
 }
 
+# name -> (restype, argtypes); kept in sync with include/crt_vfilter.h (tests/test_vfilter_cpu.py checks it)
+VFILTER_API = {
+    "crtv_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "crtv_filter": (C.c_int, [C.POINTER(CrtvFrame), C.POINTER(CrtvParams), _vp, _vp, _vp, _vp]),
+    "crtv_error_string": (C.c_char_p, [C.c_int]),
+}
+
 
 def _bind(path, table):
     if not os.path.exists(path):
@@ -336,6 +366,7 @@ _hip = None
 _host = None
 _denoise = None
 _temporal = None
+_vfilter = None
 
 
 def hip():
@@ -369,6 +400,14 @@ def temporal():
     if _temporal is None:
         _temporal = _bind(TEMPORAL_SO, TEMPORAL_API)
     return _temporal
+
+
+def vfilter():
+    """libcrt_vfilter.so (include/crt_vfilter.h). Stateless and independent of the other four; loading does not touch the GPU."""
+    global _vfilter
+    if _vfilter is None:
+        _vfilter = _bind(VFILTER_SO, VFILTER_API)
+    return _vfilter
 
 
 def crtt_camera(inv_view, inv_proj, pos, width, height):

@@ -565,6 +565,38 @@ class Session:
         history.current, history.camera, history.frames = 1 - history.current, cam, (1 if prev is None else history.frames + 1)
         return history.color, history.moments
 
+    # ---- variance-guided filtering on device buffers (libcrt_vfilter.so: crtv_filter; stateless, so there is no Renderer method to mirror) ----
+    def filter_variance(self, color, moments, *, iterations=4, depth_tol=0.05, normal_cos=0.9, luma_sigma=4.0, luma_floor=1e-4, min_history=4,
+                        demodulate=True, match_instance=False, surface=None, out=None, return_variance=False):
+        """The variance-guided a-trous filter of include/crt_vfilter.h over what Session.accumulate returns: `color` and `moments`, two contiguous
+        (height, width, 4) float32 tensors on the session's device, moments = {m1, m2, N, variance} of the luminance. A pixel's variance is the
+        history's where N >= min_history and a 7 x 7 estimate over the moments elsewhere; `iterations` passes (1..5) of 5 x 5 taps at steps 1, 2,
+        4, ..., a tap counting when it passes the geometry stops of Session.denoise (depth_tol, normal_cos, match_instance) and its luminance is
+        within luma_sigma standard deviations (of the 3 x 3 prefiltered variance) + luma_floor of the centre's, weighted by how far within;
+        demodulate: filter colour / albedo. The variance is carried through the passes. Guided as Session.denoise's tensor form is: by the planes
+        of the last render(gbuffer=True), or by surface=, a SurfaceHits of height * width records in pixel order; the same ValueErrors.
+        Returns an (height, width, 4) float32 tensor (`out`, when given), or (that, the filtered luminance variance as an (height, width) float32
+        tensor) with return_variance=True; enqueued on torch.cuda.current_stream() without synchronising."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        H, W = self.height, self.width
+        if color is None:
+            raise ValueError("color: a tensor is required (Session.accumulate returns it, beside the moments)")
+        frame = _lib.CrtvFrame(W, H, None, None, _lib.CRTV_GUIDES_PLANES, None, None, None)
+        frame.color, frame.guides, frame.geometry, frame.ids, frame.albedo = self._guided_frame("filter_variance", color, surface)
+        frame.moments = self._image("moments", moments).data_ptr()
+        result = torch.empty((H, W, 4), dtype=torch.float32, device=dev) if out is None else self._image("out", out)
+        variance = torch.empty((H, W), dtype=torch.float32, device=dev) if return_variance else None
+        params = _lib.CrtvParams(int(iterations), (_lib.CRTV_DEMODULATE if demodulate else 0) | (_lib.CRTV_MATCH_INSTANCE if match_instance else 0),
+                                 float(depth_tol), float(normal_cos), float(luma_sigma), float(luma_floor), float(min_history))
+        scratch = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
+        lib = _lib.vfilter()
+        rc = lib.crtv_filter(C.byref(frame), C.byref(params), result.data_ptr(), variance.data_ptr() if return_variance else None, scratch.data_ptr(),
+                             torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise CrtError(f"crtv_filter failed with {rc}: {lib.crtv_error_string(rc).decode()}")
+        return (result, variance) if return_variance else result      # (scratch goes back to torch's allocator, in the order of its stream)
+
     def set_row_bands(self, band_rows, rank, n_ranks):
         self.h.crth_set_row_bands(int(band_rows), int(rank), int(n_ranks))
         self._check("SetRowBands")

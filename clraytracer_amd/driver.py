@@ -17,10 +17,11 @@ class RayHits:
     """The records of Session.trace_rays(mode="closest"): `records` is one (n, 5) int32 tensor on the device holding n CrtRayHit {t, u, v,
     triIndex, instance}; t, u, v (float32) and tri, instance (int32) are views of its columns. A miss: t = 99999, instance = -1, the rest 0."""
 
-    def __init__(self, records):
+    def __init__(self, records, stream=None):
         import torch
         f = records.view(torch.float32)
         self.records = records
+        self._stream = stream       # the torch stream the query was enqueued on (None: the caller orders the records itself)
         self.t, self.u, self.v = f[:, 0], f[:, 1], f[:, 2]
         self.tri, self.instance = records[:, 3], records[:, 4]
 
@@ -29,6 +30,8 @@ class RayHits:
 
     def numpy(self):
         """The records on the host as _lib.RAYHIT_DTYPE (synchronises with the stream that produced them)."""
+        if self._stream is not None:
+            self._stream.synchronize()      # the copy below runs on torch's CURRENT stream, which need not be the query's
         return self.records.cpu().numpy().view(_lib.RAYHIT_DTYPE).reshape(-1)
 
 
@@ -37,10 +40,11 @@ class SurfaceHits:
     (n, 3), t, u, v, tex_u, tex_v (float32) and instance, tri, albedo, material (int32) are views of its columns. A miss: t = 99999,
     instance = -1, the rest 0."""
 
-    def __init__(self, records):
+    def __init__(self, records, stream=None):
         import torch
         f = records.view(torch.float32)
         self.records = records
+        self._stream = stream       # the torch stream the query was enqueued on (None: the caller orders the records itself)
         self.normal, self.t = f[:, 0:3], f[:, 3]
         self.instance, self.tri = records[:, 4], records[:, 5]
         self.u, self.v = f[:, 6], f[:, 7]
@@ -52,6 +56,8 @@ class SurfaceHits:
 
     def numpy(self):
         """The records on the host as _lib.SURFACE_HIT_DTYPE (synchronises with the stream that produced them)."""
+        if self._stream is not None:
+            self._stream.synchronize()      # the copy below runs on torch's CURRENT stream, which need not be the query's
         return self.records.cpu().numpy().view(_lib.SURFACE_HIT_DTYPE).reshape(-1)
 
 
@@ -102,6 +108,7 @@ class Session:
         self.multi_device = devices is not None and len(devices) > 1
         self._last_frame = None     # what the most recent frame came from: "render", "render+gbuffer" or "render_raw" (denoise() asks)
         self._row_bands = False
+        self._frame_readers = []    # torch events behind the filters still reading the frame's own buffers (_frame_read_queued)
         if host_only:
             ok = self.h.crth_initialize_host_only(self.width, self.height)
         elif devices is not None:
@@ -117,6 +124,7 @@ class Session:
     # ---- lifecycle ----
     def close(self):
         if self.open:
+            self._wait_frame_readers()
             self.h.crth_terminate()
             self.open = False
 
@@ -131,9 +139,35 @@ class Session:
         if rc:
             raise CrtError(f"{what}: error {rc}: {self.hip.crt_error_string(rc).decode()}")
 
+    # ---- the frame's own buffers against the filters that read them ----
+    # denoise(), accumulate() and filter_variance() hand crt_output_device_ptr() / crt_gbuffer_device_ptr() to a stateless library that
+    # enqueues on torch's stream and returns. The session's streams know nothing of that stream, and a synchronous frame always reuses
+    # slot 0: the next frame would overwrite, and a resize or close free, what the filter has yet to read. So each such call leaves an
+    # event behind it, and whatever writes or frees those buffers waits for the events on the host first, as crt_sync() does for a ray
+    # query in flight. (Waiting on the device would take the slot's stream, which the C-ABI keeps to itself.)
+    def _frame_read_queued(self):
+        """A filter reading the frame's colour buffer or planes was just enqueued on torch's current stream: remember where it ends."""
+        import torch
+        self._frame_readers = [ev for ev in self._frame_readers if not ev.query()]
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(torch.device("cuda", self.device)))
+        self._frame_readers.append(ev)
+
+    def _wait_frame_readers(self):
+        """Before the frame's buffers are written or freed: wait, on the host, for the filters still reading them."""
+        for ev in self._frame_readers:
+            ev.synchronize()
+        self._frame_readers = []
+
+    def frame_readers_pending(self):
+        """How many filter calls that read the frame's own buffers may still be running (the next render, resize or close waits for them)."""
+        self._frame_readers = [ev for ev in self._frame_readers if not ev.query()]
+        return len(self._frame_readers)
+
     # ---- scene ----
     def load_scene(self, scene, device_bvh_build=False):
         h = self.h
+        self._wait_frame_readers()
         h.crth_set_device_bvh_build(1 if device_bvh_build else 0)   # BuildBVH on the GPU (same bytes as the host build)
         h.crth_set_asset_root((scene.asset_root or "").encode())
         h.crth_prepare_meshes()
@@ -168,6 +202,7 @@ class Session:
         return iv, ip, pos
 
     def resize(self, width, height):
+        self._wait_frame_readers()
         self.h.crth_resize(int(width), int(height))
         self._check("OnWindowResize")
         if width >= 16 and height >= 16:
@@ -178,6 +213,7 @@ class Session:
     def render(self, sun_angle=None, postprocess=False, shadows=False, pipelined=False, refraction=False, fxaa=False, ssaa=1, gbuffer=False):
         if ssaa not in (1, 2, 4):
             raise ValueError(f"ssaa must be 1, 2 or 4, not {ssaa!r}")
+        self._wait_frame_readers()
         self.h.crth_set_postprocess(1 if postprocess else 0)
         self.h.crth_set_shadows(1 if shadows else 0)          # extension, off upstream
         self.h.crth_set_refraction(1 if refraction else 0)    # extension, off upstream
@@ -241,6 +277,7 @@ class Session:
             iv, ip = np.ascontiguousarray(view[0], np.float32).reshape(16), np.ascontiguousarray(view[1], np.float32).reshape(16)
             a.cameraPos[0], a.cameraPos[1], a.cameraPos[2] = (float(x) for x in view[2])
         self._last_frame = "render_raw"
+        self._wait_frame_readers()
         _lib.check(self.hip.crt_render(C.byref(a), iv.ctypes.data_as(C.POINTER(C.c_float)), ip.ctypes.data_as(C.POINTER(C.c_float)), int(flags)), "crt_render")
 
     def sync(self):
@@ -374,11 +411,11 @@ class Session:
         batch = _lib.CrtRayBatch(origins.data_ptr(), dirs.data_ptr(), tmax.data_ptr() if tmax is not None else None, so, sd, n)
         closest = mode == "closest"
         out = torch.empty((n, 5), dtype=torch.int32, device=dev) if closest else torch.empty(n, dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = torch.cuda.current_stream(dev)
         flags = (_lib.CRT_RAYS_CLOSEST if closest else _lib.CRT_RAYS_OCCLUDED) | (_lib.CRT_RAYS_INCLUSIVE if inclusive else 0)
-        if not self.h.crth_trace_rays(C.byref(batch), flags, out.data_ptr(), stream):
+        if not self.h.crth_trace_rays(C.byref(batch), flags, out.data_ptr(), stream.cuda_stream):
             self._raise_and_clear("Renderer::TraceRays")
-        return RayHits(out) if closest else out.view(torch.bool)
+        return RayHits(out, stream) if closest else out.view(torch.bool)
 
     def rays_stats(self):
         """(64-ray chunks, chunks traced without the instance cull, workgroups launched) of the last trace_rays, after waiting for it."""
@@ -401,12 +438,13 @@ class Session:
         params = _lib.CrtShadeParams(float(self.scene.sun_angle if sun_angle is None else sun_angle), 0)
         rad = torch.empty((n, 4), dtype=torch.float32, device=dev) if radiance else None
         rec = torch.empty((n, 12), dtype=torch.int32, device=dev) if surface else None
+        stream = torch.cuda.current_stream(dev)
         if not self.h.crth_shade_rays(C.byref(batch), C.byref(params), rad.data_ptr() if radiance else None, rec.data_ptr() if surface else None,
-                                      torch.cuda.current_stream(dev).cuda_stream):
+                                      stream.cuda_stream):
             self._raise_and_clear("Renderer::ShadeRays")
         if radiance and surface:
-            return rad, SurfaceHits(rec)
-        return rad if radiance else SurfaceHits(rec)
+            return rad, SurfaceHits(rec, stream)
+        return rad if radiance else SurfaceHits(rec, stream)
 
     def shade_stats(self):
         """(64-ray chunks, chunks traced without the instance cull, workgroups launched) of the last shade_rays, after waiting for it."""
@@ -468,7 +506,8 @@ class Session:
     def _guided_frame(self, what, color, surface):
         """(color, guide layout, geometry, ids, albedo) as device addresses for `what` = "denoise" / "accumulate": color=None is the float
         frame of the last render(gbuffer=True) (waits for the frames in flight first); the guides are that frame's planes, or surface=, a
-        SurfaceHits of height * width records. ValueError: see Session.denoise."""
+        SurfaceHits of height * width records. ValueError: see Session.denoise. A caller that was handed a buffer of the frame's own (color is
+        None or surface is None) calls _frame_read_queued() behind the launch that reads it."""
         H, W = self.height, self.width
         if self.host_only or self.multi_device:
             raise ValueError(f"{what}: the buffers belong to one GPU; not available in a host-only session or one of several devices")
@@ -529,7 +568,9 @@ class Session:
                               torch.cuda.current_stream(dev).cuda_stream)
         if rc != 0:
             raise CrtError(f"crtd_denoise failed with {rc}: {lib.crtd_error_string(rc).decode()}")
-        return result       # (scratch goes back to torch's allocator, which hands a block out again in the order of the stream it was made on)
+        if color is None or surface is None:
+            self._frame_read_queued()
+        return result      # (scratch goes back to torch's allocator, which hands a block out again in the order of the stream it was made on)
 
     # ---- temporal accumulation on device buffers (libcrt_temporal.so: crtt_accumulate; stateless: the history is a TemporalHistory) ----
     def accumulate(self, history, color=None, *, surface=None, camera=None, alpha=0.2, moments_alpha=0.2, max_history=32, depth_tol=0.05,
@@ -562,6 +603,8 @@ class Session:
                                  torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
         if rc != 0:
             raise CrtError(f"crtt_accumulate failed with {rc}: {lib.crtt_error_string(rc).decode()}")
+        if color is None or surface is None:
+            self._frame_read_queued()
         history.current, history.camera, history.frames = 1 - history.current, cam, (1 if prev is None else history.frames + 1)
         return history.color, history.moments
 
@@ -595,9 +638,12 @@ class Session:
                              torch.cuda.current_stream(dev).cuda_stream)
         if rc != 0:
             raise CrtError(f"crtv_filter failed with {rc}: {lib.crtv_error_string(rc).decode()}")
+        if surface is None:
+            self._frame_read_queued()
         return (result, variance) if return_variance else result      # (scratch goes back to torch's allocator, in the order of its stream)
 
     def set_row_bands(self, band_rows, rank, n_ranks):
+        self._wait_frame_readers()
         self.h.crth_set_row_bands(int(band_rows), int(rank), int(n_ranks))
         self._check("SetRowBands")
         self._row_bands = int(n_ranks) > 1

@@ -334,11 +334,16 @@ int crt_map_host_frame(const void** ptr, size_t* bytes);
  * been reused: lets a consumer work on frame k-1 while frame k renders. */
 int crt_map_host_frame_back(int framesBack, const void** ptr, size_t* bytes);
 int crt_read_rays(float* dst, size_t floats);                 /* width*height*3, after WRITE_RAYS */
+/* The frame on the device. The library orders nothing against work of the caller's that reads this buffer or a crt_gbuffer_device_ptr
+ * plane on a stream of the caller's (crtd_denoise, crtt_accumulate, crtv_filter, a kernel of its own): order that stream -- wait for it,
+ * or for an event recorded behind the reader -- before the next crt_render that reuses the frame slot (a synchronous frame always reuses
+ * slot 0), and before crt_resize and crt_shutdown, which free it. */
 void* crt_output_device_ptr(void);
 /* The first-hit planes of the most recently submitted CRT_RENDER_GBUFFER frame (later frames without the flag leave them alone).
  * crt_read_gbuffer copies a whole plane (bytes = width * height * 16, or * 4 for CRT_GBUFFER_ALBEDO) after waiting for the frames in
  * flight; CRT_E_BAD_ARGUMENT for an unknown plane, a wrong size, or when no such frame has been submitted since crt_init or the last
- * crt_resize that changed the frame. crt_gbuffer_device_ptr: the plane on the device, NULL under the same conditions.
+ * crt_resize that changed the frame. crt_gbuffer_device_ptr: the plane on the device, NULL under the same conditions;
+ * a caller that reads it on a stream of its own orders that stream before the next crt_render that reuses the slot (crt_output_device_ptr).
  * crt_pick_pixel: one pixel of all three planes (36 bytes travel, not a frame) -- the GPU's answer to upstream's mouse pick
  * CPU_RayCast(camera.ScreenPointToRaySSE(mouse)) (Engine.cpp:112-126); CRT_E_OUT_OF_RANGE outside the frame. */
 int crt_read_gbuffer(int plane, void* dst, size_t bytes);

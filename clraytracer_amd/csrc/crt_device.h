@@ -422,7 +422,8 @@ enum : unsigned {               // closest_hit, trip_steps, Traversal
     TR_DIVIDE = 1u << 6,        // the reciprocals as divisions (recip)
     TR_WAVE_CULL = 1u << 7,     // ... and one test per instance and wave against the tile's ray cone before the per-lane loop (cone_rejects)
     TR_ROOT_PRETEST = 1u << 8,  // ... and the exact root step per surviving instance and wave behind it (root_pretest_misses)
-    TR_ALL = (1u << 9) - 1u
+    TR_BOUNCE_PRETEST = 1u << 9,    // ... and the same step per instance and wave for the reflection bounce's candidates (bounce_pretest_mask)
+    TR_ALL = (1u << 10) - 1u
 };
 enum : unsigned { CM_COUNT = 1u << 0, CM_DEFER_COUNT = 1u << 1, CM_ALL = (1u << 2) - 1u };                        // candidate_mask
 enum : unsigned { SB_DEFER_ENERGY = 1u << 0, SB_REFRACT = 1u << 1, SB_SKY_DOUBLE = 1u << 2, SB_ALL = (1u << 3) - 1u };   // shade_bounce
@@ -498,6 +499,11 @@ constexpr bool trace_root_pretests(bool WAVE_CULLS, bool GBUFFER, bool SHADOW, b
 {
     return WAVE_CULLS && !(SHADOW && REFRACT) && !(GBUFFER && !SHADOW);
 }
+
+// ---- who takes the same root step per wave for the reflection bounce's candidates (bounce_pretest_mask, behind candidate_mask at bounce 1) ----
+// trace_body: the kernels of trace_root_pretests, all six -- no row of the ledger moves with it (the shape of bounce_pretest_mask is what holds them).
+// Every other kernel keeps candidate_mask alone at bounce 1 and compiles to what it compiled to before.
+constexpr bool trace_bounce_pretests(bool ROOT_PRETESTS) { return ROOT_PRETESTS; }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -868,11 +874,26 @@ __device__ __forceinline__ bool cone_rejects(const WaveCone& c, v3 oc, float oc2
 //     is written: the stack rows are untouched, the uncounted kernels keep no counters.
 // (7d) Single-leaf meshes (hazard H3). A root ref with CRT_LEAF_BIT names triangles, not a pair record: there is no box to test, the traversal tests
 //     the triangles at once, and the bit stays.
-// (7e) Who does not take it. Counted and stamped launches, the instance tree, the ldstop form and bounce 1 (sharedOrigin false) never reach
+// (7e) Who does not take it. Counted and stamped launches, the instance tree and the ldstop form never reach
 //     staged_candidate_mask and compile to what they compiled to before; the counters of the wasted visits belong to the counted launch, which still
 //     makes them, and stay exact. Of the staged kernels, the waves that take no wave test (partial tiles, quadrant waves, scenes outside
 //     CRT_WAVE_CULL_MIN ... 64 instances) keep the path they had; a kernel the policy leaves out, and every kernel
 //     under -DCRT_NO_ROOT_PRETEST, compiles to the instructions of the wave test alone (the unit's assembly compared: no difference).
+// (7f) The reflection bounce (TR_BOUNCE_PRETEST, policy::trace_bounce_pretests, bounce_pretest_mask below: sharedOrigin false). The same function behind
+//     candidate_mask, every lane with its OWN origin o and direction d -- root_pretest_misses takes both per lane and never assumed o uniform; only
+//     `inst` must be wave-uniform, and it is the scalar loop's k. (7) holds lane by lane, and nothing in it asks where the origin lies:
+//     the origins of bounce 1 sit in the hit mesh's object space (hazard H6), and that does not enter the argument.
+//     (7a) Same bits: mo is xform_xyz of the lane's o exactly as Traversal::enter computes it from the o closest_hit was called with -- the same `o`
+//          and `d` are handed to both. The wave at bounce 1 holds only the lanes whose path continued (the others left the bounce loop and wait at
+//          its end): __ballot is over those lanes, and so is recip3's wave-level choice between division and short form -- any company of lanes
+//          gives the bits of 1.0f / x, as in (7a) above.
+//     (7b) Monotone: closest_hit starts every call, bounce 1's included, at c.distance = best0 (a fresh no_hit(best0)); the bound only falls from there.
+//     (7c) No state leaves a wasted entry: the argument is about one lane's Traversal and Closest and reads neither the origin nor the other lanes.
+//     (7d) Single-leaf roots: the leaf bit is read from the instance record before the origin is touched; the bit stays.
+//     A lane whose mask does not hold the instance computes along and clears nothing (`lo & ~bit` of a clear bit); a lane that is not live computes nothing.
+//     Who takes it: the kernels of the camera bounce's pre-test, in scenes of CRT_WAVE_CULL_MIN ... 64 instances, full waves or not (rank == lane is not
+//     used). Every other kernel, and every kernel under -DCRT_NO_BOUNCE_PRETEST, compiles to the instructions it had (the unit's assembly compared:
+//     no difference in any function).
 // ------------------------------------------------------------------------------------------------
 #ifdef CRT_NO_ROOT_PRETEST
 #define CRT_ROOT_PRETESTS(PRETEST) false  // A/B builds: the instructions of the wave test alone, everywhere
@@ -1016,6 +1037,39 @@ __device__ __forceinline__ unsigned long long staged_candidate_mask(const CrtDev
     return cand;
 }
 
+#ifdef CRT_NO_BOUNCE_PRETEST
+#define CRT_BOUNCE_PRETESTS(PRETEST) false  // A/B builds: candidate_mask alone at bounce 1, everywhere
+#else
+#define CRT_BOUNCE_PRETESTS(PRETEST) (PRETEST)
+#endif
+// The root pre-test of the reflection bounce (TR_BOUNCE_PRETEST, policy::trace_bounce_pretests; (7) above root_pretest_misses): behind candidate_mask,
+// once per instance that some live lane's mask `cand` still holds, every live lane runs root_pretest_misses on its OWN origin and direction and
+// clears the bit where it returns true. No cone and no staging: the instance index is wave-uniform, so both records come through the scalar cache,
+// and rank == lane is not used, so a wave of any occupancy takes it. Scenes of CRT_WAVE_CULL_MIN ... 64 instances, like the wave test (one chunk:
+// base == 0): below, a pre-test costs more than the entries of so few instances save; above, the instance tree serves the scene.
+// The shape is staged_candidate_mask's, whose items each moved rows of the ledger when left out: the mask in 32-bit halves, the instance count as an
+// opaque scalar in a one-compare guard, the bound as root_pretest_misses' opaque VGPR copy. With it no row moved in any of the six kernels
+// (the benchmark kernel: 64 VGPRs, no scratch, 78 SGPRs, 43 spilled, as recorded).
+template <bool DIVIDE>
+__device__ __forceinline__ unsigned long long bounce_pretest_mask(const CrtDevScene& S, v3 o, v3 d, uint32_t base, uint32_t cnt, unsigned long long cand, float best0)
+{
+    uint32_t lo = (uint32_t)cand, hi = (uint32_t)(cand >> 32);
+    uint32_t all = S.numInstances;
+    asm volatile("" : "+s"(all));
+    if (all - CRT_WAVE_CULL_MIN <= 64u - CRT_WAVE_CULL_MIN) {
+        const uint32_t nLo = cnt < 32u ? cnt : 32u;
+        for (uint32_t k = 0; k < nLo; ++k) {
+            const uint32_t bit = 1u << k;
+            if (__ballot((lo & bit) != 0u) != 0) lo &= root_pretest_misses<DIVIDE>(S, o, d, base + k, best0) ? ~bit : ~0u;
+        }
+        for (uint32_t k = 32; k < cnt; ++k) {
+            const uint32_t bit = 1u << (k - 32u);
+            if (__ballot((hi & bit) != 0u) != 0) hi &= root_pretest_misses<DIVIDE>(S, o, d, base + k, best0) ? ~bit : ~0u;
+        }
+    }
+    return ((unsigned long long)hi << 32) | lo;
+}
+
 // Candidate instances of one ray from the instance tree: up to CRT_TLAS_LIST indices (16 bits each, unordered, 0xFFFF =
 // empty) in four words; returns false when the lane would need more. The traversal stack is idle at this point
 // and serves as the tree stack. Scenes with hundreds of instances (upstream allows 401 and loops over all of them for
@@ -1120,7 +1174,8 @@ __device__ __forceinline__ void trip_steps(const CrtDevScene& S, const STK& stac
 // trip's options -- no run-time branch in a step; the instance cull stays on (sphere_culls' derivation, "Inclusive pass").
 // STAGE (policy::trace_stages_cull) + sharedOrigin (wave-uniform, run time: the camera bounce): the
 // chunk's mask comes from staged_candidate_mask -- the same mask, bit for bit. A run-time value, not a second instantiation: the trip
-// loop below exists once per kernel.
+// loop below exists once per kernel. With TR_BOUNCE_PRETEST the other bounce (sharedOrigin false) passes candidate_mask's mask through
+// bounce_pretest_mask, which clears the instances the lane's ray would leave at their root.
 template <unsigned OPTS, class STK>
 __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d, const STK& stack, LaneCounters& lc, float best0 = 99999.0f,
                                                bool chunkedOnly = false, bool sharedOrigin = false)
@@ -1131,6 +1186,7 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
     static_assert(!STAGE || (!COUNT && !ITERS && !ANYHIT && !TLAS && !STK::kTop), "staged cull terms: uncounted closest-hit traversals of one-wave workgroups");
     static_assert(STAGE || !has_opt(OPTS, TR_WAVE_CULL), "the wave test lives in the staged cull");
     static_assert(has_opt(OPTS, TR_WAVE_CULL) || !has_opt(OPTS, TR_ROOT_PRETEST), "the root pre-test runs over the wave test's survivors");
+    static_assert(has_opt(OPTS, TR_ROOT_PRETEST) || !has_opt(OPTS, TR_BOUNCE_PRETEST), "the reflection bounce's pre-test: kernels that take the camera bounce's");
     Closest c = no_hit(best0);
     Traversal<OPTS> T; T.reset();
 
@@ -1170,7 +1226,10 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
     for (uint32_t base = 0; base < S.numInstances; base += 64) {
         const uint32_t cnt = (S.numInstances - base) < 64u ? (S.numInstances - base) : 64u;
         unsigned long long cand;
-        if constexpr (STAGE) cand = sharedOrigin ? staged_candidate_mask<has_opt(OPTS, TR_WAVE_CULL), has_opt(OPTS, TR_ROOT_PRETEST), has_opt(OPTS, TR_DIVIDE)>(S, o, d, base, cnt, stack, best0)
+        if constexpr (STAGE && CRT_BOUNCE_PRETESTS(has_opt(OPTS, TR_BOUNCE_PRETEST))) {
+            if (sharedOrigin) cand = staged_candidate_mask<has_opt(OPTS, TR_WAVE_CULL), has_opt(OPTS, TR_ROOT_PRETEST), has_opt(OPTS, TR_DIVIDE)>(S, o, d, base, cnt, stack, best0);
+            else cand = bounce_pretest_mask<has_opt(OPTS, TR_DIVIDE)>(S, o, d, base, cnt, candidate_mask(S, o, d, base, cnt, lc), best0);
+        } else if constexpr (STAGE) cand = sharedOrigin ? staged_candidate_mask<has_opt(OPTS, TR_WAVE_CULL), has_opt(OPTS, TR_ROOT_PRETEST), has_opt(OPTS, TR_DIVIDE)>(S, o, d, base, cnt, stack, best0)
                                                  : candidate_mask(S, o, d, base, cnt, lc);
         else cand = candidate_mask<opt_if(COUNT, CM_COUNT) | opt_if(ANYHIT, CM_DEFER_COUNT)>(S, o, d, base, cnt, lc);
         // ANYHIT + COUNT: a culled instance is only "visited" (one pop, one inner visit upstream) if the ray gets that

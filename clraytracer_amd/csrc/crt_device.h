@@ -423,7 +423,8 @@ enum : unsigned {               // closest_hit, trip_steps, Traversal
     TR_WAVE_CULL = 1u << 7,     // ... and one test per instance and wave against the tile's ray cone before the per-lane loop (cone_rejects)
     TR_ROOT_PRETEST = 1u << 8,  // ... and the exact root step per surviving instance and wave behind it (root_pretest_misses)
     TR_BOUNCE_PRETEST = 1u << 9,    // ... and the same step per instance and wave for the reflection bounce's candidates (bounce_pretest_mask)
-    TR_ALL = (1u << 10) - 1u
+    TR_PRETEST_ENTRY = 1u << 10,    // ... and the camera bounce's pre-test leaves a lane inside its first surviving instance (root_pretest_enters)
+    TR_ALL = (1u << 11) - 1u
 };
 enum : unsigned { CM_COUNT = 1u << 0, CM_DEFER_COUNT = 1u << 1, CM_ALL = (1u << 2) - 1u };                        // candidate_mask
 enum : unsigned { SB_DEFER_ENERGY = 1u << 0, SB_REFRACT = 1u << 1, SB_SKY_DOUBLE = 1u << 2, SB_ALL = (1u << 3) - 1u };   // shade_bounce
@@ -504,6 +505,12 @@ constexpr bool trace_root_pretests(bool WAVE_CULLS, bool GBUFFER, bool SHADOW, b
 // trace_body: the kernels of trace_root_pretests, all six -- no row of the ledger moves with it (the shape of bounce_pretest_mask is what holds them).
 // Every other kernel keeps candidate_mask alone at bounce 1 and compiles to what it compiled to before.
 constexpr bool trace_bounce_pretests(bool ROOT_PRETESTS) { return ROOT_PRETESTS; }
+
+// ---- whose camera-bounce pre-test enters a lane's first surviving instance (root_pretest_enters, in place of root_pretest_misses there) ----
+// trace_body: the kernels of trace_root_pretests, except the two with shadow rays, whose row of the ledger it would move -- the supersampled kernel
+// (SGPR spills 52 -> 48) and the G-buffer kernel (59 -> 57). The four without shadow rays -- plain and supersampled, with and without refraction --
+// hold every row. Every other kernel keeps root_pretest_misses and compiles to what it compiled to before.
+constexpr bool trace_pretest_enters(bool ROOT_PRETESTS, bool SHADOW) { return ROOT_PRETESTS && !SHADOW; }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -894,6 +901,44 @@ __device__ __forceinline__ bool cone_rejects(const WaveCone& c, v3 oc, float oc2
 //     Who takes it: the kernels of the camera bounce's pre-test, in scenes of CRT_WAVE_CULL_MIN ... 64 instances, full waves or not (rank == lane is not
 //     used). Every other kernel, and every kernel under -DCRT_NO_BOUNCE_PRETEST, compiles to the instructions it had (the unit's assembly compared:
 //     no difference in any function).
+// (7g) The pre-test enters (TR_PRETEST_ENTRY, policy::trace_pretest_enters, root_pretest_enters below). A lane that survives the pre-test of its first
+//     instance would repeat, in the trip loop, the step the pre-test has just made: enter, then the root's inner step, in blocks the wave runs for
+//     however few lanes are at that step. The camera bounce's pre-test, which walks the wave's survivors in ascending k, keeps the step instead. A lane
+//     commits to k when (i) its mask holds bit k, (ii) it is inside no instance (T.active false: every lane starts so, T.reset in closest_hit, and a lane
+//     that has committed is inside), (iii) its mask holds no bit below k, (iv) the nearer child is hit. Its bit k is cleared and the trip loop starts
+//     with the lane at level 1 of k; every later instance is entered by `enter`, as before.
+//     1. Same state. The lane's first `enter` in the trip loop would be for the lowest bit of its mask -- k, by (i) and (iii) -- with
+//        bestSoFar = c.distance = best0: c is a fresh no_hit(best0) and nothing has touched it. The pre-test's bound is best0 (an opaque copy of the same
+//        bits). enter would set curInst = k, mo, md, inv (7a: the same functions on the same o and d; recip3 here in enter's own two-compare form),
+//        tr = {best0, 0, 0, 0}, ref = root, sp = 0, prot = 1, inters = 0, active = true. The trip's inner step on that root would compute dist1, dist2
+//        at tr.t = best0 -- the pre-test's two distances, (7a) -- and select on `dist1 > dist2`: n1 <= n2 afterwards, nearRef / farRef as here. It
+//        would push farRef at sp = 0 and set sp = 1 when n2 != 1e30, and otherwise leave sp = 0; then, n1 == 1e30: pop_next -- not taken here, by
+//        (iv), whatever n2 is; else ref = nearRef. inner touches no other field, and neither does the commit: curInst, mo, md, inv, tr, prot, inters,
+//        active, sp, stack row 0 under the same condition, ref -- bit for bit what the two steps leave. When both distances are 1e30 the bit is cleared
+//        as in (7); when n1 == 1e30 != n2 (possible only for a bound above 1e30, never for a frame's 99999) nothing is committed and the bit stays.
+//        The counted kernels make these steps themselves and count them: they do not take the pre-test (7e). The stamps (TR_ITERS) are not here either.
+//     2. Order. Per ray the instances are visited in ascending index (upstream's loop), and that order decides ties: `t < out.t` is strict, so of two
+//        instances hit at the same t the lower index keeps the hit. (iii) keeps the order: a lane may be inside k before the trip loop only if the
+//        trip loop would have entered k first. Bits below k that the pre-test cleared are instances the ray leaves at the root (7); a bit it left is
+//        either an inner root whose step passed for a lane that was not `first` -- then the lane is inside a lower instance already, (ii) -- or a
+//        single-leaf root (7d), whose bit is never cleared here and which is never committed to (root_pretest_enters returns before it reads the
+//        lane). A lane that holds the bit of a lower single-leaf instance therefore fails (iii) for every k above it and enters that instance first,
+//        through the trip loop. The test is `(lo & (bit | (bit - 1))) == bit` on the low half and, on the high half, the same with `lo == 0` besides.
+//        After the commit the lane's mask holds only bits above k (k cleared, none below), and `cand == 0` / find-first-set go on from there.
+//     3. Stack row 0. The staged cull terms lie in the wave's rows 0-5, and a lane's slot 0 is a word of row 0. The push is a store to the lane's own
+//        slot 0, written in the pre-test's loop: behind both `culls(k)` loops and behind the wave test's rowA[lane] read in the source. Two things
+//        keep it there. The compiler: the store and those loads go through pointers into the same LDS array (lds, rowA, rowB: s_stack) whose
+//        addresses it cannot tell apart -- they do alias -- so it may not move the store above a load, fence or no fence; and the store is
+//        control-dependent on the lane's mask, which is computed from the low half's loads. The hardware: LDS operations of one wave complete in the
+//        order they are issued, and in a one-wave workgroup nobody else reads these rows. Nothing reads rows 0-5 as cull terms after the pre-test: the scene has one 64-chunk (the guard on
+//        numInstances), so no restaging follows. The fence and wave barrier at the end of staged_candidate_mask stood between the last read and the
+//        first push of the trip loop; they still stand behind every read, and the pushes that now precede them are ordered behind the reads by the
+//        rule above. The first pop of a committed lane reads slot 0 in the trip loop, behind the barrier and behind the lane's own store.
+//     4. Who does not take it: the list of (7e) -- counted and stamped launches, the instance tree, ldstop, the refill, block, wavefront and query
+//        kernels never reach staged_candidate_mask; waves that take no wave test keep the path they had -- and, of the six kernels of the pre-test,
+//        the two with shadow rays (policy). The reflection bounce's pre-test (7f) commits nothing: bounce_pretest_mask is as it was. A kernel the
+//        policy leaves out, and every kernel under -DCRT_NO_PRETEST_ENTRY, compiles to the instructions it had (the unit's assembly compared
+//        function by function: no difference).
 // ------------------------------------------------------------------------------------------------
 #ifdef CRT_NO_ROOT_PRETEST
 #define CRT_ROOT_PRETESTS(PRETEST) false  // A/B builds: the instructions of the wave test alone, everywhere
@@ -929,13 +974,64 @@ __device__ __forceinline__ bool root_pretest_misses(const CrtDevScene& S, v3 o, 
     return (dist1 == 1e30f) & (dist2 == 1e30f);
 }
 
+#ifdef CRT_NO_PRETEST_ENTRY
+#define CRT_PRETEST_ENTERS(ENTER) false   // A/B builds: root_pretest_misses alone, everywhere
+#else
+#define CRT_PRETEST_ENTERS(ENTER) (ENTER)
+#endif
+// The committing form, (7g): root_pretest_misses' step, and a lane for which `first` holds (its mask holds `inst`, no lower instance, and it is
+// inside none yet) and whose root step goes on to a child keeps the step as its traversal state instead of throwing it away. Returns whether the
+// lane's bit is to be cleared: both children missed, or the lane is now inside the instance.
+// The shape is again what the ledger's rows allow. With root_pretest_misses' one-compare recip3 the benchmark kernel's spilled SGPRs moved with every
+// form of the commit tried: one branch 43 -> 42, all selects and an exec-masked ds_write 39, the branch without the stores of zeros 41, opaque VGPR
+// copies of `first`, of the take-flag or of the instance index 39 ... 42, the bound not opaque 42 (and a spilled VGPR with the selects). With recip3 in
+// enter's own two-compare form (the same bits, (7a)) the branch form, and the select form, hold every row
+// of the four kernels without shadow rays; the two with shadow rays move in every form (SGPR spills 59 -> 57, 52 -> 48) and are left out by the policy.
+template <bool DIVIDE, unsigned OWNER, class STK>
+__device__ __forceinline__ bool root_pretest_enters(const CrtDevScene& S, v3 o, v3 d, uint32_t inst, float best0, bool first, Traversal<OWNER>& T, const STK& stack)
+{
+    const crt_const_f32x4_ptr p = (crt_const_f32x4_ptr)(S.devInstances + inst);         // load_instance's uniform path
+    const crt_f32x4 r0 = p[0];
+    const uint32_t root = __float_as_uint(r0.w);
+    if (root & CRT_LEAF_BIT) return false;
+    const crt_f32x4 r1 = p[1], r2 = p[2], r3 = p[3];
+    CrtDevInstance I;
+    I.r0 = make_float4(r0.x, r0.y, r0.z, r0.w); I.r1 = make_float4(r1.x, r1.y, r1.z, r1.w);
+    I.r2 = make_float4(r2.x, r2.y, r2.z, r2.w); I.r3 = make_float4(r3.x, r3.y, r3.z, r3.w);
+    float bound = best0;
+    asm volatile("" : "+v"(bound));
+    const v3 mo = xform_xyz(I, o.x, o.y, o.z, 1.0f);
+    const v3 md = xform_xyz(I, d.x, d.y, d.z, 0.0f);
+    const v3 inv = recip3<DIVIDE>(md);                                                  // enter's own form: two compares
+    const crt_const_f32x4_ptr q = (crt_const_f32x4_ptr)(S.pairs + (size_t)root * 4);            // the scalar path of Traversal::inner
+    const crt_f32x4 a = q[0], b = q[1], c4 = q[2], e = q[3];
+    const float dist1 = intersect_aabb<false>(mo, inv, make_float4(a.x, a.y, a.z, a.w), make_float4(b.x, b.y, b.z, b.w), bound);
+    const float dist2 = intersect_aabb<false>(mo, inv, make_float4(c4.x, c4.y, c4.z, c4.w), make_float4(e.x, e.y, e.z, e.w), bound);
+    const bool miss = (dist1 == 1e30f) & (dist2 == 1e30f);
+    // Traversal::inner's select and its two conditions: the far child is pushed when it is hit, the lane goes on at the nearer child when that is hit
+    const bool sw = dist1 > dist2;
+    const float n1 = sw ? dist2 : dist1, n2 = sw ? dist1 : dist2;
+    const uint32_t nearRef = sw ? __float_as_uint(c4.w) : __float_as_uint(a.w), farRef = sw ? __float_as_uint(a.w) : __float_as_uint(c4.w);
+    const bool take = first & (n1 != 1e30f);
+    if (take) {
+        T.curInst = inst; T.mo = mo; T.md = md; T.inv = inv;
+        T.tr.t = bound; T.tr.u = 0.0f; T.tr.v = 0.0f; T.tr.tri = 0;
+        T.prot = 1; T.inters = 0; T.active = true;
+        T.sp = 0;
+        if (n2 != 1e30f) { stack.write(0, farRef); T.sp = 1; }
+        T.ref = nearRef;
+    }
+    return miss | take;
+}
+
 typedef uint32_t crt_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t crt_u32x2 __attribute__((ext_vector_type(2)));
 typedef crt_u32x4 __attribute__((address_space(3)))* crt_lds_u32x4_ptr;
 typedef crt_u32x2 __attribute__((address_space(3)))* crt_lds_u32x2_ptr;
 #define CRT_STAGE_ROWS 6
-template <bool WAVE, bool PRETEST, bool DIVIDE, class STK>
-__device__ __forceinline__ unsigned long long staged_candidate_mask(const CrtDevScene& S, v3 o, v3 d, uint32_t base, uint32_t cnt, const STK& stack, float best0)
+template <bool WAVE, bool PRETEST, bool DIVIDE, bool ENTER, unsigned OWNER, class STK>
+__device__ __forceinline__ unsigned long long staged_candidate_mask(const CrtDevScene& S, v3 o, v3 d, uint32_t base, uint32_t cnt, const STK& stack, float best0,
+                                                                    [[maybe_unused]] Traversal<OWNER>& T)
 {
     static_assert(STK::kLds >= CRT_STAGE_ROWS && CRT_BLOCK == 64, "the staged cull terms take six stack rows of a one-wave workgroup");
     // the wave's row 0. One-wave workgroups: lds = s_stack + threadIdx.x, so this folds to the array's address (the kernel's only LDS
@@ -1017,6 +1113,23 @@ __device__ __forceinline__ unsigned long long staged_candidate_mask(const CrtDev
             // The root pre-test, (7) above: over the same survivors, in the waves that took the wave test (`pre`; the others have all `cnt` bits in
             // `touch` and keep the path they had). A survivor no lane kept is skipped. The branch is the wave's, not the lanes': every lane computes
             // and a lane without the bit clears nothing -- one compare and a scalar branch instead of a saved and restored exec mask.
+            if constexpr (CRT_PRETEST_ENTERS(ENTER)) {
+                // (7g): the lane whose lowest remaining bit is `bit`, and which is inside no instance yet, may stay inside this one
+                for (uint32_t m = touchLo & pre; m != 0u; m &= m - 1u) {
+                    const uint32_t k = (uint32_t)__builtin_ctz(m), bit = 1u << k;
+                    if (__ballot((lo & bit) != 0u) != 0) {
+                        const bool first = ((lo & (bit | (bit - 1u))) == bit) & !T.active;
+                        lo &= root_pretest_enters<DIVIDE>(S, o, d, base + k, best0, first, T, stack) ? ~bit : ~0u;
+                    }
+                }
+                for (uint32_t m = touchHi & pre; m != 0u; m &= m - 1u) {
+                    const uint32_t k = (uint32_t)__builtin_ctz(m), bit = 1u << k;
+                    if (__ballot((hi & bit) != 0u) != 0) {
+                        const bool first = (lo == 0u) & ((hi & (bit | (bit - 1u))) == bit) & !T.active;
+                        hi &= root_pretest_enters<DIVIDE>(S, o, d, base + k + 32u, best0, first, T, stack) ? ~bit : ~0u;
+                    }
+                }
+            } else {
             for (uint32_t m = touchLo & pre; m != 0u; m &= m - 1u) {
                 const uint32_t k = (uint32_t)__builtin_ctz(m), bit = 1u << k;
                 if (__ballot((lo & bit) != 0u) != 0) lo &= root_pretest_misses<DIVIDE>(S, o, d, base + k, best0) ? ~bit : ~0u;
@@ -1024,6 +1137,7 @@ __device__ __forceinline__ unsigned long long staged_candidate_mask(const CrtDev
             for (uint32_t m = touchHi & pre; m != 0u; m &= m - 1u) {
                 const uint32_t k = (uint32_t)__builtin_ctz(m), bit = 1u << k;
                 if (__ballot((hi & bit) != 0u) != 0) hi &= root_pretest_misses<DIVIDE>(S, o, d, base + k + 32u, best0) ? ~bit : ~0u;
+            }
             }
         }
     } else {
@@ -1187,6 +1301,7 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
     static_assert(STAGE || !has_opt(OPTS, TR_WAVE_CULL), "the wave test lives in the staged cull");
     static_assert(has_opt(OPTS, TR_WAVE_CULL) || !has_opt(OPTS, TR_ROOT_PRETEST), "the root pre-test runs over the wave test's survivors");
     static_assert(has_opt(OPTS, TR_ROOT_PRETEST) || !has_opt(OPTS, TR_BOUNCE_PRETEST), "the reflection bounce's pre-test: kernels that take the camera bounce's");
+    static_assert(has_opt(OPTS, TR_ROOT_PRETEST) || !has_opt(OPTS, TR_PRETEST_ENTRY), "the entry is made by the camera bounce's pre-test");
     Closest c = no_hit(best0);
     Traversal<OPTS> T; T.reset();
 
@@ -1227,9 +1342,9 @@ __device__ __forceinline__ Closest closest_hit(const CrtDevScene& S, v3 o, v3 d,
         const uint32_t cnt = (S.numInstances - base) < 64u ? (S.numInstances - base) : 64u;
         unsigned long long cand;
         if constexpr (STAGE && CRT_BOUNCE_PRETESTS(has_opt(OPTS, TR_BOUNCE_PRETEST))) {
-            if (sharedOrigin) cand = staged_candidate_mask<has_opt(OPTS, TR_WAVE_CULL), has_opt(OPTS, TR_ROOT_PRETEST), has_opt(OPTS, TR_DIVIDE)>(S, o, d, base, cnt, stack, best0);
+            if (sharedOrigin) cand = staged_candidate_mask<has_opt(OPTS, TR_WAVE_CULL), has_opt(OPTS, TR_ROOT_PRETEST), has_opt(OPTS, TR_DIVIDE), has_opt(OPTS, TR_PRETEST_ENTRY)>(S, o, d, base, cnt, stack, best0, T);
             else cand = bounce_pretest_mask<has_opt(OPTS, TR_DIVIDE)>(S, o, d, base, cnt, candidate_mask(S, o, d, base, cnt, lc), best0);
-        } else if constexpr (STAGE) cand = sharedOrigin ? staged_candidate_mask<has_opt(OPTS, TR_WAVE_CULL), has_opt(OPTS, TR_ROOT_PRETEST), has_opt(OPTS, TR_DIVIDE)>(S, o, d, base, cnt, stack, best0)
+        } else if constexpr (STAGE) cand = sharedOrigin ? staged_candidate_mask<has_opt(OPTS, TR_WAVE_CULL), has_opt(OPTS, TR_ROOT_PRETEST), has_opt(OPTS, TR_DIVIDE), has_opt(OPTS, TR_PRETEST_ENTRY)>(S, o, d, base, cnt, stack, best0, T)
                                                  : candidate_mask(S, o, d, base, cnt, lc);
         else cand = candidate_mask<opt_if(COUNT, CM_COUNT) | opt_if(ANYHIT, CM_DEFER_COUNT)>(S, o, d, base, cnt, lc);
         // ANYHIT + COUNT: a culled instance is only "visited" (one pop, one inner visit upstream) if the ray gets that

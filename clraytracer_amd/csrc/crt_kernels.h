@@ -387,7 +387,8 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
     constexpr bool kWaveCulls = policy::trace_wave_culls(kStages, CASE == CRT_TRACE_PLAIN, GBUFFER, SHADOW, REFRACT);
     constexpr bool kRootPretests = policy::trace_root_pretests(kWaveCulls, GBUFFER, SHADOW, REFRACT);
     constexpr unsigned kPrimary = kRay | opt_if(STAMP, TR_ITERS) | opt_if(kStages, TR_STAGE) | opt_if(kWaveCulls, TR_WAVE_CULL) | opt_if(kRootPretests, TR_ROOT_PRETEST)
-                                | opt_if(policy::trace_bounce_pretests(kRootPretests), TR_BOUNCE_PRETEST);
+                                | opt_if(policy::trace_bounce_pretests(kRootPretests), TR_BOUNCE_PRETEST)
+                                | opt_if(policy::trace_pretest_enters(kRootPretests, SHADOW), TR_PRETEST_ENTRY);
     constexpr unsigned kShade = opt_if(SHADOW, SB_DEFER_ENERGY) | opt_if(REFRACT, SB_REFRACT)
                               | opt_if(policy::trace_sky_double(COUNT, GBUFFER, SHADOW, TLAS, REFRACT), SB_SKY_DOUBLE);
     LaneCounters lc; zero_counters(lc);

@@ -3,6 +3,7 @@
 #   clraytracer_amd/denoise/libcrt_denoise.so   the a-trous denoiser on device buffers (include/crt_denoise.h), gfx950 only, stateless
 #   clraytracer_amd/temporal/libcrt_temporal.so   temporal reprojection and accumulation on device buffers (include/crt_temporal.h), gfx950 only, stateless
 #   clraytracer_amd/vfilter/libcrt_vfilter.so   the variance-guided a-trous filter on device buffers (include/crt_vfilter.h), gfx950 only, stateless
+#   clraytracer_amd/motion/libcrt_motion.so   temporal accumulation that follows moving instances (include/crt_motion.h), gfx950 only, stateless
 #   clraytracer_amd/host/libcrt_host.so  C++ host mirror of Renderer/ResourceManager/AssetManager (+ include/crt_host.h)
 #   oracle/libcrt_oracle.so              CPU oracle (test infrastructure only)
 HIPCC ?= /opt/rocm/bin/hipcc
@@ -30,12 +31,14 @@ DENOISE_SO = clraytracer_amd/denoise/libcrt_denoise.so
 TEMPORAL_SO = clraytracer_amd/temporal/libcrt_temporal.so
 # likewise: the filter that reads the accumulation stage's moments plane
 VFILTER_SO = clraytracer_amd/vfilter/libcrt_vfilter.so
+# likewise: the accumulation stage again, reprojecting through each instance's own motion
+MOTION_SO = clraytracer_amd/motion/libcrt_motion.so
 
 EXAMPLE = examples/crt_headless
 
 UBENCH = tools/ubench/gather tools/ubench/chain tools/ubench/cumask tools/ubench/sky_index
 
-all: $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(TEMPORAL_SO) $(VFILTER_SO) $(EXAMPLE) $(UBENCH) oracle
+all: $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(TEMPORAL_SO) $(VFILTER_SO) $(MOTION_SO) $(EXAMPLE) $(UBENCH) oracle
 
 # vector-L1 gather microbenchmark (profiles/r01_ubench_gather.txt)
 tools/ubench/gather: tools/ubench/gather.hip
@@ -70,6 +73,9 @@ $(TEMPORAL_SO): clraytracer_amd/temporal/crt_temporal.hip include/crt_temporal.h
 $(VFILTER_SO): clraytracer_amd/vfilter/crt_vfilter.hip include/crt_vfilter.h
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $<
 
+$(MOTION_SO): clraytracer_amd/motion/crt_motion.hip include/crt_motion.h include/crt_temporal.h
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $<
+
 $(HOST_SO): $(HOST_SRC) $(HOST_HDR) $(HIP_SO)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRC) -Lclraytracer_amd/csrc -lcrt_hip -lrt -Wl,-rpath,'$$ORIGIN/../csrc'
 
@@ -77,7 +83,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(TEMPORAL_SO) $(VFILTER_SO) $(EXAMPLE) $(UBENCH)
+	rm -f $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(TEMPORAL_SO) $(VFILTER_SO) $(MOTION_SO) $(EXAMPLE) $(UBENCH)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -6,6 +6,7 @@
 * ``libcrt_denoise.so`` -- the stateless a-trous denoiser on device buffers (``include/crt_denoise.h``): HIP kernels for gfx950.
 * ``libcrt_temporal.so`` -- stateless temporal reprojection and accumulation on device buffers (``include/crt_temporal.h``): HIP for gfx950.
 * ``libcrt_vfilter.so`` -- the stateless variance-guided a-trous filter on device buffers (``include/crt_vfilter.h``): HIP for gfx950.
+* ``libcrt_motion.so`` -- stateless temporal accumulation that follows moving instances (``include/crt_motion.h``): HIP for gfx950.
 
 Loading fails loudly (``ImportError``) when a library has not been built: there is no Python or
 CPU fallback for the ray-trace path. Build with ``make`` at the repo root or
@@ -28,6 +29,7 @@ HOST_SO = os.path.join(_HERE, "host", "libcrt_host.so")
 DENOISE_SO = os.path.join(_HERE, "denoise", "libcrt_denoise.so")
 TEMPORAL_SO = os.path.join(_HERE, "temporal", "libcrt_temporal.so")
 VFILTER_SO = os.path.join(_HERE, "vfilter", "libcrt_vfilter.so")
+MOTION_SO = os.path.join(_HERE, "motion", "libcrt_motion.so")
 
 
 class CrtTraceArgs(C.Structure):
@@ -175,6 +177,27 @@ assert C.sizeof(CrtvFrame) == 56 and C.sizeof(CrtvParams) == 28      # static_as
 CRTV_OK, CRTV_E_BAD_ARGUMENT, CRTV_E_OUT_OF_RANGE = 0, -2, -3
 CRTV_GUIDES_PLANES, CRTV_GUIDES_SURFACE = 0, 1
 CRTV_DEMODULATE, CRTV_MATCH_INSTANCE = 1, 2                          # CrtvParams.flags
+
+
+
+class CrtmMotion(C.Structure):
+    """One instance's motion between two frames (include/crt_motion.h; made by crtm_motion): previous.k = dot3(point[4k .. 4k+2], p) + point[4k+3]
+    for a world point p of the instance now; a normal n now was m.k = dot3(normal[3k .. 3k+2], n) before normalising."""
+    _fields_ = [("kind", C.c_uint32), ("point", C.c_float * 12), ("normal", C.c_float * 9)]
+
+
+class CrtmMotionArgs(C.Structure):
+    """What crtm_accumulate takes beside crtt_accumulate's arguments: `count` CrtmMotion records in device memory (or None and 0) and the
+    float4 motion-vector plane to write (or None); pointers as integers."""
+    _fields_ = [("table", C.c_void_p), ("count", C.c_uint32), ("vectors", C.c_void_p)]
+
+
+# the table of crtm_motions as numpy sees it
+MOTION_DTYPE = np.dtype([("kind", "<u4"), ("point", "<f4", 12), ("normal", "<f4", 9)])
+# static_asserts of the same figures: motion/crt_motion.hip
+assert C.sizeof(CrtmMotion) == 88 and C.alignment(CrtmMotion) == 4 and C.sizeof(CrtmMotionArgs) == 24 and MOTION_DTYPE.itemsize == 88
+CRTM_STATIC, CRTM_MOVING, CRTM_NEW = 0, 1, 2                         # CrtmMotion.kind
+CRTM_MAX_COUNT = 65536
 
 _f = C.c_float
 _fp = C.POINTER(C.c_float)
@@ -349,6 +372,15 @@ VFILTER_API = {
     "crtv_error_string": (C.c_char_p, [C.c_int]),
 }
 
+# name -> (restype, argtypes); kept in sync with include/crt_motion.h (tests/test_motion_cpu.py checks it)
+MOTION_API = {
+    "crtm_motion": (C.c_int, [_fp, _fp, C.POINTER(CrtmMotion)]),
+    "crtm_motions": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    "crtm_accumulate": (C.c_int, [C.POINTER(CrttFrame), C.POINTER(CrttHistory), C.POINTER(CrttHistory), C.POINTER(CrttParams),
+                                  C.POINTER(CrtmMotionArgs), _vp]),
+    "crtm_error_string": (C.c_char_p, [C.c_int]),
+}
+
 
 def _bind(path, table):
     if not os.path.exists(path):
@@ -367,6 +399,7 @@ _host = None
 _denoise = None
 _temporal = None
 _vfilter = None
+_motion = None
 
 
 def hip():
@@ -408,6 +441,39 @@ def vfilter():
     if _vfilter is None:
         _vfilter = _bind(VFILTER_SO, VFILTER_API)
     return _vfilter
+
+
+def motion():
+    """libcrt_motion.so (include/crt_motion.h). Stateless and independent of the other five; loading does not touch the GPU."""
+    global _motion
+    if _motion is None:
+        _motion = _bind(MOTION_SO, MOTION_API)
+    return _motion
+
+
+def instance_records(instances, name="instances"):
+    """`instances` as a contiguous (n,) array of INSTANCE_DTYPE: given as such records, or as (n, 4, 4) float32 inverse transforms."""
+    a = np.asarray(instances)
+    if a.dtype == INSTANCE_DTYPE and a.ndim == 1:
+        return np.ascontiguousarray(a)
+    if a.dtype == np.float32 and a.ndim == 3 and a.shape[1:] == (4, 4):
+        rec = np.zeros(len(a), INSTANCE_DTYPE)
+        rec["inv"] = a
+        return rec
+    raise ValueError(f"{name}: (n,) CrtMeshInstance records (_lib.INSTANCE_DTYPE) or (n, 4, 4) float32 inverse transforms are required, "
+                     f"not dtype {a.dtype}, shape {a.shape}")
+
+
+def crtm_motions(prev, cur):
+    """crtm_motions: the (len(cur),) MOTION_DTYPE table of the instances `cur` against `prev` (both as instance_records makes them; prev may be
+    None or shorter: the instances beyond it are CRTM_NEW); CrtError when it refuses a matrix."""
+    table = np.zeros(len(cur), MOTION_DTYPE)
+    n_prev = 0 if prev is None else len(prev)
+    rc = motion().crtm_motions(prev.ctypes.data if n_prev else None, n_prev, cur.ctypes.data if len(cur) else None, len(cur),
+                               table.ctypes.data if len(cur) else None)
+    if rc != 0:
+        raise CrtError(f"crtm_motions failed with {rc}: {motion().crtm_error_string(rc).decode()}")
+    return table
 
 
 def crtt_camera(inv_view, inv_proj, pos, width, height):

@@ -65,7 +65,8 @@ class TemporalHistory:
     """The history of Session.accumulate: two sets of planes (color, moments {m1, m2, N, variance}, geometry {n, t}: (height, width, 4) float32;
     with match_instance=True also instance: (height, width) int32) as torch tensors on the session's device, of which each accumulate reads
     one and writes the other, and the CrttCamera of the set last written. color, moments, geometry, instance: the set last written; frames:
-    how many frames went in since the last reset. A history belongs to the session's size at its making: after a resize make a new one."""
+    how many frames went in since the last reset; instances: the CrtMeshInstance records the last frame went in with (accumulate's
+    instances=), or None. A history belongs to the session's size at its making: after a resize make a new one."""
 
     def __init__(self, session, match_instance=False):
         import torch
@@ -82,7 +83,7 @@ class TemporalHistory:
             for name, plane, _, _ in planes:
                 assert one[name].numel() * one[name].element_size() == lib.crtt_history_bytes(self.width, self.height, plane), name
             self.sets.append(one)
-        self.current, self.camera, self.frames = 0, None, 0
+        self.current, self.camera, self.frames, self.instances = 0, None, 0, None
 
     def _struct(self, which, camera):
         s = self.sets[which]
@@ -574,7 +575,7 @@ class Session:
 
     # ---- temporal accumulation on device buffers (libcrt_temporal.so: crtt_accumulate; stateless: the history is a TemporalHistory) ----
     def accumulate(self, history, color=None, *, surface=None, camera=None, alpha=0.2, moments_alpha=0.2, max_history=32, depth_tol=0.05,
-                   normal_cos=0.9, clamp=False, reset=False):
+                   normal_cos=0.9, clamp=False, reset=False, instances=None, return_vectors=False):
         """One frame into `history` (a TemporalHistory of this session's size), by the definition of include/crt_temporal.h: the history is
         fetched where each pixel's surface was in the previous frame -- four taps, each counting when it is a hit whose distance is within
         depth_tol (relative) of the reprojected one and whose normal's cosine is at least normal_cos (and, for a history made with
@@ -585,11 +586,24 @@ class Session:
         same ValueErrors. camera=(invView, invProj, pos): the matrices the frame was shot with; default: self.camera().
         Enqueues on torch.cuda.current_stream() without synchronising, swaps the history's two sets and returns (color, moments): two
         (height, width, 4) float32 tensors, moments = {m1, m2, N, variance} of the luminance. They are the history's own planes: valid until
-        the next accumulate but one into it; color is a valid color= for Session.denoise."""
+        the next accumulate but one into it; color is a valid color= for Session.denoise.
+        instances=None: the reprojection follows the camera only (libcrt_temporal.so), which is right where no surface moved. instances=: the
+        CrtMeshInstance records the frame was rendered with -- an (n,) array of 80-byte records as Session.arenas()["instances"] holds them, or
+        (n, 4, 4) float32 inverse transforms -- and the history is fetched where each pixel's instance was in the previous frame, by the
+        definition of include/crt_motion.h (libcrt_motion.so): a table of one motion record per instance is made against history.instances, the
+        copy kept from the previous accumulate (an instance beyond it is new and has no history), and uploaded on the current stream; the new
+        copy is kept in the history. ValueError: records of another shape or dtype; a history whose last frame went in without instances=
+        and is not being reset (the previous transforms are unknown). return_vectors=True: returns (color, moments, vectors), vectors a fresh
+        (height, width, 4) float32 tensor {fx - x, fy - y, dist, state} per pixel: where the history was fetched relative to the pixel, the
+        reprojected distance, and 2 = history kept, 1 = reprojected on the previous screen but no history, 0 (with zeros) = nothing to fetch."""
         import torch
         H, W = self.height, self.width
         if not isinstance(history, TemporalHistory) or (history.width, history.height, history.device) != (W, H, self.device):
             raise ValueError(f"history: a TemporalHistory of {W} x {H} on cuda:{self.device} is required")
+        records = None if instances is None else _lib.instance_records(instances)
+        if records is not None and not reset and history.camera is not None and history.instances is None:
+            raise ValueError("instances=: the history's last frame went in without instances=, so the previous transforms are unknown "
+                             "(pass reset=True to start over from this frame)")
         ptr, guides, geometry, ids, _ = self._guided_frame("accumulate", color, surface)
         iv, ip, pos = self.camera() if camera is None else camera
         cam = _lib.crtt_camera(iv, ip, pos, W, H)
@@ -598,15 +612,40 @@ class Session:
         nxt = history._struct(1 - history.current, cam)
         params = _lib.CrttParams((_lib.CRTT_MATCH_INSTANCE if history.match_instance else 0) | (_lib.CRTT_CLAMP if clamp else 0), float(alpha),
                                  float(moments_alpha), float(max_history), float(depth_tol), float(normal_cos))
-        lib = _lib.temporal()
-        rc = lib.crtt_accumulate(C.byref(frame), None if prev is None else C.byref(prev), C.byref(nxt), C.byref(params),
-                                 torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
-        if rc != 0:
-            raise CrtError(f"crtt_accumulate failed with {rc}: {lib.crtt_error_string(rc).decode()}")
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        vectors = None
+        if records is None and not return_vectors:
+            lib = _lib.temporal()
+            rc = lib.crtt_accumulate(C.byref(frame), None if prev is None else C.byref(prev), C.byref(nxt), C.byref(params), stream)
+            if rc != 0:
+                raise CrtError(f"crtt_accumulate failed with {rc}: {lib.crtt_error_string(rc).decode()}")
+        else:
+            lib = _lib.motion()
+            table = None        # a reset, or no instances=: every pixel reprojects through the camera alone
+            if records is not None and prev is not None and len(records):
+                table = torch.from_numpy(_lib.crtm_motions(history.instances, records).view(np.uint8)).to(dev)
+            vectors = torch.empty((H, W, 4), dtype=torch.float32, device=dev) if return_vectors else None
+            margs = _lib.CrtmMotionArgs(table.data_ptr() if table is not None else None, len(records) if table is not None else 0,
+                                        vectors.data_ptr() if return_vectors else None)
+            rc = lib.crtm_accumulate(C.byref(frame), None if prev is None else C.byref(prev), C.byref(nxt), C.byref(params), C.byref(margs), stream)
+            if rc != 0:
+                raise CrtError(f"crtm_accumulate failed with {rc}: {lib.crtm_error_string(rc).decode()}")
+            # (table goes back to torch's allocator, which hands a block out again in the order of the stream it was made on)
         if color is None or surface is None:
             self._frame_read_queued()
         history.current, history.camera, history.frames = 1 - history.current, cam, (1 if prev is None else history.frames + 1)
-        return history.color, history.moments
+        history.instances = None if records is None else records.copy()
+        return (history.color, history.moments, vectors) if return_vectors else (history.color, history.moments)
+
+    def upload_instances(self, records, first=0):
+        """crt_upload_instances: replace the instance records from `first` on by `records` -- (n,) CrtMeshInstance records as
+        Session.arenas()["instances"] holds them -- for every later frame; it waits for no frame in flight."""
+        records = np.asarray(records)
+        if records.dtype != _lib.INSTANCE_DTYPE or records.ndim != 1:
+            raise ValueError(f"records: an (n,) array of _lib.INSTANCE_DTYPE is required, not dtype {records.dtype}, shape {records.shape}")
+        records = np.ascontiguousarray(records)
+        _lib.check(self.hip.crt_upload_instances(records.ctypes.data, int(first), len(records)), "crt_upload_instances")
 
     # ---- variance-guided filtering on device buffers (libcrt_vfilter.so: crtv_filter; stateless, so there is no Renderer method to mirror) ----
     def filter_variance(self, color, moments, *, iterations=4, depth_tol=0.05, normal_cos=0.9, luma_sigma=4.0, luma_floor=1e-4, min_history=4,

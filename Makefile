@@ -6,6 +6,7 @@
 #   clraytracer_amd/motion/libcrt_motion.so   temporal accumulation that follows moving instances (include/crt_motion.h), gfx950 only, stateless
 #   clraytracer_amd/host/libcrt_host.so  C++ host mirror of Renderer/ResourceManager/AssetManager (+ include/crt_host.h)
 #   oracle/libcrt_oracle.so              CPU oracle (test infrastructure only)
+# The four stateless libraries are one .hip unit each over the headers of clraytracer_amd/image/ (the steps they share; no library of its own).
 HIPCC ?= /opt/rocm/bin/hipcc
 CXX ?= g++
 ARCH ?= gfx950
@@ -33,6 +34,12 @@ TEMPORAL_SO = clraytracer_amd/temporal/libcrt_temporal.so
 VFILTER_SO = clraytracer_amd/vfilter/libcrt_vfilter.so
 # likewise: the accumulation stage again, reprojecting through each instance's own motion
 MOTION_SO = clraytracer_amd/motion/libcrt_motion.so
+
+# the headers the four share, compiled into each: device and host steps; the environment switches (not motion's); the accumulate kernel of
+# temporal and motion
+IMAGE_HDR = clraytracer_amd/image/crt_image_device.h clraytracer_amd/image/crt_image_host.h
+IMAGE_ENV_HDR = clraytracer_amd/image/crt_image_env.h
+ACCUMULATE_HDR = clraytracer_amd/image/crt_accumulate.h include/crt_temporal.h include/crt_motion.h
 
 EXAMPLE = examples/crt_headless
 
@@ -64,16 +71,16 @@ $(EXAMPLE): examples/headless_main.cpp $(HOST_SO)
 $(HIP_SO): $(wildcard clraytracer_amd/csrc/*.h) $(HIP_SRC) include/crt_api.h include/crt_debug.h include/crt_types.h
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $(HIP_SRC)
 
-$(DENOISE_SO): clraytracer_amd/denoise/crt_denoise.hip include/crt_denoise.h
+$(DENOISE_SO): clraytracer_amd/denoise/crt_denoise.hip include/crt_denoise.h $(IMAGE_HDR) $(IMAGE_ENV_HDR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $<
 
-$(TEMPORAL_SO): clraytracer_amd/temporal/crt_temporal.hip include/crt_temporal.h
+$(TEMPORAL_SO): clraytracer_amd/temporal/crt_temporal.hip $(ACCUMULATE_HDR) $(IMAGE_HDR) $(IMAGE_ENV_HDR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $<
 
-$(VFILTER_SO): clraytracer_amd/vfilter/crt_vfilter.hip include/crt_vfilter.h
+$(VFILTER_SO): clraytracer_amd/vfilter/crt_vfilter.hip include/crt_vfilter.h $(IMAGE_HDR) $(IMAGE_ENV_HDR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $<
 
-$(MOTION_SO): clraytracer_amd/motion/crt_motion.hip include/crt_motion.h include/crt_temporal.h
+$(MOTION_SO): clraytracer_amd/motion/crt_motion.hip $(ACCUMULATE_HDR) $(IMAGE_HDR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $<
 
 $(HOST_SO): $(HOST_SRC) $(HOST_HDR) $(HIP_SO)

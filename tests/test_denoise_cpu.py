@@ -21,9 +21,10 @@ if not os.path.exists(_lib.DENOISE_SO):
 
 import denoise_ref as ref
 from test_abi import HIP_OWNING_CALLS
-from util import bits, kernel_resource_rows, resource_line
+from util import bits, kernel_resource_rows, resource_line, unit_sources
 
 DENOISE_DIR = os.path.join(ROOT, "clraytracer_amd", "denoise")
+IMAGE_DIR = os.path.join(ROOT, "clraytracer_amd", "image")          # the headers the image libraries share, compiled into each
 A = 0x10000                                      # dummy device addresses, 64 KiB apart: a refusal looks at none of them
 
 
@@ -200,7 +201,11 @@ def test_pass_kernels_need_no_scratch_no_spill_and_no_agprs():
 def test_the_library_owns_no_hip_object_and_follows_the_recipe():
     sources = sorted(f for f in os.listdir(DENOISE_DIR) if f.endswith((".h", ".hip", ".cpp", ".hpp")))
     assert sources == ["crt_denoise.hip"]
-    for path in [os.path.join(DENOISE_DIR, f) for f in sources] + [os.path.join(ROOT, "include", "crt_denoise.h")]:
+    # the unit and every in-tree header it includes, transitively: the shared steps of clraytracer_amd/image/ are this library's source too
+    scanned = unit_sources("clraytracer_amd/denoise/crt_denoise.hip")
+    assert {os.path.join(DENOISE_DIR, f) for f in sources} | {os.path.join(ROOT, "include", "crt_denoise.h"), os.path.join(IMAGE_DIR, "crt_image_device.h"),
+                                                            os.path.join(IMAGE_DIR, "crt_image_host.h"), os.path.join(IMAGE_DIR, "crt_image_env.h")} <= set(scanned)
+    for path in scanned:
         text = open(path).read()
         text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
         text = re.sub(r"//[^\n]*", "", text)

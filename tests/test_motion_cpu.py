@@ -26,9 +26,10 @@ import motion_ref as ref
 import temporal_ref
 import test_temporal_cpu as sibling                     # its table of crtt_accumulate's refusals: every one is a refusal of crtm_accumulate
 from test_abi import HIP_OWNING_CALLS
-from util import bits, kernel_resource_rows, resource_line
+from util import bits, kernel_resource_rows, resource_line, unit_sources
 
 MOTION_DIR = os.path.join(ROOT, "clraytracer_amd", "motion")
+IMAGE_DIR = os.path.join(ROOT, "clraytracer_amd", "image")          # the headers the image libraries share, compiled into each
 A = 0x10000                                      # dummy device addresses, 64 KiB apart: a refusal looks at none of them
 NAMES = ["crtm_accumulate", "crtm_error_string", "crtm_motion", "crtm_motions"]
 BAD = _lib.CRTT_E_BAD_ARGUMENT
@@ -444,36 +445,49 @@ def test_the_hand_made_table_reaches_every_kind():
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or shutil.which("c++filt") is None, reason="needs hipcc and c++filt")
 def test_kernels_need_no_scratch_no_spill_no_agprs_and_keep_the_siblings_occupancy():
     source = open(os.path.join(MOTION_DIR, "crt_motion.hip")).read()
-    const = {k: int(v) for k, v in re.findall(r"^#define (CRTM_TILE_W|CRTM_TILE_H|CRTM_HALO|CRTM_TABLE_LDS|CRTM_UNSTAGED_PAD) (\d+)\b", source, re.M)}
+    # the unit's own constants, the tile's from the shared device steps and the halo from the shared kernel's header
+    defines = lambda text, names: {k: int(v) for k, v in re.findall(r"^#define (%s) (\d+)\b" % names, text, re.M)}
+    const = {**defines(source, "CRTM_TABLE_LDS|CRTM_UNSTAGED_PAD"), **defines(open(os.path.join(IMAGE_DIR, "crt_image_device.h")).read(), "CRTI_TILE_W|CRTI_TILE_H"),
+             **defines(open(os.path.join(IMAGE_DIR, "crt_accumulate.h")).read(), "CRT_ACCUMULATE_HALO")}
     assert len(const) == 5
-    tile = (const["CRTM_TILE_W"] + 2 * const["CRTM_HALO"]) * (const["CRTM_TILE_H"] + 2 * const["CRTM_HALO"]) * 16 + const["CRTM_TABLE_LDS"]
+    tile = (const["CRTI_TILE_W"] + 2 * const["CRT_ACCUMULATE_HALO"]) * (const["CRTI_TILE_H"] + 2 * const["CRT_ACCUMULATE_HALO"]) * 16 + const["CRTM_TABLE_LDS"]
     rows = kernel_resource_rows(source=os.path.join(MOTION_DIR, "crt_motion.hip"))
     for n, r in rows:
         print(resource_line(n, r))
     tf = ("false", "true")
-    assert sorted(n for n, _ in rows) == sorted(f"crtm_accumulate_kernel<{s}, {l}>" for s in tf for l in tf)      # <SURFACE, STAGE> and nothing else
+    # instantiations over this library's pass of the template it shares with libcrt_temporal.so: <PASS, SURFACE, GATED, STAGE>, always gated, and nothing else
+    assert sorted(n for n, _ in rows) == sorted(f"crt_accumulate_kernel<CrtmPass, {s}, true, {l}>" for s in tf for l in tf)
     for n, r in rows:
         assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r.get("SGPRs Spill", 0) == 0 and r["AGPRs"] == 0, resource_line(n, r)
         assert r["LDS Size"] == (tile if n.endswith("true>") else 0), resource_line(n, r)       # nothing but the staged tile
-        assert r["Occupancy"] >= 5, resource_line(n, r)                         # crtt_accumulate_kernel<*, true, *>'s
+        assert r["Occupancy"] >= 5, resource_line(n, r)                         # crt_accumulate_kernel<CrttPass, *, true, *>'s
     # The unstaged kernels' registers would allow 8 waves per SIMD, which measures slower than 5: they are launched with a pad of
     # dynamic LDS they never touch (no remark counts it) that holds a CU's 160 KiB to 5 workgroups of 4 waves; the staged ones with none
     assert (160 * 1024) // const["CRTM_UNSTAGED_PAD"] == 5 and const["CRTM_UNSTAGED_PAD"] % 1024 == 0
-    assert "crtm_accumulate_kernel<SURFACE, false><<<grid, CRTM_BLOCK, CRTM_UNSTAGED_PAD, stream>>>" in source
-    assert "crtm_accumulate_kernel<SURFACE, true><<<grid, CRTM_BLOCK, 0, stream>>>" in source and "extern __shared__" not in source
+    assert "crt_accumulate_kernel<CrtmPass, SURFACE, true, false><<<grid, CRTI_BLOCK, CRTM_UNSTAGED_PAD, stream>>>" in source
+    assert "crt_accumulate_kernel<CrtmPass, SURFACE, true, true><<<grid, CRTI_BLOCK, 0, stream>>>" in source
+    assert not any("extern __shared__" in open(path).read() for path in unit_sources("clraytracer_amd/motion/crt_motion.hip"))
 
 
 def test_the_library_owns_no_hip_object_and_follows_the_recipe():
     sources = sorted(f for f in os.listdir(MOTION_DIR) if f.endswith((".h", ".hip", ".cpp", ".hpp")))
     assert sources == ["crt_motion.hip"]
-    for path in [os.path.join(MOTION_DIR, f) for f in sources] + [os.path.join(ROOT, "include", "crt_motion.h")]:
+    # what the image libraries share, exactly: headers that are compiled into each library; this one leaves out the environment's
+    assert sorted(os.listdir(IMAGE_DIR)) == ["crt_accumulate.h", "crt_image_device.h", "crt_image_env.h", "crt_image_host.h"]
+    # the unit and every in-tree header it includes, transitively: the shared steps of clraytracer_amd/image/ are this library's source too
+    scanned = unit_sources("clraytracer_amd/motion/crt_motion.hip")
+    assert {os.path.join(MOTION_DIR, f) for f in sources} | {os.path.join(ROOT, "include", "crt_motion.h"), os.path.join(IMAGE_DIR, "crt_image_device.h"),
+                                                            os.path.join(IMAGE_DIR, "crt_image_host.h"), os.path.join(IMAGE_DIR, "crt_accumulate.h")} <= set(scanned)
+    for path in scanned:
         text = open(path).read()
         text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
         text = re.sub(r"//[^\n]*", "", text)
         assert not re.findall(HIP_OWNING_CALLS, text), path
         assert not re.findall(r"\bhip(DeviceSynchronize|StreamSynchronize|EventSynchronize|Memcpy\w*|Memset\w*)\s*\(", text), path     # nor waits or copies
         assert not re.findall(r"\basm\b|getenv", text), path                  # plain C++ stores, and no switch in the environment
+    assert os.path.join(IMAGE_DIR, "crt_image_env.h") not in scanned
     assert len(re.findall(r"<<<", open(os.path.join(MOTION_DIR, "crt_motion.hip")).read())) == 2     # one launch per call: STAGE or not
+    assert sum(len(re.findall(r"<<<", open(path).read())) for path in scanned) == 2                  # ... and none in a header
     if shutil.which("make"):
         p = subprocess.run(["make", "-n", "-W", "clraytracer_amd/motion/crt_motion.hip", _lib.MOTION_SO.replace(ROOT + os.sep, "")], cwd=ROOT,
                            stdout=subprocess.PIPE, text=True, check=True)

@@ -25,9 +25,10 @@ import gbuffer_ref
 import oracle_lib
 import temporal_ref as ref
 from test_abi import HIP_OWNING_CALLS
-from util import bits, kernel_resource_rows, resource_line
+from util import bits, kernel_resource_rows, resource_line, unit_sources
 
 TEMPORAL_DIR = os.path.join(ROOT, "clraytracer_amd", "temporal")
+IMAGE_DIR = os.path.join(ROOT, "clraytracer_amd", "image")          # the headers the image libraries share, compiled into each
 A = 0x10000                                      # dummy device addresses, 64 KiB apart: a refusal looks at none of them
 NAMES = ["crtt_accumulate", "crtt_camera", "crtt_error_string", "crtt_history_bytes"]
 
@@ -420,7 +421,8 @@ def test_kernels_need_no_scratch_no_spill_and_no_agprs():
         print(resource_line(n, r))
     # per guide layout: the taps' colour loaded with the geometry or behind its test, the clamp's pixels through L1 or from a 34 x 10 tile in LDS
     tf = ("false", "true")
-    assert sorted(n for n, _ in rows) == sorted(f"crtt_accumulate_kernel<{s}, {g}, {l}>" for s in tf for g in tf for l in tf)
+    # (instantiations over this library's pass of the template it shares with libcrt_motion.so: <PASS, SURFACE, GATED, STAGE>, and nothing else)
+    assert sorted(n for n, _ in rows) == sorted(f"crt_accumulate_kernel<CrttPass, {s}, {g}, {l}>" for s in tf for g in tf for l in tf)
     for n, r in rows:
         assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0 and r.get("SGPRs Spill", 0) == 0 and r["AGPRs"] == 0, resource_line(n, r)
         assert r["LDS Size"] == (34 * 10 * 16 if n.endswith("true>") else 0), resource_line(n, r)     # nothing but the staged tile
@@ -430,12 +432,18 @@ def test_kernels_need_no_scratch_no_spill_and_no_agprs():
 def test_the_library_owns_no_hip_object_and_follows_the_recipe():
     sources = sorted(f for f in os.listdir(TEMPORAL_DIR) if f.endswith((".h", ".hip", ".cpp", ".hpp")))
     assert sources == ["crt_temporal.hip"]
-    for path in [os.path.join(TEMPORAL_DIR, f) for f in sources] + [os.path.join(ROOT, "include", "crt_temporal.h")]:
+    # the unit and every in-tree header it includes, transitively: the shared steps of clraytracer_amd/image/ are this library's source too
+    scanned = unit_sources("clraytracer_amd/temporal/crt_temporal.hip")
+    assert {os.path.join(TEMPORAL_DIR, f) for f in sources} | {os.path.join(ROOT, "include", "crt_temporal.h"), os.path.join(IMAGE_DIR, "crt_image_device.h"),
+                                                            os.path.join(IMAGE_DIR, "crt_image_host.h"), os.path.join(IMAGE_DIR, "crt_image_env.h"), os.path.join(IMAGE_DIR, "crt_accumulate.h")} <= set(scanned)
+    for path in scanned:
         text = open(path).read()
         text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
         text = re.sub(r"//[^\n]*", "", text)
         assert not re.findall(HIP_OWNING_CALLS, text), path
         assert not re.findall(r"\bhip(DeviceSynchronize|StreamSynchronize|EventSynchronize|Memcpy\w*|Memset\w*)\s*\(", text), path     # nor waits or copies
+    assert sum(len(re.findall(r"<<<", open(path).read())) for path in scanned) == 4          # <GATED, STAGE>, all in the unit itself
+    assert len(re.findall(r"<<<", open(os.path.join(TEMPORAL_DIR, "crt_temporal.hip")).read())) == 4
     if shutil.which("make"):
         p = subprocess.run(["make", "-n", "-W", "clraytracer_amd/temporal/crt_temporal.hip", _lib.TEMPORAL_SO.replace(ROOT + os.sep, "")], cwd=ROOT,
                            stdout=subprocess.PIPE, text=True, check=True)

@@ -1,6 +1,7 @@
 """Shared helpers for the parity tests."""
 import importlib.util
 import os
+import re
 
 import numpy as np
 
@@ -10,6 +11,21 @@ _kernel_resources = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(_kernel_resources)
 kernel_resources, kernel_resource_rows, resource_line = _kernel_resources.kernel_resources, _kernel_resources.kernel_resource_rows, _kernel_resources.resource_line
 HIP_UNITS = _kernel_resources.HIP_UNITS
+
+
+def unit_sources(unit):
+    """`unit` (a path below the repository) and every in-tree file it includes by #include "...", transitively: what the compiler reads of this
+    repository when it builds the unit, as sorted absolute paths. A source scan that reads these follows code that moves into a shared header."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    seen, todo = set(), [os.path.join(root, unit)]
+    while todo:
+        path = os.path.normpath(todo.pop())
+        if path in seen:
+            continue
+        assert path.startswith(root + os.sep) and os.path.isfile(path), path
+        seen.add(path)
+        todo += [os.path.join(os.path.dirname(path), inc) for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M)]
+    return sorted(seen)
 
 
 def seeded_rays(scene_arenas, cam_pos, n, seed):

@@ -7,6 +7,7 @@
 * ``libcrt_temporal.so`` -- stateless temporal reprojection and accumulation on device buffers (``include/crt_temporal.h``): HIP for gfx950.
 * ``libcrt_vfilter.so`` -- the stateless variance-guided a-trous filter on device buffers (``include/crt_vfilter.h``): HIP for gfx950.
 * ``libcrt_motion.so`` -- stateless temporal accumulation that follows moving instances (``include/crt_motion.h``): HIP for gfx950.
+* ``libcrt_upsample.so`` -- stateless guided upsampling of a low-resolution pass on device buffers (``include/crt_upsample.h``): HIP for gfx950.
 
 Loading fails loudly (``ImportError``) when a library has not been built: there is no Python or
 CPU fallback for the ray-trace path. Build with ``make`` at the repo root or
@@ -30,6 +31,7 @@ DENOISE_SO = os.path.join(_HERE, "denoise", "libcrt_denoise.so")
 TEMPORAL_SO = os.path.join(_HERE, "temporal", "libcrt_temporal.so")
 VFILTER_SO = os.path.join(_HERE, "vfilter", "libcrt_vfilter.so")
 MOTION_SO = os.path.join(_HERE, "motion", "libcrt_motion.so")
+UPSAMPLE_SO = os.path.join(_HERE, "upsample", "libcrt_upsample.so")
 
 
 class CrtTraceArgs(C.Structure):
@@ -198,6 +200,32 @@ MOTION_DTYPE = np.dtype([("kind", "<u4"), ("point", "<f4", 12), ("normal", "<f4"
 assert C.sizeof(CrtmMotion) == 88 and C.alignment(CrtmMotion) == 4 and C.sizeof(CrtmMotionArgs) == 24 and MOTION_DTYPE.itemsize == 88
 CRTM_STATIC, CRTM_MOVING, CRTM_NEW = 0, 1, 2                         # CrtmMotion.kind
 CRTM_MAX_COUNT = 65536
+
+
+class CrtuFrame(C.Structure):
+    """The FULL-resolution frame of one crtu_upsample call (include/crt_upsample.h): its size and guides; pointers as integers; `guides` says how
+    geometry / ids / albedo lie (as CrtdFrame)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("guides", C.c_int32), ("geometry", C.c_void_p), ("ids", C.c_void_p),
+                ("albedo", C.c_void_p)]
+
+
+class CrtuLow(C.Structure):
+    """The low-resolution image of crtu_upsample: float[LW*LH] (channels 1) or float4[LW*LH] (channels 4), factor 2 or 4; low sample (X, Y) sits on
+    full pixel (factor*X + offsetX, factor*Y + offsetY), the offsets in 0 .. factor-1."""
+    _fields_ = [("low", C.c_void_p), ("channels", C.c_int32), ("factor", C.c_int32), ("offsetX", C.c_int32), ("offsetY", C.c_int32)]
+
+
+class CrtuParams(C.Structure):
+    """Parameters of crtu_upsample: CRTU_* flags, depthTol >= 0 (relative; +inf allowed), a normalCos that is no NaN (-inf allowed)."""
+    _fields_ = [("flags", C.c_uint32), ("depthTol", C.c_float), ("normalCos", C.c_float)]
+
+
+# static_asserts of the same figures: upsample/crt_upsample.hip
+assert C.sizeof(CrtuFrame) == 40 and C.sizeof(CrtuLow) == 24 and C.sizeof(CrtuParams) == 12
+CRTU_OK, CRTU_E_BAD_ARGUMENT, CRTU_E_OUT_OF_RANGE = 0, -2, -3
+CRTU_GUIDES_PLANES, CRTU_GUIDES_SURFACE = 0, 1
+CRTU_MATCH_INSTANCE, CRTU_MODULATE = 1, 2                            # CrtuParams.flags
+CRTU_STATE_INTERPOLATED, CRTU_STATE_NEAREST, CRTU_STATE_EMPTY = 0, 1, 2     # the words of outState
 
 _f = C.c_float
 _fp = C.POINTER(C.c_float)
@@ -381,6 +409,13 @@ MOTION_API = {
     "crtm_error_string": (C.c_char_p, [C.c_int]),
 }
 
+# name -> (restype, argtypes); kept in sync with include/crt_upsample.h (tests/test_upsample_cpu.py checks it)
+UPSAMPLE_API = {
+    "crtu_low_size": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "crtu_upsample": (C.c_int, [C.POINTER(CrtuFrame), C.POINTER(CrtuLow), C.POINTER(CrtuParams), _vp, _vp, _vp]),
+    "crtu_error_string": (C.c_char_p, [C.c_int]),
+}
+
 
 def _bind(path, table):
     if not os.path.exists(path):
@@ -400,6 +435,7 @@ _denoise = None
 _temporal = None
 _vfilter = None
 _motion = None
+_upsample = None
 
 
 def hip():
@@ -449,6 +485,14 @@ def motion():
     if _motion is None:
         _motion = _bind(MOTION_SO, MOTION_API)
     return _motion
+
+
+def upsample():
+    """libcrt_upsample.so (include/crt_upsample.h). Stateless and independent of the other six; loading does not touch the GPU."""
+    global _upsample
+    if _upsample is None:
+        _upsample = _bind(UPSAMPLE_SO, UPSAMPLE_API)
+    return _upsample
 
 
 def instance_records(instances, name="instances"):

@@ -141,7 +141,7 @@ class Session:
             raise CrtError(f"{what}: error {rc}: {self.hip.crt_error_string(rc).decode()}")
 
     # ---- the frame's own buffers against the filters that read them ----
-    # denoise(), accumulate() and filter_variance() hand crt_output_device_ptr() / crt_gbuffer_device_ptr() to a stateless library that
+    # denoise(), accumulate(), filter_variance() and upsample() hand crt_output_device_ptr() / crt_gbuffer_device_ptr() to a stateless library that
     # enqueues on torch's stream and returns. The session's streams know nothing of that stream, and a synchronous frame always reuses
     # slot 0: the next frame would overwrite, and a resize or close free, what the filter has yet to read. So each such call leaves an
     # event behind it, and whatever writes or frees those buffers waits for the events on the host first, as crt_sync() does for a ray
@@ -504,17 +504,18 @@ class Session:
             raise ValueError(f"{name}: the tensor is on {x.device}, the session on cuda:{self.device}")
         return x
 
-    def _guided_frame(self, what, color, surface):
+    def _guided_frame(self, what, color, surface, guides_only=False):
         """(color, guide layout, geometry, ids, albedo) as device addresses for `what` = "denoise" / "accumulate": color=None is the float
         frame of the last render(gbuffer=True) (waits for the frames in flight first); the guides are that frame's planes, or surface=, a
         SurfaceHits of height * width records. ValueError: see Session.denoise. A caller that was handed a buffer of the frame's own (color is
-        None or surface is None) calls _frame_read_queued() behind the launch that reads it."""
+        None or surface is None) calls _frame_read_queued() behind the launch that reads it. guides_only=True (Session.upsample, whose image
+        has another size): `color` is not looked at and the address returned for it is None."""
         H, W = self.height, self.width
         if self.host_only or self.multi_device:
             raise ValueError(f"{what}: the buffers belong to one GPU; not available in a host-only session or one of several devices")
         guides, geometry, ids, albedo = _lib.CRTD_GUIDES_PLANES, None, None, None
         if surface is not None:
-            if color is None:
+            if color is None and not guides_only:
                 raise ValueError("surface=: guides for a colour tensor; the frame form (color=None) is guided by the frame's own planes")
             rec = surface.records if isinstance(surface, SurfaceHits) else None
             if rec is None or tuple(rec.shape) != (H * W, 12) or not rec.is_contiguous():
@@ -533,6 +534,8 @@ class Session:
             geometry, ids, albedo = [self.hip.crt_gbuffer_device_ptr(p) for p in (_lib.CRT_GBUFFER_GEOMETRY, _lib.CRT_GBUFFER_IDS, _lib.CRT_GBUFFER_ALBEDO)]
             if not (geometry and ids and albedo):
                 raise CrtError("crt_gbuffer_device_ptr returned null")
+        if guides_only:
+            return None, guides, geometry, ids, albedo
         if color is None:
             ptr = self.hip.crt_output_device_ptr()
             if not ptr:
@@ -680,6 +683,56 @@ class Session:
         if surface is None:
             self._frame_read_queued()
         return (result, variance) if return_variance else result      # (scratch goes back to torch's allocator, in the order of its stream)
+
+    # ---- guided upsampling on device buffers (libcrt_upsample.so: crtu_upsample; stateless, so there is no Renderer method to mirror) ----
+    def upsample(self, low, *, factor=2, offset=(0, 0), surface=None, depth_tol=0.05, normal_cos=0.9, match_instance=False, modulate=False,
+                 return_state=False, stream=None):
+        """The guided upsample of include/crt_upsample.h: `low`, a pass computed at every `factor`-th pixel (2 or 4) of the frame -- low sample
+        (X, Y) sits on pixel (factor * X + offset[0], factor * Y + offset[1]), offset in 0 .. factor-1 -- brought to the frame's resolution by a
+        bilinear blend of the up to four samples around each pixel, a sample counting when the pixel it sits on passes the geometry stops of
+        Session.denoise against the pixel (depth_tol, relative; normal_cos; match_instance), sky blending among sky; where none counts, the
+        sample nearest in depth. `low`: a float32 tensor on the session's device or a numpy array (uploaded on the stream), contiguous, of shape
+        (LH, LW) or (LH, LW, 4) with LW = ceil((width - offset[0]) / factor), LH likewise. modulate (four channels): a hit pixel's rgb is
+        multiplied by its albedo, for a pass that was traced demodulated. Guided as Session.denoise's tensor form is: by the planes of the last
+        render(gbuffer=True) (waits for the frames in flight first), or by surface=, a SurfaceHits of height * width records in pixel order;
+        the same ValueErrors. Returns an (height, width) or (height, width, 4) float32 tensor, or (that, the (height, width) int32 state plane:
+        0 interpolated, 1 nearest, 2 nothing finite around) with return_state=True; enqueued on `stream`, a torch.cuda.Stream (None:
+        torch.cuda.current_stream()), without synchronising."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        H, W = self.height, self.width
+        if stream is not None and not isinstance(stream, torch.cuda.Stream):
+            raise ValueError(f"stream: a torch.cuda.Stream or None is required, not {type(stream)}")
+        factor, (ox, oy) = int(factor), (int(o) for o in offset)
+        lib = _lib.upsample()
+        lw, lh = C.c_int32(), C.c_int32()
+        rc = lib.crtu_low_size(W, H, factor, ox, oy, C.byref(lw), C.byref(lh))
+        if rc != 0:
+            raise CrtError(f"crtu_low_size failed with {rc}: {lib.crtu_error_string(rc).decode()}")
+        frame = _lib.CrtuFrame(W, H, _lib.CRTU_GUIDES_PLANES, None, None, None)
+        _, frame.guides, frame.geometry, frame.ids, frame.albedo = self._guided_frame("upsample", None, surface, guides_only=True)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+            if isinstance(low, np.ndarray):
+                low = torch.from_numpy(np.ascontiguousarray(low)).to(dev)
+            shapes = ((lh.value, lw.value), (lh.value, lw.value, 4))
+            if not isinstance(low, torch.Tensor) or low.dtype != torch.float32 or tuple(low.shape) not in shapes or not low.is_contiguous():
+                raise ValueError(f"low: a contiguous float32 tensor or array of shape {shapes[0]} or {shapes[1]} is required for factor {factor}, "
+                                 f"offset {(ox, oy)}, not {getattr(low, 'dtype', type(low))}, shape {tuple(getattr(low, 'shape', ()))}")
+            if low.device.type != "cuda" or low.device.index != self.device:
+                raise ValueError(f"low: the tensor is on {low.device}, the session on cuda:{self.device}")
+            channels = 4 if low.dim() == 3 else 1
+            image = _lib.CrtuLow(low.data_ptr(), channels, factor, ox, oy)
+            params = _lib.CrtuParams((_lib.CRTU_MATCH_INSTANCE if match_instance else 0) | (_lib.CRTU_MODULATE if modulate else 0), float(depth_tol),
+                                     float(normal_cos))
+            result = torch.empty((H, W, 4) if channels == 4 else (H, W), dtype=torch.float32, device=dev)
+            state = torch.empty((H, W), dtype=torch.int32, device=dev) if return_state else None
+            rc = lib.crtu_upsample(C.byref(frame), C.byref(image), C.byref(params), result.data_ptr(), state.data_ptr() if return_state else None,
+                                   torch.cuda.current_stream(dev).cuda_stream)
+            if rc != 0:
+                raise CrtError(f"crtu_upsample failed with {rc}: {lib.crtu_error_string(rc).decode()}")
+            if surface is None:
+                self._frame_read_queued()
+        return (result, state) if return_state else result
 
     def set_row_bands(self, band_rows, rank, n_ranks):
         self._wait_frame_readers()

@@ -5,9 +5,10 @@
 #   clraytracer_amd/vfilter/libcrt_vfilter.so   the variance-guided a-trous filter on device buffers (include/crt_vfilter.h), gfx950 only, stateless
 #   clraytracer_amd/motion/libcrt_motion.so   temporal accumulation that follows moving instances (include/crt_motion.h), gfx950 only, stateless
 #   clraytracer_amd/upsample/libcrt_upsample.so   guided upsampling of a low-resolution pass on device buffers (include/crt_upsample.h), gfx950 only, stateless
+#   clraytracer_amd/select/libcrt_select.so   selective re-tracing on device buffers: compact, gather, scatter (include/crt_select.h), gfx950 only, stateless
 #   clraytracer_amd/host/libcrt_host.so  C++ host mirror of Renderer/ResourceManager/AssetManager (+ include/crt_host.h)
 #   oracle/libcrt_oracle.so              CPU oracle (test infrastructure only)
-# The five stateless libraries are one .hip unit each over the headers of clraytracer_amd/image/ (the steps they share; no library of its own).
+# The six stateless libraries are one .hip unit each over the headers of clraytracer_amd/image/ (the steps they share; no library of its own).
 HIPCC ?= /opt/rocm/bin/hipcc
 CXX ?= g++
 ARCH ?= gfx950
@@ -37,8 +38,10 @@ VFILTER_SO = clraytracer_amd/vfilter/libcrt_vfilter.so
 MOTION_SO = clraytracer_amd/motion/libcrt_motion.so
 # likewise: a low-resolution pass brought to the frame's resolution, guided by the frame's planes
 UPSAMPLE_SO = clraytracer_amd/upsample/libcrt_upsample.so
+# likewise: what lies between the image libraries and the point queries -- an ordered index list of selected pixels, their points, the way back
+SELECT_SO = clraytracer_amd/select/libcrt_select.so
 
-# the headers the five share, compiled into each: device and host steps; the environment switches (not motion's); the accumulate kernel of
+# the headers the six share, compiled into each: device and host steps; the environment switches (not motion's); the accumulate kernel of
 # temporal and motion
 IMAGE_HDR = clraytracer_amd/image/crt_image_device.h clraytracer_amd/image/crt_image_host.h
 IMAGE_ENV_HDR = clraytracer_amd/image/crt_image_env.h
@@ -48,7 +51,7 @@ EXAMPLE = examples/crt_headless
 
 UBENCH = tools/ubench/gather tools/ubench/chain tools/ubench/cumask tools/ubench/sky_index
 
-all: $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(TEMPORAL_SO) $(VFILTER_SO) $(MOTION_SO) $(UPSAMPLE_SO) $(EXAMPLE) $(UBENCH) oracle
+all: $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(TEMPORAL_SO) $(VFILTER_SO) $(MOTION_SO) $(UPSAMPLE_SO) $(SELECT_SO) $(EXAMPLE) $(UBENCH) oracle
 
 # vector-L1 gather microbenchmark (profiles/r01_ubench_gather.txt)
 tools/ubench/gather: tools/ubench/gather.hip
@@ -89,6 +92,9 @@ $(MOTION_SO): clraytracer_amd/motion/crt_motion.hip $(ACCUMULATE_HDR) $(IMAGE_HD
 $(UPSAMPLE_SO): clraytracer_amd/upsample/crt_upsample.hip include/crt_upsample.h $(IMAGE_HDR) $(IMAGE_ENV_HDR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $<
 
+$(SELECT_SO): clraytracer_amd/select/crt_select.hip include/crt_select.h include/crt_temporal.h $(IMAGE_HDR)
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $<
+
 $(HOST_SO): $(HOST_SRC) $(HOST_HDR) $(HIP_SO)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRC) -Lclraytracer_amd/csrc -lcrt_hip -lrt -Wl,-rpath,'$$ORIGIN/../csrc'
 
@@ -96,7 +102,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(TEMPORAL_SO) $(VFILTER_SO) $(MOTION_SO) $(UPSAMPLE_SO) $(EXAMPLE) $(UBENCH)
+	rm -f $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(TEMPORAL_SO) $(VFILTER_SO) $(MOTION_SO) $(UPSAMPLE_SO) $(SELECT_SO) $(EXAMPLE) $(UBENCH)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -8,6 +8,7 @@
 * ``libcrt_vfilter.so`` -- the stateless variance-guided a-trous filter on device buffers (``include/crt_vfilter.h``): HIP for gfx950.
 * ``libcrt_motion.so`` -- stateless temporal accumulation that follows moving instances (``include/crt_motion.h``): HIP for gfx950.
 * ``libcrt_upsample.so`` -- stateless guided upsampling of a low-resolution pass on device buffers (``include/crt_upsample.h``): HIP for gfx950.
+* ``libcrt_select.so`` -- stateless selective re-tracing on device buffers: compact, gather, scatter (``include/crt_select.h``): HIP for gfx950.
 
 Loading fails loudly (``ImportError``) when a library has not been built: there is no Python or
 CPU fallback for the ray-trace path. Build with ``make`` at the repo root or
@@ -32,6 +33,7 @@ TEMPORAL_SO = os.path.join(_HERE, "temporal", "libcrt_temporal.so")
 VFILTER_SO = os.path.join(_HERE, "vfilter", "libcrt_vfilter.so")
 MOTION_SO = os.path.join(_HERE, "motion", "libcrt_motion.so")
 UPSAMPLE_SO = os.path.join(_HERE, "upsample", "libcrt_upsample.so")
+SELECT_SO = os.path.join(_HERE, "select", "libcrt_select.so")
 
 
 class CrtTraceArgs(C.Structure):
@@ -227,6 +229,38 @@ CRTU_GUIDES_PLANES, CRTU_GUIDES_SURFACE = 0, 1
 CRTU_MATCH_INSTANCE, CRTU_MODULATE = 1, 2                            # CrtuParams.flags
 CRTU_STATE_INTERPOLATED, CRTU_STATE_NEAREST, CRTU_STATE_EMPTY = 0, 1, 2     # the words of outState
 
+
+class CrtsCompact(C.Structure):
+    """The input of one crts_compact call (include/crt_select.h): `n` words of 1 or 4 bytes, pointers as integers; item k is selected iff
+    words[k] < 32 and bit words[k] of `values` is set; `capacity` entries of the list."""
+    _fields_ = [("words", C.c_void_p), ("wordBytes", C.c_int32), ("values", C.c_uint32), ("n", C.c_int32), ("capacity", C.c_int32)]
+
+
+class CrtsFrame(C.Structure):
+    """The frame of one crts_points call: its size, the guide layout of `geometry` (as CrtdFrame) and the camera it was shot with."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("guides", C.c_int32), ("geometry", C.c_void_p), ("camera", CrttCamera)]
+
+
+class CrtsItems(C.Structure):
+    """The items of crts_points: `count` uint32 pixel indices at `list`, or list None and the grid of a low-resolution pass (factor 1, 2 or 4,
+    offsets in 0 .. factor-1, count = LW*LH)."""
+    _fields_ = [("list", C.c_void_p), ("count", C.c_int32), ("factor", C.c_int32), ("offsetX", C.c_int32), ("offsetY", C.c_int32)]
+
+
+class CrtsScatter(C.Structure):
+    """One crts_scatter call: out[list[j]] = values[j] for the `count` entries below `n`, 1 or 4 channels; outState (or None) receives stateWord."""
+    _fields_ = [("list", C.c_void_p), ("values", C.c_void_p), ("out", C.c_void_p), ("outState", C.c_void_p), ("count", C.c_int32),
+                ("channels", C.c_int32), ("n", C.c_int32), ("stateWord", C.c_uint32)]
+
+
+# static_asserts of the same figures: select/crt_select.hip
+assert C.sizeof(CrtsCompact) == 24 and C.sizeof(CrtsFrame) == 112 and C.sizeof(CrtsItems) == 24 and C.sizeof(CrtsScatter) == 48
+CRTS_OK, CRTS_E_BAD_ARGUMENT, CRTS_E_OUT_OF_RANGE = 0, -2, -3
+CRTS_GUIDES_PLANES, CRTS_GUIDES_SURFACE = 0, 1
+CRTS_STATE_RETRACED = 3                                              # behind the three CRTU_STATE_* words
+CRTS_CHUNK, CRTS_SCAN, CRTS_MAX_ITEMS = 2048, 256, 1 << 28           # crts_compact: items per workgroup, chunk sums per scan round
+CRTS_NONE = 0xFFFFFFFF                                               # a list entry that names no item; -1 as int32
+
 _f = C.c_float
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
@@ -416,6 +450,15 @@ UPSAMPLE_API = {
     "crtu_error_string": (C.c_char_p, [C.c_int]),
 }
 
+# name -> (restype, argtypes); kept in sync with include/crt_select.h (tests/test_select_cpu.py checks it)
+SELECT_API = {
+    "crts_scratch_bytes": (C.c_size_t, [C.c_int32]),
+    "crts_compact": (C.c_int, [C.POINTER(CrtsCompact), _vp, _vp, _vp, _vp]),
+    "crts_points": (C.c_int, [C.POINTER(CrtsFrame), C.POINTER(CrtsItems), _vp, _vp, _vp, _vp]),
+    "crts_scatter": (C.c_int, [C.POINTER(CrtsScatter), _vp]),
+    "crts_error_string": (C.c_char_p, [C.c_int]),
+}
+
 
 def _bind(path, table):
     if not os.path.exists(path):
@@ -436,6 +479,7 @@ _temporal = None
 _vfilter = None
 _motion = None
 _upsample = None
+_select = None
 
 
 def hip():
@@ -493,6 +537,14 @@ def upsample():
     if _upsample is None:
         _upsample = _bind(UPSAMPLE_SO, UPSAMPLE_API)
     return _upsample
+
+
+def select():
+    """libcrt_select.so (include/crt_select.h). Stateless and independent of the other seven; loading does not touch the GPU."""
+    global _select
+    if _select is None:
+        _select = _bind(SELECT_SO, SELECT_API)
+    return _select
 
 
 def instance_records(instances, name="instances"):

@@ -141,7 +141,7 @@ class Session:
             raise CrtError(f"{what}: error {rc}: {self.hip.crt_error_string(rc).decode()}")
 
     # ---- the frame's own buffers against the filters that read them ----
-    # denoise(), accumulate(), filter_variance() and upsample() hand crt_output_device_ptr() / crt_gbuffer_device_ptr() to a stateless library that
+    # denoise(), accumulate(), filter_variance(), upsample() and frame_points() hand crt_output_device_ptr() / crt_gbuffer_device_ptr() to a stateless library that
     # enqueues on torch's stream and returns. The session's streams know nothing of that stream, and a synchronous frame always reuses
     # slot 0: the next frame would overwrite, and a resize or close free, what the filter has yet to read. So each such call leaves an
     # event behind it, and whatever writes or frees those buffers waits for the events on the host first, as crt_sync() does for a ray
@@ -509,7 +509,7 @@ class Session:
         frame of the last render(gbuffer=True) (waits for the frames in flight first); the guides are that frame's planes, or surface=, a
         SurfaceHits of height * width records. ValueError: see Session.denoise. A caller that was handed a buffer of the frame's own (color is
         None or surface is None) calls _frame_read_queued() behind the launch that reads it. guides_only=True (Session.upsample, whose image
-        has another size): `color` is not looked at and the address returned for it is None."""
+        has another size, and Session.frame_points, which takes no image): `color` is not looked at and the address returned for it is None."""
         H, W = self.height, self.width
         if self.host_only or self.multi_device:
             raise ValueError(f"{what}: the buffers belong to one GPU; not available in a host-only session or one of several devices")
@@ -733,6 +733,141 @@ class Session:
             if surface is None:
                 self._frame_read_queued()
         return (result, state) if return_state else result
+
+    # ---- selective re-tracing on device buffers (libcrt_select.so: crts_compact, crts_points, crts_scatter; stateless like the filters) ----
+    def _select_tensor(self, name, x, dtypes, shape=None):
+        """`x` checked as an argument of select / frame_points / scatter: a contiguous torch tensor of one of `dtypes` (and of `shape`, where
+        given) on the session's device."""
+        import torch
+        if not isinstance(x, torch.Tensor) or x.dtype not in dtypes:
+            raise ValueError(f"{name}: a torch tensor of dtype {' or '.join(str(d) for d in dtypes)} is required, not {getattr(x, 'dtype', type(x))}")
+        if not x.is_contiguous() or x.numel() < 1 or (shape is not None and tuple(x.shape) not in shape):
+            wanted = "" if shape is None else " of shape " + " or ".join(str(s) for s in shape)
+            raise ValueError(f"{name}: a contiguous, non-empty tensor{wanted} is required, not shape {tuple(x.shape)}, strides {x.stride()}")
+        if x.device.type != "cuda" or x.device.index != self.device:
+            raise ValueError(f"{name}: the tensor is on {x.device}, the session on cuda:{self.device}")
+        return x
+
+    def _select_device(self, what):
+        import torch
+        if self.host_only or self.multi_device:
+            raise ValueError(f"{what}: the buffers belong to one GPU; not available in a host-only session or one of several devices")
+        return torch.device("cuda", self.device)
+
+    def select(self, words, values=(1, 2), capacity=None):
+        """crts_compact (include/crt_select.h): the items of `words` whose value is one of `values` (each 0 .. 31), as an ordered, padded index
+        list. `words`: a bool, uint8 or int32 tensor of any shape on the session's device, taken flat -- a mask (True is 1), or the state
+        plane of Session.upsample(return_state=True), for which the default `values` name NEAREST and EMPTY. Returns (list, counts), int32
+        tensors: list of `capacity` entries (default ceil(n / 8)), the selected flat indices in ascending order and -1 behind them; counts =
+        [total, min(total, capacity)]. total > capacity is no error: the first `capacity` are listed. Enqueued on
+        torch.cuda.current_stream() without synchronising; nothing here reads counts."""
+        import torch
+        dev = self._select_device("select")
+        words = self._select_tensor("words", words, (torch.bool, torch.uint8, torch.int32))
+        mask = 0
+        for v in values:
+            if not 0 <= int(v) < 32:
+                raise ValueError(f"values: each must lie in 0 .. 31, not {v!r}")
+            mask |= 1 << int(v)
+        n = words.numel()
+        capacity = (n + 7) // 8 if capacity is None else int(capacity)
+        lib = _lib.select()
+        if capacity < 1 or capacity > _lib.CRTS_MAX_ITEMS or n > _lib.CRTS_MAX_ITEMS:
+            raise ValueError(f"select: n and capacity must lie in 1 .. 2^28, not n {n}, capacity {capacity}")
+        c = _lib.CrtsCompact(words.data_ptr(), words.element_size(), mask, n, capacity)
+        lst = torch.empty(capacity, dtype=torch.int32, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        scratch = torch.empty(lib.crts_scratch_bytes(n) // 4, dtype=torch.int32, device=dev)
+        rc = lib.crts_compact(C.byref(c), lst.data_ptr(), counts.data_ptr(), scratch.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise CrtError(f"crts_compact failed with {rc}: {lib.crts_error_string(rc).decode()}")
+        return lst, counts      # (scratch goes back to torch's allocator, which hands a block out again in the order of the stream it was made on)
+
+    def frame_points(self, list=None, *, factor=1, offset=(0, 0), surface=None, dirs=False):
+        """crts_points: what Session.trace_ao and the ray queries take, made on the device from the frame's guides. list=None: the pixels a
+        low-resolution pass sits on -- item j is low sample (j % LW, j / LW) of Session.upsample's grid for `factor` (1, 2 or 4; 1: every
+        pixel) and `offset`. list given, an int32 tensor as Session.select returns it: the listed pixels; an entry that is -1 or names no
+        pixel gives all-zero rows, which trace nothing. Returns (positions, normals), or (positions, normals, dirs) with dirs=True: (m, 4)
+        float32 tensors -- positions = the hit point and the pixel's distance, normals = the stored normal turned towards the viewer and 0,
+        dirs = the pixel's unit ray direction and 0; a pixel that is no hit has a zero point and normal. positions[:, :3] and normals[:, :3]
+        are arguments of trace_ao as they are. Guided as Session.upsample is (the last render(gbuffer=True), or surface=), with the same
+        ValueErrors; the camera is self.camera(). Enqueued on torch.cuda.current_stream() without synchronising."""
+        import torch
+        dev = self._select_device("frame_points")
+        H, W = self.height, self.width
+        lib = _lib.select()
+        factor, (ox, oy) = int(factor), (int(o) for o in offset)
+        if list is None:
+            if factor not in (1, 2, 4) or not (0 <= ox < min(factor, W) and 0 <= oy < min(factor, H)):
+                raise ValueError(f"frame_points: factor must be 1, 2 or 4 and offset lie in 0 .. factor-1 inside the frame, not {factor}, {(ox, oy)}")
+            count = ((W - ox + factor - 1) // factor) * ((H - oy + factor - 1) // factor)
+        else:
+            count = self._select_tensor("list", list, (torch.int32,)).numel()
+            if list.dim() != 1:
+                raise ValueError(f"list: shape (m,) is required, not {tuple(list.shape)}")
+        frame = _lib.CrtsFrame(W, H, _lib.CRTS_GUIDES_PLANES, None, _lib.CrttCamera())
+        _, frame.guides, frame.geometry, _, _ = self._guided_frame("frame_points", None, surface, guides_only=True)
+        iv, ip, pos = self.camera()
+        frame.camera = _lib.crtt_camera(iv, ip, pos, W, H)
+        items = _lib.CrtsItems(None if list is None else list.data_ptr(), count, factor, ox, oy)
+        out = [torch.empty((count, 4), dtype=torch.float32, device=dev) for _ in range(3 if dirs else 2)]
+        rc = lib.crts_points(C.byref(frame), C.byref(items), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr() if dirs else None,
+                             torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise CrtError(f"crts_points failed with {rc}: {lib.crts_error_string(rc).decode()}")
+        if surface is None:
+            self._frame_read_queued()
+        return tuple(out)
+
+    def scatter(self, list, values, out, state=None):
+        """crts_scatter, in place: out.flat[list[j]] = values[j] for every entry of `list` (int32, (m,)) that names an item of `out`; -1 and
+        the like are skipped and nothing else is touched. values: float32 (m,) or (m, 4); out: a contiguous float32 tensor of n or n x 4
+        elements accordingly, such as an (H, W) or (H, W, 4) image. state: an int32 tensor of n elements whose listed items become 3
+        (CRTS_STATE_RETRACED), or None. A list that names an item twice is legal; which value stays is unspecified. Enqueued on
+        torch.cuda.current_stream() without synchronising."""
+        import torch
+        dev = self._select_device("scatter")
+        lst = self._select_tensor("list", list, (torch.int32,))
+        m = lst.numel()
+        if lst.dim() != 1:
+            raise ValueError(f"list: shape (m,) is required, not {tuple(lst.shape)}")
+        values = self._select_tensor("values", values, (torch.float32,), ((m,), (m, 4)))
+        channels = 4 if values.dim() == 2 else 1
+        out = self._select_tensor("out", out, (torch.float32,))
+        if channels == 4 and (out.dim() < 2 or out.shape[-1] != 4):
+            raise ValueError(f"out: four-channel values need a last dimension of 4, not shape {tuple(out.shape)}")
+        n = out.numel() // channels
+        if state is not None:
+            state = self._select_tensor("state", state, (torch.int32,))
+            if state.numel() != n:
+                raise ValueError(f"state: {n} elements are required, one per item of out, not {state.numel()}")
+        if m > _lib.CRTS_MAX_ITEMS or n > _lib.CRTS_MAX_ITEMS:
+            raise ValueError(f"scatter: at most 2^28 entries and items, not {m} and {n}")
+        lib = _lib.select()
+        s = _lib.CrtsScatter(lst.data_ptr(), values.data_ptr(), out.data_ptr(), state.data_ptr() if state is not None else None, m, channels, n,
+                             _lib.CRTS_STATE_RETRACED)
+        rc = lib.crts_scatter(C.byref(s), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise CrtError(f"crts_scatter failed with {rc}: {lib.crts_error_string(rc).decode()}")
+
+    def retrace_ao(self, ao, state, *, capacity=None, samples=8, radius, bias, seed=0, inclusive=False, surface=None):
+        """The consumer of Session.upsample's state plane: the pixels of `ao` (an (height, width) float32 tensor, an upsampled ambient-occlusion
+        pass) whose `state` (its (height, width) int32 state plane) is NEAREST or EMPTY are traced at full resolution and patched in place,
+        and their state becomes 3. select(state, capacity=) -> frame_points(list) -> trace_ao on all `capacity` items, of which the padding
+        traces nothing -> scatter: four calls enqueued on torch.cuda.current_stream() with sizes known on the host, none of which waits.
+        capacity: default ceil(height * width / 8). samples, radius, bias, seed, inclusive: as trace_ao takes them (item j of the list is
+        point j of that call). surface: as frame_points takes it. Returns counts, the int32 device tensor [total, patched]: the caller reads
+        it when it pleases, and total > capacity means that the pixels behind the first `capacity` kept what the upsample gave them."""
+        import torch
+        self._select_device("retrace_ao")
+        H, W = self.height, self.width
+        ao = self._select_tensor("ao", ao, (torch.float32,), ((H, W),))
+        state = self._select_tensor("state", state, (torch.int32,), ((H, W),))
+        lst, counts = self.select(state, (_lib.CRTU_STATE_NEAREST, _lib.CRTU_STATE_EMPTY), capacity)
+        positions, normals = self.frame_points(lst, surface=surface)
+        values = self.trace_ao(positions[:, :3], normals[:, :3], samples, radius=radius, bias=bias, seed=seed, inclusive=inclusive)
+        self.scatter(lst, values, ao, state)
+        return counts
 
     def set_row_bands(self, band_rows, rank, n_ranks):
         self._wait_frame_readers()

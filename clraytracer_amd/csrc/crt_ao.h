@@ -142,7 +142,8 @@ __device__ __forceinline__ void crt_ao_body(CrtDevScene S0, CrtAoArgs A, CrtFram
                     const float w = dot3(d, n2);
                     const CrtStackT<TLAS ? CRT_TLAS_PARK : 0> stack = { s_stack + lane2, S0.stackOverflow };
                     constexpr unsigned kOcclusion = TR_ANYHIT | opt_if(TLAS, TR_TLAS) | opt_if(INCLUSIVE, TR_INCLUSIVE)
-                                                  | opt_if(policy::ao_divides(SOURCE == CRT_AO_FRAME, TLAS), TR_DIVIDE);
+                                                  | opt_if(policy::ao_divides(SOURCE == CRT_AO_FRAME, TLAS), TR_DIVIDE)
+                                                  | opt_if(policy::kDeviceQueryOffset32, TR_OFFSET32);
                     const Closest c = closest_hit<kOcclusion>(S, o, d, stack, lc, best0, noCull);
                     const float occ = c.anyHit ? 1.0f : 0.0f;
                     num += w * occ; den += w;

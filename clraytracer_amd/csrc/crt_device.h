@@ -386,12 +386,80 @@ __device__ __forceinline__ v3 mat3mul(const CrtDevInstance& m, v3 v)
     return r;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Record addresses of the per-lane fetches (TR_OFFSET32, policy's "who takes 32-bit record offsets"). A lane's record address is
+// base + index * size with a wave-uniform base. Written with a 64-bit index it is built in a VGPR pair -- two moves from a VGPR that holds 0,
+// a 64-bit shift, a 64-bit add -- and the loads go through that pair; written as base plus a 32-bit BYTE offset the base stays in its SGPR pair
+// and one VGPR of offset is all the vector unit computes (global_load ... v, s[n:n+1]). Same loads, same bytes; fewer VALU instructions.
+// Why 32 bits hold it: a reference that reaches a kernel is inside its pool. The pools have the fixed capacities below, whatever the scene
+// (crt_upload.h: alloc_pools allocates with these constants); crt_relayout.h's make_ref admits a leaf only with firstTri + count <= the
+// triangle pool's slots and an inner node only with both children below the node count, which an upload keeps below the node pool's slots
+// (SPANCHK), and anything else sets the error word: the scene is invalid and no frame or query is launched on it (g.sceneValid). The empty
+// reference names slot CRT_TRI_POOL_SLOTS itself with a count of zero: bigLeaf has that one entry more, and the triangle address is formed
+// and never loaded from. An instance index is below numInstances <= CRT_MAX_INSTANCES. Each static_assert says that the largest offset its
+// helper can form is below 2^32; tests/test_offset32_cpu.py says the same in a sentence when a capacity changes.
+// OFFSET32 false: the 64-bit expressions as they were. -DCRT_NO_OFFSET32 (A/B builds): those everywhere.
+// ------------------------------------------------------------------------------------------------
+#define CRT_TRI_POOL_SLOTS ((size_t)CRT_MAX_TRIANGLES * 2)      // ResourceManager.cpp:158
+#define CRT_NODE_POOL_SLOTS ((size_t)CRT_MAX_TRIANGLES * 2)     // ResourceManager.cpp:159 (MAX_BVHMEMORY * 2)
+#define CRT_PAIR_POOL_RECORDS (CRT_NODE_POOL_SLOTS / 2 + 1)     // siblings are adjacent: pair index = leftFirst >> 1
+#define CRT_PAIR_BYTES 64u
+#define CRT_TRI_HOT_BYTES 36u
+#define CRT_TRI_COLD_BYTES 32u
+#ifdef CRT_NO_OFFSET32
+#define CRT_OFFSETS32(OFFSET32) false
+#else
+#define CRT_OFFSETS32(OFFSET32) (OFFSET32)
+#endif
+// the pair record of inner reference `ref`
+static_assert(CRT_PAIR_POOL_RECORDS * CRT_PAIR_BYTES < (1ull << 32) && CRT_PAIR_BYTES == 4 * sizeof(float4), "pair pool: 32-bit byte offsets");
+template <bool OFFSET32>
+__device__ __forceinline__ const float4* pair_record(const CrtDevScene& S, uint32_t ref)
+{
+    if constexpr (CRT_OFFSETS32(OFFSET32)) return reinterpret_cast<const float4*>(reinterpret_cast<const char*>(S.pairs) + ref * CRT_PAIR_BYTES);
+    else return S.pairs + (size_t)ref * 4;
+}
+// the hot record of triangle `i` (i <= CRT_TRI_POOL_SLOTS: the empty reference's address is formed)
+static_assert((CRT_TRI_POOL_SLOTS + 1) * CRT_TRI_HOT_BYTES < (1ull << 32) && CRT_TRI_HOT_BYTES == 9 * sizeof(float), "hot triangle pool: 32-bit byte offsets");
+template <bool OFFSET32>
+__device__ __forceinline__ const float* tri_hot_record(const CrtDevScene& S, uint32_t i)
+{
+    if constexpr (CRT_OFFSETS32(OFFSET32)) return reinterpret_cast<const float*>(reinterpret_cast<const char*>(S.triHot) + i * CRT_TRI_HOT_BYTES);
+    else return S.triHot + (size_t)i * 9;
+}
+// the cold record of triangle `i` (a hit's triangle: i < CRT_TRI_POOL_SLOTS)
+static_assert(CRT_TRI_POOL_SLOTS * CRT_TRI_COLD_BYTES < (1ull << 32) && CRT_TRI_COLD_BYTES == 2 * sizeof(uint4), "cold triangle pool: 32-bit byte offsets");
+template <bool OFFSET32>
+__device__ __forceinline__ const uint4* tri_cold_record(const CrtDevScene& S, uint32_t i)
+{
+    if constexpr (CRT_OFFSETS32(OFFSET32)) return reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(S.triCold) + i * CRT_TRI_COLD_BYTES);
+    else return S.triCold + (size_t)i * 2;
+}
+// the triangle count of a leaf of 128 or more triangles (first <= CRT_TRI_POOL_SLOTS)
+static_assert((CRT_TRI_POOL_SLOTS + 1) * sizeof(uint32_t) < (1ull << 32), "bigLeaf: 32-bit byte offsets");
+template <bool OFFSET32>
+__device__ __forceinline__ uint32_t big_leaf_count(const CrtDevScene& S, uint32_t first)
+{
+    if constexpr (CRT_OFFSETS32(OFFSET32)) return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(S.bigLeaf) + first * (uint32_t)sizeof(uint32_t));
+    else return S.bigLeaf[first];
+}
+// the device record of instance `inst`
+static_assert((size_t)CRT_MAX_INSTANCES * sizeof(CrtDevInstance) < (1ull << 32) && sizeof(CrtDevInstance) == 64, "instance table: 32-bit byte offsets");
+template <bool OFFSET32>
+__device__ __forceinline__ const CrtDevInstance* instance_record(const CrtDevInstance* __restrict__ table, uint32_t inst)
+{
+    if constexpr (CRT_OFFSETS32(OFFSET32)) return reinterpret_cast<const CrtDevInstance*>(reinterpret_cast<const char*>(table) + inst * (uint32_t)sizeof(CrtDevInstance));
+    else return table + inst;
+}
+
 // The device record of instance `inst` (per lane). It comes through a SCALAR load (one s_load_dwordx16 through the scalar
 // cache) when every lane that asks in this step asks for the same instance -- the common case for a coherent packet, whose
 // lanes share their first candidates and mostly hit the same instance -- and through four per-lane vector loads otherwise:
 // vector-memory instructions are what bounds the kernel, and unlike the node fetches (where the same test
 // cost more than it saved, round 2) instance records are fetched rarely enough for one readfirstlane + compare + ballot
 // per step to pay. (The table is written by crt_refresh_instances_kernel in an earlier launch, never by the reading kernel.)
+// OFFSET32: the divergent path's record address (instance_record above); the uniform path addresses through SGPRs already.
+template <bool OFFSET32 = false>
 __device__ __forceinline__ CrtDevInstance load_instance(const CrtDevInstance* __restrict__ table, uint32_t inst)
 {
     CrtDevInstance I;
@@ -402,7 +470,7 @@ __device__ __forceinline__ CrtDevInstance load_instance(const CrtDevInstance* __
         I.r0 = make_float4(a.x, a.y, a.z, a.w); I.r1 = make_float4(b.x, b.y, b.z, b.w);
         I.r2 = make_float4(c.x, c.y, c.z, c.w); I.r3 = make_float4(e.x, e.y, e.z, e.w);
     } else {
-        const CrtDevInstance* ip = table + inst;
+        const CrtDevInstance* ip = instance_record<OFFSET32>(table, inst);
         I.r0 = ip->r0; I.r1 = ip->r1; I.r2 = ip->r2; I.r3 = ip->r3;
     }
     return I;
@@ -424,10 +492,11 @@ enum : unsigned {               // closest_hit, trip_steps, Traversal
     TR_ROOT_PRETEST = 1u << 8,  // ... and the exact root step per surviving instance and wave behind it (root_pretest_misses)
     TR_BOUNCE_PRETEST = 1u << 9,    // ... and the same step per instance and wave for the reflection bounce's candidates (bounce_pretest_mask)
     TR_PRETEST_ENTRY = 1u << 10,    // ... and the camera bounce's pre-test leaves a lane inside its first surviving instance (root_pretest_enters)
-    TR_ALL = (1u << 11) - 1u
+    TR_OFFSET32 = 1u << 11,         // the per-lane record fetches address as a scalar base plus a 32-bit byte offset (pair_record ... instance_record)
+    TR_ALL = (1u << 12) - 1u
 };
 enum : unsigned { CM_COUNT = 1u << 0, CM_DEFER_COUNT = 1u << 1, CM_ALL = (1u << 2) - 1u };                        // candidate_mask
-enum : unsigned { SB_DEFER_ENERGY = 1u << 0, SB_REFRACT = 1u << 1, SB_SKY_DOUBLE = 1u << 2, SB_ALL = (1u << 3) - 1u };   // shade_bounce
+enum : unsigned { SB_DEFER_ENERGY = 1u << 0, SB_REFRACT = 1u << 1, SB_SKY_DOUBLE = 1u << 2, SB_OFFSET32 = 1u << 3, SB_ALL = (1u << 4) - 1u };   // shade_bounce
 constexpr unsigned opt_if(bool on, unsigned bit) { return on ? bit : 0u; }
 constexpr bool has_opt(unsigned opts, unsigned bit) { return (opts & bit) != 0u; }
 
@@ -511,6 +580,29 @@ constexpr bool trace_bounce_pretests(bool ROOT_PRETESTS) { return ROOT_PRETESTS;
 // (SGPR spills 52 -> 48) and the G-buffer kernel (59 -> 57). The four without shadow rays -- plain and supersampled, with and without refraction --
 // hold every row. Every other kernel keeps root_pretest_misses and compiles to what it compiled to before.
 constexpr bool trace_pretest_enters(bool ROOT_PRETESTS, bool SHADOW) { return ROOT_PRETESTS && !SHADOW; }
+
+// ---- who takes 32-bit record offsets (TR_OFFSET32 in the traversal: pair_record, tri_hot_record, big_leaf_count, instance_record;
+//      SB_OFFSET32 in the shading: tri_cold_record, instance_record) ----
+// A counted or stamped launch keeps the 64-bit form in every family (the independent path, above). Of the others, a kernel takes the option
+// unless a row of the ledger would move with it; five would, each downwards, and keep the 64-bit form:
+//   crt_trace_gbuffer_kernel<true, true, true>   VGPRs 68 -> 67
+//   crt_trace_ldstop_kernel<false>               VGPRs 65 -> 64 (its vector path selects between two bases per lane: little to gain)
+//   crt_primary_kernel<false>                    VGPRs 59 -> 58
+//   crt_bounce_kernel<false>                     VGPRs 64 -> 63
+//   crt_trace_block_kernel<false, false>         ScratchSize 32 -> 16, VGPRs Spill 6 -> 2
+// trace_body: the plain, supersampled and G-buffer kernels, the benchmark's among them -- all but the one G-buffer kernel above and the ldstop form (TOP)
+constexpr bool trace_offset32(bool COUNT, bool STAMP, bool TOP, bool GBUFFER, bool SHADOW, bool TLAS, bool REFRACT)
+{
+    return !COUNT && !STAMP && !TOP && !(GBUFFER && SHADOW && TLAS && REFRACT);
+}
+// the wavefront form (crt_primary_kernel, crt_bounce_kernel) and crt_trace_block_kernel: never; crt_trace_refill_kernel: uncounted and unstamped
+constexpr bool kWavefrontOffset32 = false;
+constexpr bool kBlockOffset32 = false;
+constexpr bool refill_offset32(bool COUNT, bool STAMP) { return !COUNT && !STAMP; }
+// crt_query_kernel: a counted kernel
+constexpr bool kQueryOffset32 = false;
+// the queries on device buffers (crt_rays_kernel, crt_ao_kernel, their inclusive twins, crt_shade_kernel): all of them, no row moves
+constexpr bool kDeviceQueryOffset32 = true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -525,11 +617,11 @@ constexpr bool trace_pretest_enters(bool ROOT_PRETESTS, bool SHADOW) { return RO
 // The stack lives in LDS/scratch (CRT_STACK_*); slot indices wrap modulo 32 where upstream's array would overflow.
 // ------------------------------------------------------------------------------------------------
 // OPTS: the TR_* options of the closest_hit (or the kernel's own loop, crt_refill.h) that owns it, carried in the type: trip_steps reads them
-// back from it. The members read TR_COUNT and TR_DIVIDE; inner and leaf take the box rule and any-hit from the options of the trip that calls them.
+// back from it. The members read TR_COUNT, TR_DIVIDE and TR_OFFSET32; inner and leaf take the box rule and any-hit from the options of the trip that calls them.
 template <unsigned OPTS>
 struct Traversal {
     static_assert((OPTS & ~TR_ALL) == 0u, "unknown traversal option");
-    static constexpr bool COUNT = has_opt(OPTS, TR_COUNT), DIVIDE = has_opt(OPTS, TR_DIVIDE);
+    static constexpr bool COUNT = has_opt(OPTS, TR_COUNT), DIVIDE = has_opt(OPTS, TR_DIVIDE), OFFSET32 = has_opt(OPTS, TR_OFFSET32);
     v3 mo, md, inv;               // ray in the current instance's object space (direction not renormalised, hazard H6)
     Triout tr;                    // running best of the current instance (kernel_main.cl:200-202)
     int sp, prot, inters;         // stack pointer, pop counter (kernel_main.cl:131), OR of the `passed` flags
@@ -573,7 +665,7 @@ struct Traversal {
     __device__ __forceinline__ void enter(const CrtDevScene& S, uint32_t inst, v3 o, v3 d, float bestSoFar, LaneCounters& lc)
     {
         curInst = inst;
-        const CrtDevInstance I = load_instance(S.devInstances, inst);
+        const CrtDevInstance I = load_instance<OFFSET32>(S.devInstances, inst);
         mo = xform_xyz(I, o.x, o.y, o.z, 1.0f);
         md = xform_xyz(I, d.x, d.y, d.z, 0.0f);
         inv = recip3<DIVIDE>(md);                                   // native_recip pinned to IEEE: the bits of 1.0f / x
@@ -621,7 +713,7 @@ struct Traversal {
         } else {
             // one aligned 64-byte record (a step that mixes tree-top and other records takes the top ones from the table's global copy:
             // the four vector loads are issued for the wave either way)
-            const float4* p = (STK::kTop && (ref & CRT_TOP_BIT)) ? S.topPairs + (size_t)(ref & 0xFFFFu) * 4 : S.pairs + (size_t)ref * 4;
+            const float4* p = (STK::kTop && (ref & CRT_TOP_BIT)) ? S.topPairs + (size_t)(ref & 0xFFFFu) * 4 : pair_record<OFFSET32>(S, ref);
             const float4 lmin = p[0], lmax = p[1], rmin = p[2], rmax = p[3];
             dist1 = intersect_aabb<INCLUSIVE>(mo, inv, lmin, lmax, tr.t);
             dist2 = intersect_aabb<INCLUSIVE>(mo, inv, rmin, rmax, tr.t);
@@ -651,10 +743,10 @@ struct Traversal {
         constexpr bool ANYHIT = has_opt(TRIP, TR_ANYHIT);
         const uint32_t first = ref & 0x00FFFFFFu;
         uint32_t n = (ref >> 24) & 0x7Fu;
-        if (n == 0) n = S.bigLeaf[first];
+        if (n == 0) n = big_leaf_count<OFFSET32>(S, first);
         for (uint32_t i = first, end = first + n; i < end; ++i) {
             if (COUNT) lc.triTests++;
-            const float* __restrict__ hot = S.triHot + (size_t)i * 9;
+            const float* __restrict__ hot = tri_hot_record<OFFSET32>(S, i);
             inters |= intersect_triangle<DIVIDE>(mo, md, mk3(hot[0], hot[1], hot[2]), mk3(hot[3], hot[4], hot[5]), mk3(hot[6], hot[7], hot[8]), tr, i);
             if (ANYHIT) { if (inters) break; }
         }
@@ -1595,7 +1687,8 @@ __device__ __forceinline__ int shade_bounce(const CrtDevScene& S, const Closest&
                                             float* ndlOut = nullptr, const SINK* sink = nullptr)
 {
     static_assert((OPTS & ~SB_ALL) == 0u, "unknown shading option");
-    constexpr bool DEFER_ENERGY = has_opt(OPTS, SB_DEFER_ENERGY), REFRACT = has_opt(OPTS, SB_REFRACT), SKY_DOUBLE = has_opt(OPTS, SB_SKY_DOUBLE);
+    constexpr bool DEFER_ENERGY = has_opt(OPTS, SB_DEFER_ENERGY), REFRACT = has_opt(OPTS, SB_REFRACT), SKY_DOUBLE = has_opt(OPTS, SB_SKY_DOUBLE),
+                   OFFSET32 = has_opt(OPTS, SB_OFFSET32);
     constexpr bool kSink = !std::is_same<SINK, NoSink>::value;
     const float UcharToFloat01 = 1.0f / 255.0f;
     if (c.distance > 99998.0f) {
@@ -1611,12 +1704,13 @@ __device__ __forceinline__ int shade_bounce(const CrtDevScene& S, const Closest&
     const v3 light = bounce == 0 ? mk3(0.0f, lightY, lightZ) : ps.d;     // lightDir = ray.direction after the first bounce
     const v3 atm0 = scale3(mk3(0.255f, 0.25f, 0.27f), 1.0f);
     const v3 atm = bounce == 0 ? atm0 : scale3(atm0, 0.4f);
-    const CrtDevInstance I = load_instance(S.devInstances, (uint32_t)c.hitInstance);
+    const CrtDevInstance I = load_instance<OFFSET32>(S.devInstances, (uint32_t)c.hitInstance);
     // meshRay of the winning instance, recomputed with the same arithmetic as in the loop
     const v3 mo = xform_xyz(I, ps.o.x, ps.o.y, ps.o.z, 1.0f);
     const v3 md = xform_xyz(I, ps.d.x, ps.d.y, ps.d.z, 0.0f);
 
-    const uint4 c0 = S.triCold[(size_t)c.hit.tri * 2], c1 = S.triCold[(size_t)c.hit.tri * 2 + 1];
+    const uint4* cold = tri_cold_record<OFFSET32>(S, c.hit.tri);
+    const uint4 c0 = cold[0], c1 = cold[1];
     // c0 = {uv0x|uv0y, uv1x|uv1y, uv2x|uv2y, mat|n0x}; c1 = {n0y|n0z, n1x|n1y, n1z|n2x, n2y|n2z}
     const uint32_t matIndex = c0.w & 0xffffu;
     uint32_t mi = __float_as_uint(I.r1.w) + matIndex;

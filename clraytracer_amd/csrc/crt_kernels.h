@@ -382,7 +382,8 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
     constexpr bool SSAA = CASE == CRT_TRACE_SSAA, GBUFFER = CASE == CRT_TRACE_GBUFFER;
     constexpr int kParkNdl = TLAS ? CRT_TLAS_PARK : 0;
     // what both traversals share, the primary one's own options, and the shading's (division, double-only sky index, staged cull: crt_device.h, policy)
-    constexpr unsigned kRay = opt_if(COUNT, TR_COUNT) | opt_if(TLAS, TR_TLAS) | opt_if(policy::trace_divides(COUNT, GBUFFER, SHADOW, TLAS, REFRACT), TR_DIVIDE);
+    constexpr unsigned kRay = opt_if(COUNT, TR_COUNT) | opt_if(TLAS, TR_TLAS) | opt_if(policy::trace_divides(COUNT, GBUFFER, SHADOW, TLAS, REFRACT), TR_DIVIDE)
+                            | opt_if(policy::trace_offset32(COUNT, STAMP, STK::kTop, GBUFFER, SHADOW, TLAS, REFRACT), TR_OFFSET32);
     constexpr bool kStages = policy::trace_stages_cull(COUNT, STAMP, TLAS, STK::kTop);
     constexpr bool kWaveCulls = policy::trace_wave_culls(kStages, CASE == CRT_TRACE_PLAIN, GBUFFER, SHADOW, REFRACT);
     constexpr bool kRootPretests = policy::trace_root_pretests(kWaveCulls, GBUFFER, SHADOW, REFRACT);
@@ -390,7 +391,8 @@ __device__ __forceinline__ void trace_body(const CrtDevScene& S, const CrtFrame&
                                 | opt_if(policy::trace_bounce_pretests(kRootPretests), TR_BOUNCE_PRETEST)
                                 | opt_if(policy::trace_pretest_enters(kRootPretests, SHADOW), TR_PRETEST_ENTRY);
     constexpr unsigned kShade = opt_if(SHADOW, SB_DEFER_ENERGY) | opt_if(REFRACT, SB_REFRACT)
-                              | opt_if(policy::trace_sky_double(COUNT, GBUFFER, SHADOW, TLAS, REFRACT), SB_SKY_DOUBLE);
+                              | opt_if(policy::trace_sky_double(COUNT, GBUFFER, SHADOW, TLAS, REFRACT), SB_SKY_DOUBLE)
+                              | opt_if(has_opt(kRay, TR_OFFSET32), SB_OFFSET32);
     LaneCounters lc; zero_counters(lc);
     WaveStampStart t0 = { 0, 0 };
     if (STAMP) t0 = wave_stamp_start();
@@ -542,7 +544,7 @@ __global__ __launch_bounds__(CRT_BLOCK, COUNT ? CRT_WAVES_PER_SIMD_COUNT : CRT_W
     if (active) {
         ps.d = raygen_dir(F, px, py);
         if (COUNT) { lc.rays++; lc.primary++; }
-        Closest c = closest_hit<opt_if(COUNT, TR_COUNT) | opt_if(policy::primary_divides(COUNT), TR_DIVIDE)>(S, ps.o, ps.d, stack, lc);
+        Closest c = closest_hit<opt_if(COUNT, TR_COUNT) | opt_if(policy::primary_divides(COUNT), TR_DIVIDE) | opt_if(policy::kWavefrontOffset32, TR_OFFSET32)>(S, ps.o, ps.d, stack, lc);
         cont = shade_bounce<opt_if(policy::wavefront_sky_double(COUNT), SB_SKY_DOUBLE)>(S, c, ps, 0, F.lightY, F.lightZ) != 0;
         if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
         out[(size_t)py * (size_t)F.width + (size_t)px] = make_float4(ps.result.x, ps.result.y, ps.result.z, 1.0f);
@@ -600,7 +602,7 @@ __global__ __launch_bounds__(CRT_BLOCK, COUNT ? CRT_WAVES_PER_SIMD_COUNT : CRT_W
         const float4 partial = out[r.pixel];
         PathState ps = unpack_bounce(r, mk3(partial.x, partial.y, partial.z));
         if (COUNT) { lc.rays++; lc.secondary++; }
-        Closest c = closest_hit<opt_if(COUNT, TR_COUNT) | opt_if(policy::kBounceDivides, TR_DIVIDE)>(S, ps.o, ps.d, stack, lc);
+        Closest c = closest_hit<opt_if(COUNT, TR_COUNT) | opt_if(policy::kBounceDivides, TR_DIVIDE) | opt_if(policy::kWavefrontOffset32, TR_OFFSET32)>(S, ps.o, ps.d, stack, lc);
         const bool cont = shade_bounce<opt_if(policy::wavefront_sky_double(COUNT), SB_SKY_DOUBLE)>(S, c, ps, 1, F.lightY, F.lightZ) != 0;
         if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
         out[r.pixel] = make_float4(ps.result.x, ps.result.y, ps.result.z, 1.0f);
@@ -738,7 +740,7 @@ __global__ __launch_bounds__(CRT_BLOCK, CRT_WAVES_PER_SIMD_COUNT) void crt_query
         v3 o = mk3(origins[3 * k], origins[3 * k + 1], origins[3 * k + 2]);
         v3 d = mk3(dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]);
         lc.rays++;
-        Closest c = closest_hit<TR_COUNT | opt_if(TLAS, TR_TLAS) | opt_if(policy::kQueryDivides, TR_DIVIDE)>(S, o, d, stack, lc);
+        Closest c = closest_hit<TR_COUNT | opt_if(TLAS, TR_TLAS) | opt_if(policy::kQueryDivides, TR_DIVIDE) | opt_if(policy::kQueryOffset32, TR_OFFSET32)>(S, o, d, stack, lc);
         CrtRayHit h;
         if (c.anyHit) { h.t = c.hit.t; h.u = c.hit.u; h.v = c.hit.v; h.triIndex = c.hit.tri; h.instance = c.hitInstance; lc.hits++; }
         else { h.t = c.distance; h.u = 0.0f; h.v = 0.0f; h.triIndex = 0; h.instance = -1; lc.misses++; }

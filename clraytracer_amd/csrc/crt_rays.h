@@ -27,7 +27,8 @@ template <bool ANYHIT, bool TLAS> __global__ void crt_rays_kernel(CrtDevScene S0
 template <bool ANYHIT, bool TLAS, bool INCLUSIVE>
 __device__ __forceinline__ void crt_rays_body(CrtDevScene S0, CrtRaysArgs A, crt_lds_u32_ptr s_stack)
 {
-    constexpr unsigned kRay = opt_if(ANYHIT, TR_ANYHIT) | opt_if(TLAS, TR_TLAS) | opt_if(INCLUSIVE, TR_INCLUSIVE) | opt_if(policy::kDeviceQueryDivides, TR_DIVIDE);
+    constexpr unsigned kRay = opt_if(ANYHIT, TR_ANYHIT) | opt_if(TLAS, TR_TLAS) | opt_if(INCLUSIVE, TR_INCLUSIVE) | opt_if(policy::kDeviceQueryDivides, TR_DIVIDE)
+                            | opt_if(policy::kDeviceQueryOffset32, TR_OFFSET32);
     LaneCounters lc = {};                        // no TR_COUNT: never read
     for (;;) {
         uint32_t chunk;

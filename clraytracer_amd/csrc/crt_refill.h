@@ -65,7 +65,8 @@ void crt_trace_refill_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out
         uint32_t cursor = 0;                                 // next pixel of the block nobody has taken yet (wave-uniform)
         PathState ps = camera_path(F, mk3(0.f, 0.f, 0.f));
         Closest c = no_hit();
-        constexpr unsigned kTrip = opt_if(COUNT, TR_COUNT) | opt_if(STAMP, TR_ITERS) | opt_if(policy::refill_block_divides(COUNT), TR_DIVIDE);
+        constexpr unsigned kTrip = opt_if(COUNT, TR_COUNT) | opt_if(STAMP, TR_ITERS) | opt_if(policy::refill_block_divides(COUNT), TR_DIVIDE)
+                                 | opt_if(policy::refill_offset32(COUNT, STAMP), TR_OFFSET32);
         Traversal<kTrip> T; T.reset();
         unsigned long long cand = 0;
         bool havePath = false;
@@ -89,7 +90,7 @@ void crt_trace_refill_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out
                     const uint32_t st = stack.parked(0);
                     const int bounce = (int)(st >> 31);
                     ps.energy = __uint_as_float(stack.parked(1));      // (waits in LDS through the traversals, as in the megakernel's SHADOW instantiations)
-                    const int cont = shade_bounce<opt_if(policy::refill_sky_double(COUNT), SB_SKY_DOUBLE)>(S, c, ps, bounce, F.lightY, F.lightZ);
+                    const int cont = shade_bounce<opt_if(policy::refill_sky_double(COUNT), SB_SKY_DOUBLE) | opt_if(policy::refill_offset32(COUNT, STAMP), SB_OFFSET32)>(S, c, ps, bounce, F.lightY, F.lightZ);
                     c = no_hit();
                     if (COUNT) { if (cont) lc.hits++; else lc.misses++; }
                     if (cont != 0 && bounce == 0) {           // kernel_main.cl:187: the second iteration of the bounce loop
@@ -183,7 +184,8 @@ void crt_trace_block_kernel(CrtDevScene S, CrtFrame F, float4* __restrict__ out,
     const unsigned long long tc0 = tile_cost_start(F);
     int tx0 = 0, tileRow = 0, costSlot = -1;
     const bool valid = refill_block(F, blockIdx.x, tx0, tileRow, costSlot, CRT_BLOCK_TILES);
-    constexpr unsigned kRay = opt_if(COUNT, TR_COUNT) | opt_if(STAMP, TR_ITERS) | opt_if(policy::refill_block_divides(COUNT), TR_DIVIDE);
+    constexpr unsigned kRay = opt_if(COUNT, TR_COUNT) | opt_if(STAMP, TR_ITERS) | opt_if(policy::refill_block_divides(COUNT), TR_DIVIDE)
+                                 | opt_if(policy::kBlockOffset32, TR_OFFSET32);
     constexpr unsigned kShade = opt_if(policy::kBlockSkyDouble, SB_SKY_DOUBLE);
     if (valid) {
         const uint32_t cnt = S.numInstances < 64u ? S.numInstances : 64u;

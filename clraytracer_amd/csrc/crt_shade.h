@@ -74,8 +74,9 @@ template <int WHAT, bool TLAS>
 __device__ __forceinline__ void crt_shade_body(CrtDevScene S0, CrtShadeArgs A, crt_lds_u32_ptr s_stack)
 {
     constexpr bool kRadiance = (WHAT & CRT_SHADE_RADIANCE) != 0, kSurface = (WHAT & CRT_SHADE_SURFACE) != 0;
-    constexpr unsigned kRay = opt_if(TLAS, TR_TLAS) | opt_if(policy::kDeviceQueryDivides, TR_DIVIDE) | opt_if(policy::kShadeStagesCull, TR_STAGE);
-    constexpr unsigned kShade = opt_if(policy::kShadeSkyDouble, SB_SKY_DOUBLE);
+    constexpr unsigned kRay = opt_if(TLAS, TR_TLAS) | opt_if(policy::kDeviceQueryDivides, TR_DIVIDE) | opt_if(policy::kShadeStagesCull, TR_STAGE)
+                            | opt_if(policy::kDeviceQueryOffset32, TR_OFFSET32);
+    constexpr unsigned kShade = opt_if(policy::kShadeSkyDouble, SB_SKY_DOUBLE) | opt_if(policy::kDeviceQueryOffset32, SB_OFFSET32);
     LaneCounters lc = {};                        // no TR_COUNT: never read
     for (;;) {
         uint32_t chunk;

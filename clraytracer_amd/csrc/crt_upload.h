@@ -71,8 +71,10 @@ int create_frame_slots()
 
 int alloc_pools()
 {
-    g.triCap = (size_t)CRT_MAX_TRIANGLES * 2;           // ResourceManager.cpp:158
-    g.nodeCap = (size_t)CRT_MAX_TRIANGLES * 2;          // ResourceManager.cpp:159 (MAX_BVHMEMORY * 2)
+    // (the constants crt_device.h's record-address helpers prove their 32-bit offsets with)
+    g.triCap = CRT_TRI_POOL_SLOTS;                      // ResourceManager.cpp:158
+    g.nodeCap = CRT_NODE_POOL_SLOTS;                    // ResourceManager.cpp:159 (MAX_BVHMEMORY * 2)
+    static_assert(CRT_PAIR_POOL_RECORDS == CRT_NODE_POOL_SLOTS / 2 + 1, "the pair pool below");
     g.texelByteCap = CRT_MAX_TEXTURE_BYTES * 2;         // ResourceManager.cpp:163
     RCCHK(g.rawTris.alloc(g.triCap));
     HIPCHK(hipMemsetAsync(g.rawTris, 0, g.triCap * sizeof(CrtTri), g.stream));   // crt_tri_reach_kernel may scan slots nobody has uploaded yet (an upload that leaves a gap)

@@ -9,6 +9,7 @@
 * ``libcrt_motion.so`` -- stateless temporal accumulation that follows moving instances (``include/crt_motion.h``): HIP for gfx950.
 * ``libcrt_upsample.so`` -- stateless guided upsampling of a low-resolution pass on device buffers (``include/crt_upsample.h``): HIP for gfx950.
 * ``libcrt_select.so`` -- stateless selective re-tracing on device buffers: compact, gather, scatter (``include/crt_select.h``): HIP for gfx950.
+* ``libcrt_present.so`` -- the stateless last step on device buffers: compose, tone-map, FXAA, RGBA8, and the G-buffer's views (``include/crt_present.h``): HIP for gfx950.
 
 Loading fails loudly (``ImportError``) when a library has not been built: there is no Python or
 CPU fallback for the ray-trace path. Build with ``make`` at the repo root or
@@ -34,6 +35,7 @@ VFILTER_SO = os.path.join(_HERE, "vfilter", "libcrt_vfilter.so")
 MOTION_SO = os.path.join(_HERE, "motion", "libcrt_motion.so")
 UPSAMPLE_SO = os.path.join(_HERE, "upsample", "libcrt_upsample.so")
 SELECT_SO = os.path.join(_HERE, "select", "libcrt_select.so")
+PRESENT_SO = os.path.join(_HERE, "present", "libcrt_present.so")
 
 
 class CrtTraceArgs(C.Structure):
@@ -261,6 +263,31 @@ CRTS_STATE_RETRACED = 3                                              # behind th
 CRTS_CHUNK, CRTS_SCAN, CRTS_MAX_ITEMS = 2048, 256, 1 << 28           # crts_compact: items per workgroup, chunk sums per scan round
 CRTS_NONE = 0xFFFFFFFF                                               # a list entry that names no item; -1 as int32
 
+
+class CrtpPresent(C.Structure):
+    """One crtp_present call (include/crt_present.h): the frame's size, `color` float4[W*H] and `ao` float[W*H] or None as integers, aoStrength
+    in 0 .. 1, a finite exposure > 0 (1: no such step), CRTP_* flags."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("color", C.c_void_p), ("ao", C.c_void_p), ("aoStrength", C.c_float),
+                ("exposure", C.c_float), ("flags", C.c_uint32)]
+
+
+class CrtpView(C.Structure):
+    """One crtp_view call: the frame's size, the guide layout (as CrtdFrame) and a CRTP_VIEW_* mode; geometry / ids / albedo as CrtdFrame has them,
+    `plane` float[W*H] (SCALAR) or uint32[W*H] (STATE); scale (DEPTH), lo < hi (SCALAR)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("guides", C.c_int32), ("mode", C.c_int32), ("geometry", C.c_void_p),
+                ("ids", C.c_void_p), ("albedo", C.c_void_p), ("plane", C.c_void_p), ("scale", C.c_float), ("lo", C.c_float), ("hi", C.c_float)]
+
+
+# static_asserts of the same figures: present/crt_present.hip
+assert C.sizeof(CrtpPresent) == 40 and C.sizeof(CrtpView) == 64
+CRTP_OK, CRTP_E_BAD_ARGUMENT, CRTP_E_OUT_OF_RANGE = 0, -2, -3
+CRTP_GUIDES_PLANES, CRTP_GUIDES_SURFACE = 0, 1
+CRTP_UNORM8, CRTP_POST, CRTP_FXAA, CRTP_HEAL = 1, 2, 4, 8             # CrtpPresent.flags
+CRTP_VIEW_NORMAL, CRTP_VIEW_DEPTH, CRTP_VIEW_INSTANCE, CRTP_VIEW_TRIANGLE, CRTP_VIEW_ALBEDO, CRTP_VIEW_SCALAR, CRTP_VIEW_STATE = range(7)
+CRTP_VIEW_MODES = {"normal": CRTP_VIEW_NORMAL, "depth": CRTP_VIEW_DEPTH, "instance": CRTP_VIEW_INSTANCE, "triangle": CRTP_VIEW_TRIANGLE,
+                   "albedo": CRTP_VIEW_ALBEDO, "scalar": CRTP_VIEW_SCALAR, "state": CRTP_VIEW_STATE}
+CRTP_FXAA_HALO = 5                                                   # the pixels around a tile the FXAA form stages
+
 _f = C.c_float
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
@@ -460,6 +487,15 @@ SELECT_API = {
 }
 
 
+# name -> (restype, argtypes); kept in sync with include/crt_present.h (tests/test_present_cpu.py checks it)
+PRESENT_API = {
+    "crtp_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_uint32]),
+    "crtp_present": (C.c_int, [C.POINTER(CrtpPresent), _vp, _vp, _vp, _vp]),
+    "crtp_view": (C.c_int, [C.POINTER(CrtpView), _vp, _vp, _vp]),
+    "crtp_error_string": (C.c_char_p, [C.c_int]),
+}
+
+
 def _bind(path, table):
     if not os.path.exists(path):
         raise ImportError(f"{path} has not been built (run `make` at {ROOT} or __graft_entry__.build()); "
@@ -480,6 +516,7 @@ _vfilter = None
 _motion = None
 _upsample = None
 _select = None
+_present = None
 
 
 def hip():
@@ -545,6 +582,14 @@ def select():
     if _select is None:
         _select = _bind(SELECT_SO, SELECT_API)
     return _select
+
+
+def present():
+    """libcrt_present.so (include/crt_present.h). Stateless and independent of the other eight; loading does not touch the GPU."""
+    global _present
+    if _present is None:
+        _present = _bind(PRESENT_SO, PRESENT_API)
+    return _present
 
 
 def instance_records(instances, name="instances"):

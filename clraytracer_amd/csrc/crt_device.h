@@ -32,6 +32,7 @@
 #include <type_traits>
 #include <utility>
 #include "../../include/crt_types.h"
+#include "crt_vec3.h"
 
 #define CRT_LEAF_BIT 0x80000000u
 // CRT_KERNEL=ldstop only: an INNER reference with this bit names record (ref & 0xFFFF) of the tree-top table (crt_ldstop.h) instead of
@@ -188,15 +189,7 @@ struct CrtGBuffer {
     __host__ __device__ char* albedo(size_t pixels) const { return planes + 32 * pixels; }
 };
 
-struct v3 { float x, y, z; };
-
-__device__ __forceinline__ v3 mk3(float x, float y, float z) { v3 r; r.x = x; r.y = y; r.z = z; return r; }
-__device__ __forceinline__ v3 add3(v3 a, v3 b) { return mk3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ v3 sub3(v3 a, v3 b) { return mk3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ v3 mul3(v3 a, v3 b) { return mk3(a.x * b.x, a.y * b.y, a.z * b.z); }
-__device__ __forceinline__ v3 scale3(v3 a, float s) { return mk3(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ v3 neg3(v3 a) { return mk3(-a.x, -a.y, -a.z); }
-__device__ __forceinline__ float dot3(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+// v3, mk3, add3, sub3, mul3, scale3, neg3, dot3: crt_vec3.h (included above)
 __device__ __forceinline__ v3 cross3(v3 a, v3 b)
 {
     return mk3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);

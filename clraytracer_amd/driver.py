@@ -141,7 +141,7 @@ class Session:
             raise CrtError(f"{what}: error {rc}: {self.hip.crt_error_string(rc).decode()}")
 
     # ---- the frame's own buffers against the filters that read them ----
-    # denoise(), accumulate(), filter_variance(), upsample() and frame_points() hand crt_output_device_ptr() / crt_gbuffer_device_ptr() to a stateless library that
+    # denoise(), accumulate(), filter_variance(), upsample(), frame_points(), present() and view() hand crt_output_device_ptr() / crt_gbuffer_device_ptr() to a stateless library that
     # enqueues on torch's stream and returns. The session's streams know nothing of that stream, and a synchronous frame always reuses
     # slot 0: the next frame would overwrite, and a resize or close free, what the filter has yet to read. So each such call leaves an
     # event behind it, and whatever writes or frees those buffers waits for the events on the host first, as crt_sync() does for a ray
@@ -868,6 +868,94 @@ class Session:
         values = self.trace_ao(positions[:, :3], normals[:, :3], samples, radius=radius, bias=bias, seed=seed, inclusive=inclusive)
         self.scatter(lst, values, ao, state)
         return counts
+
+    # ---- the end of the chain on device buffers (libcrt_present.so: crtp_present, crtp_view; stateless like the filters) ----
+    def _present_outputs(self, dev, out, bytes):
+        """(float tensor or None, uint8 tensor or None, what the call returns) for present() and view()."""
+        import torch
+        H, W = self.height, self.width
+        if out is not None:
+            self._image("out", out)
+        elif not bytes:
+            out = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
+        packed = torch.empty((H, W, 4), dtype=torch.uint8, device=dev) if bytes else None
+        return out, packed, (out, packed) if out is not None and bytes else packed if bytes else out
+
+    def present(self, color=None, *, ao=None, ao_strength=1.0, exposure=1.0, postprocess=True, unorm8=True, fxaa=False, heal=False, out=None,
+                bytes=True):
+        """crtp_present (include/crt_present.h): the stages that follow Trace in a frame -- upstream's RGBA8 render target (unorm8), FXAA (fxaa),
+        PostProcess (postprocess), the packed bytes -- applied to `color`, a contiguous (height, width, 4) float32 tensor on the session's
+        device such as denoise(), accumulate() or upsample() return; before them rgb * ((1 - ao_strength) + ao_strength * ao) for `ao`, an
+        (height, width) float32 tensor, and rgb * exposure; heal: non-finite values become 0 (and a non-finite ao factor 1) first. On the
+        plain colour of a frame the result is, bit for bit, what render_raw with the same three flags stores.
+        color=None: the float frame of the last render / render_raw (waits for the frames in flight first); ValueError when there is none, in
+        a host-only session, one of several devices or one under row bands.
+        Returns the (height, width, 4) uint8 tensor of RGBA8 bytes (bytes=True, the default); the (height, width, 4) float32 tensor, alpha 1
+        (bytes=False; `out`, when given); or (float tensor, uint8 tensor) when both bytes=True and out= are given. Enqueued on
+        torch.cuda.current_stream() without synchronising."""
+        import torch
+        dev = self._select_device("present")
+        H, W = self.height, self.width
+        if color is None:
+            if self._row_bands:
+                raise ValueError("present: the session is under row bands; the frame holds this rank's rows only")
+            if self._last_frame is None:
+                raise ValueError("present: no frame has been rendered since the session began or was resized")
+            self.sync()
+            ptr = self.hip.crt_output_device_ptr()
+            if not ptr:
+                raise CrtError("crt_output_device_ptr returned null")
+        else:
+            ptr = self._image("color", color).data_ptr()
+        if ao is not None:
+            ao = self._select_tensor("ao", ao, (torch.float32,), ((H, W),))
+        result, packed, returned = self._present_outputs(dev, out, bytes)
+        flags = ((_lib.CRTP_UNORM8 if unorm8 else 0) | (_lib.CRTP_POST if postprocess else 0) | (_lib.CRTP_FXAA if fxaa else 0)
+                 | (_lib.CRTP_HEAL if heal else 0))
+        p = _lib.CrtpPresent(W, H, ptr, ao.data_ptr() if ao is not None else None, float(ao_strength), float(exposure), flags)
+        lib = _lib.present()
+        nbytes = lib.crtp_scratch_bytes(W, H, flags)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        rc = lib.crtp_present(C.byref(p), result.data_ptr() if result is not None else None, packed.data_ptr() if packed is not None else None,
+                              scratch.data_ptr() if scratch is not None else None, torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise CrtError(f"crtp_present failed with {rc}: {lib.crtp_error_string(rc).decode()}")
+        if color is None:
+            self._frame_read_queued()
+        return returned
+
+    def view(self, mode, *, plane=None, surface=None, scale=10.0, lo=0.0, hi=1.0, out=None, bytes=True):
+        """crtp_view: a picture of the frame's guides. mode: "normal" (n * 0.5 + 0.5), "depth" (grey scale / (t + scale)), "instance" and
+        "triangle" (a hash colour per instance id, per triangle), "albedo" -- guided as Session.upsample is, by the planes of the last
+        render(gbuffer=True) or by surface=, a SurfaceHits of height * width records, with the same ValueErrors --, "scalar" (`plane`, an
+        (height, width) float32 tensor such as an AO pass, grey from lo to hi, NaN magenta) or "state" (`plane`, the int32 state plane of
+        upsample / retrace_ao: interpolated dark grey, nearest orange, empty red, retraced green, anything else magenta). Returns as present()
+        does: the uint8 tensor, the float tensor (bytes=False), or both (out= given); both hold the same bytes. Enqueued on
+        torch.cuda.current_stream() without synchronising."""
+        import torch
+        dev = self._select_device("view")
+        H, W = self.height, self.width
+        if mode not in _lib.CRTP_VIEW_MODES:
+            raise ValueError(f"mode: one of {', '.join(_lib.CRTP_VIEW_MODES)} is required, not {mode!r}")
+        v = _lib.CrtpView(W, H, _lib.CRTP_GUIDES_PLANES, _lib.CRTP_VIEW_MODES[mode], None, None, None, None, float(scale), float(lo), float(hi))
+        planar = mode in ("scalar", "state")
+        if planar:
+            if surface is not None:
+                raise ValueError(f"surface=: the {mode} view reads plane= only")
+            v.plane = self._select_tensor("plane", plane, (torch.float32,) if mode == "scalar" else (torch.int32,), ((H, W),)).data_ptr()
+        else:
+            if plane is not None:
+                raise ValueError(f"plane=: the {mode} view reads the frame's guides")
+            _, v.guides, v.geometry, v.ids, v.albedo = self._guided_frame("view", None, surface, guides_only=True)
+        result, packed, returned = self._present_outputs(dev, out, bytes)
+        lib = _lib.present()
+        rc = lib.crtp_view(C.byref(v), result.data_ptr() if result is not None else None, packed.data_ptr() if packed is not None else None,
+                           torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise CrtError(f"crtp_view failed with {rc}: {lib.crtp_error_string(rc).decode()}")
+        if not planar and surface is None:
+            self._frame_read_queued()
+        return returned
 
     def set_row_bands(self, band_rows, rank, n_ranks):
         self._wait_frame_readers()

@@ -7,9 +7,10 @@
 #   clraytracer_amd/upsample/libcrt_upsample.so   guided upsampling of a low-resolution pass on device buffers (include/crt_upsample.h), gfx950 only, stateless
 #   clraytracer_amd/select/libcrt_select.so   selective re-tracing on device buffers: compact, gather, scatter (include/crt_select.h), gfx950 only, stateless
 #   clraytracer_amd/present/libcrt_present.so   the chain's last step on device buffers: compose, tone-map, FXAA, RGBA8, and the G-buffer's ID views (include/crt_present.h), gfx950 only, stateless
+#   clraytracer_amd/meter/libcrt_meter.so   metering and auto-exposure on device buffers: a log-luminance histogram resolved to an exposure in device memory, and the multiply by it (include/crt_meter.h), gfx950 only, stateless
 #   clraytracer_amd/host/libcrt_host.so  C++ host mirror of Renderer/ResourceManager/AssetManager (+ include/crt_host.h)
 #   oracle/libcrt_oracle.so              CPU oracle (test infrastructure only)
-# The seven stateless libraries are one .hip unit each over the headers of clraytracer_amd/image/ (the steps they share; no library of its own);
+# The eight stateless image libraries are one .hip unit each over the headers of clraytracer_amd/image/ (the steps they share; no library of its own);
 # libcrt_present.so also compiles clraytracer_amd/csrc/crt_post.h, the frame's per-pixel stages, which libcrt_hip.so compiles from the same text.
 HIPCC ?= /opt/rocm/bin/hipcc
 CXX ?= g++
@@ -44,8 +45,10 @@ UPSAMPLE_SO = clraytracer_amd/upsample/libcrt_upsample.so
 SELECT_SO = clraytracer_amd/select/libcrt_select.so
 # likewise: the end of the chain -- the stages that follow Trace in a frame, on any image of the caller's, and the views of the guides
 PRESENT_SO = clraytracer_amd/present/libcrt_present.so
+# likewise: what the end of the chain is exposed by -- an image metered on the device, the exposure left in device memory
+METER_SO = clraytracer_amd/meter/libcrt_meter.so
 
-# the headers the seven share, compiled into each: device and host steps; the environment switches (not motion's); the accumulate kernel of
+# the headers they share, compiled into each: device and host steps; the environment switches (not motion's); the accumulate kernel of
 # temporal and motion
 IMAGE_HDR = clraytracer_amd/image/crt_image_device.h clraytracer_amd/image/crt_image_host.h
 IMAGE_ENV_HDR = clraytracer_amd/image/crt_image_env.h
@@ -57,7 +60,7 @@ EXAMPLE = examples/crt_headless
 
 UBENCH = tools/ubench/gather tools/ubench/chain tools/ubench/cumask tools/ubench/sky_index
 
-all: $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(TEMPORAL_SO) $(VFILTER_SO) $(MOTION_SO) $(UPSAMPLE_SO) $(SELECT_SO) $(PRESENT_SO) $(EXAMPLE) $(UBENCH) oracle
+all: $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(TEMPORAL_SO) $(VFILTER_SO) $(MOTION_SO) $(UPSAMPLE_SO) $(SELECT_SO) $(PRESENT_SO) $(METER_SO) $(EXAMPLE) $(UBENCH) oracle
 
 # vector-L1 gather microbenchmark (profiles/r01_ubench_gather.txt)
 tools/ubench/gather: tools/ubench/gather.hip
@@ -104,6 +107,9 @@ $(SELECT_SO): clraytracer_amd/select/crt_select.hip include/crt_select.h include
 $(PRESENT_SO): clraytracer_amd/present/crt_present.hip include/crt_present.h $(POST_HDR) $(IMAGE_HDR) $(IMAGE_ENV_HDR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $<
 
+$(METER_SO): clraytracer_amd/meter/crt_meter.hip include/crt_meter.h $(IMAGE_HDR) $(IMAGE_ENV_HDR)
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -shared -o $@ $<
+
 $(HOST_SO): $(HOST_SRC) $(HOST_HDR) $(HIP_SO)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRC) -Lclraytracer_amd/csrc -lcrt_hip -lrt -Wl,-rpath,'$$ORIGIN/../csrc'
 
@@ -111,7 +117,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(TEMPORAL_SO) $(VFILTER_SO) $(MOTION_SO) $(UPSAMPLE_SO) $(SELECT_SO) $(PRESENT_SO) $(EXAMPLE) $(UBENCH)
+	rm -f $(HIP_SO) $(HOST_SO) $(DENOISE_SO) $(TEMPORAL_SO) $(VFILTER_SO) $(MOTION_SO) $(UPSAMPLE_SO) $(SELECT_SO) $(PRESENT_SO) $(METER_SO) $(EXAMPLE) $(UBENCH)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

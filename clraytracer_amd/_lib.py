@@ -10,6 +10,7 @@
 * ``libcrt_upsample.so`` -- stateless guided upsampling of a low-resolution pass on device buffers (``include/crt_upsample.h``): HIP for gfx950.
 * ``libcrt_select.so`` -- stateless selective re-tracing on device buffers: compact, gather, scatter (``include/crt_select.h``): HIP for gfx950.
 * ``libcrt_present.so`` -- the stateless last step on device buffers: compose, tone-map, FXAA, RGBA8, and the G-buffer's views (``include/crt_present.h``): HIP for gfx950.
+* ``libcrt_meter.so`` -- stateless metering and auto-exposure on device buffers: a log-luminance histogram resolved to an exposure in device memory (``include/crt_meter.h``): HIP for gfx950.
 
 Loading fails loudly (``ImportError``) when a library has not been built: there is no Python or
 CPU fallback for the ray-trace path. Build with ``make`` at the repo root or
@@ -36,6 +37,7 @@ MOTION_SO = os.path.join(_HERE, "motion", "libcrt_motion.so")
 UPSAMPLE_SO = os.path.join(_HERE, "upsample", "libcrt_upsample.so")
 SELECT_SO = os.path.join(_HERE, "select", "libcrt_select.so")
 PRESENT_SO = os.path.join(_HERE, "present", "libcrt_present.so")
+METER_SO = os.path.join(_HERE, "meter", "libcrt_meter.so")
 
 
 class CrtTraceArgs(C.Structure):
@@ -288,6 +290,39 @@ CRTP_VIEW_MODES = {"normal": CRTP_VIEW_NORMAL, "depth": CRTP_VIEW_DEPTH, "instan
                    "albedo": CRTP_VIEW_ALBEDO, "scalar": CRTP_VIEW_SCALAR, "state": CRTP_VIEW_STATE}
 CRTP_FXAA_HALO = 5                                                   # the pixels around a tile the FXAA form stages
 
+
+class CrtxResult(C.Structure):
+    """What crtx_meter leaves in device memory (include/crt_meter.h): the exposure, the target it adapts towards, the metered luminance, and the
+    integers behind them."""
+    _fields_ = [("exposure", C.c_float), ("target", C.c_float), ("average", C.c_float), ("meanQ", C.c_uint32), ("valid", C.c_uint32),
+                ("invalid", C.c_uint32), ("minQ", C.c_uint32), ("maxQ", C.c_uint32)]
+
+
+class CrtxMeter(C.Structure):
+    """One crtx_meter call: the frame's size, `color` float4[W*H] and `ao` float[W*H] or None as integers, aoStrength in 0 .. 1, CRTX_* flags, the
+    metered rectangle [x0, x1) x [y0, y1), key > 0, the ranks that count (0 <= lowFraction <= highFraction <= 1), 0 < minExposure <= maxExposure,
+    the adaptation's two rates in 0 .. 1, the workgroups of the histogram launch (0: the library's choice) and `prev`, a CrtxResult on the device
+    or None."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("color", C.c_void_p), ("ao", C.c_void_p), ("aoStrength", C.c_float),
+                ("flags", C.c_uint32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("key", C.c_float),
+                ("lowFraction", C.c_float), ("highFraction", C.c_float), ("minExposure", C.c_float), ("maxExposure", C.c_float),
+                ("rateUp", C.c_float), ("rateDown", C.c_float), ("groups", C.c_int32), ("prev", C.c_void_p)]
+
+
+class CrtxExpose(C.Structure):
+    """One crtx_expose call: the frame's size, `color`, `ao` or None and `exposure`, a CrtxResult on the device, as integers; aoStrength in
+    0 .. 1; CRTX_HEAL or 0."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("color", C.c_void_p), ("ao", C.c_void_p), ("exposure", C.c_void_p),
+                ("aoStrength", C.c_float), ("flags", C.c_uint32)]
+
+
+# static_asserts of the same figures: meter/crt_meter.hip
+assert C.sizeof(CrtxResult) == 32 and C.sizeof(CrtxMeter) == 88 and C.sizeof(CrtxExpose) == 40
+CRTX_OK, CRTX_E_BAD_ARGUMENT, CRTX_E_OUT_OF_RANGE = 0, -2, -3
+CRTX_HEAL, CRTX_ADAPT = 1, 2                                         # CrtxMeter.flags; CrtxExpose.flags takes CRTX_HEAL only
+CRTX_HIST_BINS, CRTX_QMIN, CRTX_QMAX = 256, 107 << 16, 139 << 16     # the log code and its bins
+CRTX_MAX_GROUPS, CRTX_DEFAULT_GROUPS, CRTX_RECORD_WORDS = 2048, 128, 264     # the histogram launch and its partial records
+
 _f = C.c_float
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
@@ -495,6 +530,15 @@ PRESENT_API = {
     "crtp_error_string": (C.c_char_p, [C.c_int]),
 }
 
+# name -> (restype, argtypes); kept in sync with include/crt_meter.h (tests/test_meter_cpu.py checks it)
+METER_API = {
+    "crtx_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "crtx_meter": (C.c_int, [C.POINTER(CrtxMeter), _vp, _vp, _vp, _vp]),
+    "crtx_expose": (C.c_int, [C.POINTER(CrtxExpose), _vp, _vp]),
+    "crtx_rate": (C.c_float, [C.c_double, C.c_double]),
+    "crtx_error_string": (C.c_char_p, [C.c_int]),
+}
+
 
 def _bind(path, table):
     if not os.path.exists(path):
@@ -517,6 +561,7 @@ _motion = None
 _upsample = None
 _select = None
 _present = None
+_meter = None
 
 
 def hip():
@@ -590,6 +635,14 @@ def present():
     if _present is None:
         _present = _bind(PRESENT_SO, PRESENT_API)
     return _present
+
+
+def meter():
+    """libcrt_meter.so (include/crt_meter.h). Stateless and independent of the other nine; loading does not touch the GPU."""
+    global _meter
+    if _meter is None:
+        _meter = _bind(METER_SO, METER_API)
+    return _meter
 
 
 def instance_records(instances, name="instances"):

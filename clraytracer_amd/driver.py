@@ -957,6 +957,86 @@ class Session:
             self._frame_read_queued()
         return returned
 
+    # ---- metering and auto-exposure on device buffers (libcrt_meter.so: crtx_meter, crtx_expose; stateless like the filters) ----
+    def meter(self, color=None, *, ao=None, ao_strength=1.0, key=0.18, low=0.0, high=1.0, min_exposure=2 ** -8, max_exposure=2 ** 8, prev=None,
+              rate_up=1.0, rate_down=1.0, region=None, heal=False, histogram=False, groups=0):
+        """crtx_meter (include/crt_meter.h): the exposure that brings the average luminance of `color` -- a contiguous (height, width, 4) float32
+        tensor on the session's device, composed with `ao` and ao_strength (and healed) as present() composes it -- to `key`, left in device
+        memory. The average is the geometric mean (formed in a piecewise-linear log2: up to 6.1 % below it) of the pixels whose luminance is
+        finite and not negative, over region=(x0, y0, x1, y1), a half-open rectangle inside the frame (None: all of it); low and high, fractions
+        in 0 .. 1, keep only the pixels ranked between them by luminance (by 256 bins, 8 per octave; 0 and 1: every pixel, exactly). The
+        exposure is key / average clamped to min_exposure .. max_exposure. prev=: the record of the frame before; the exposure then moves from
+        prev's by rate_up (towards a larger one) or rate_down of the way to that target (_lib.meter().crtx_rate(dt, tau) gives a rate from a
+        frame time and a time constant), and stays prev's where no pixel is valid. groups: the workgroups of the histogram launch (0: the
+        library's choice).
+        color=None: the float frame of the last render / render_raw, exactly as present() takes it, with the same ValueErrors.
+        Returns the record as an (8,) float32 tensor on the device: [exposure, target, average], then -- through .view(torch.int32) -- meanQ,
+        valid, invalid, minQ, maxQ; it is what expose() and prev= take. histogram=True: (record, hist), hist the (256,) int32 counts per bin.
+        Enqueued on torch.cuda.current_stream() without synchronising: the host never sees the exposure."""
+        import torch
+        dev = self._select_device("meter")
+        H, W = self.height, self.width
+        if color is None:
+            if self._row_bands:
+                raise ValueError("meter: the session is under row bands; the frame holds this rank's rows only")
+            if self._last_frame is None:
+                raise ValueError("meter: no frame has been rendered since the session began or was resized")
+            self.sync()
+            ptr = self.hip.crt_output_device_ptr()
+            if not ptr:
+                raise CrtError("crt_output_device_ptr returned null")
+        else:
+            ptr = self._image("color", color).data_ptr()
+        if ao is not None:
+            ao = self._select_tensor("ao", ao, (torch.float32,), ((H, W),))
+        if prev is not None:
+            prev = self._select_tensor("prev", prev, (torch.float32,), ((8,),))
+        try:
+            x0, y0, x1, y1 = (0, 0, W, H) if region is None else (int(v) for v in region)
+        except (TypeError, ValueError):
+            raise ValueError(f"region: (x0, y0, x1, y1) or None is required, not {region!r}") from None
+        lib = _lib.meter()
+        groups = int(groups)
+        nbytes = lib.crtx_scratch_bytes(W, H, groups)
+        if not nbytes:
+            raise ValueError(f"groups: 0 .. {_lib.CRTX_MAX_GROUPS} is required, not {groups}")
+        record = torch.empty(8, dtype=torch.float32, device=dev)
+        hist = torch.empty(_lib.CRTX_HIST_BINS, dtype=torch.int32, device=dev) if histogram else None
+        scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+        m = _lib.CrtxMeter(W, H, ptr, ao.data_ptr() if ao is not None else None, float(ao_strength),
+                           (_lib.CRTX_HEAL if heal else 0) | (_lib.CRTX_ADAPT if prev is not None else 0), x0, y0, x1, y1, float(key), float(low),
+                           float(high), float(min_exposure), float(max_exposure), float(rate_up), float(rate_down), groups,
+                           prev.data_ptr() if prev is not None else None)
+        rc = lib.crtx_meter(C.byref(m), record.data_ptr(), hist.data_ptr() if histogram else None, scratch.data_ptr(),
+                            torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise CrtError(f"crtx_meter failed with {rc}: {lib.crtx_error_string(rc).decode()}")
+        if color is None:
+            self._frame_read_queued()
+        return (record, hist) if histogram else record      # (scratch goes back to torch's allocator, in the order of its stream)
+
+    def expose(self, color, record, *, ao=None, ao_strength=1.0, heal=False, out=None):
+        """crtx_expose: `color` composed with `ao` (and healed) as present() composes it, times the exposure that `record` -- what meter()
+        returned -- holds on the device; alpha stays. present(..., exposure=1.0) of the result then gives what present(color, ao=...,
+        exposure=) would with that exposure, which the host never read. Returns the (height, width, 4) float32 tensor (`out`, when given; it
+        may be `color`). Enqueued on torch.cuda.current_stream() without synchronising."""
+        import torch
+        dev = self._select_device("expose")
+        H, W = self.height, self.width
+        if color is None:
+            raise ValueError("color: a tensor is required (meter() takes the frame itself; expose() writes an image of the caller's)")
+        ptr = self._image("color", color).data_ptr()
+        record = self._select_tensor("record", record, (torch.float32,), ((8,),))
+        if ao is not None:
+            ao = self._select_tensor("ao", ao, (torch.float32,), ((H, W),))
+        result = torch.empty((H, W, 4), dtype=torch.float32, device=dev) if out is None else self._image("out", out)
+        e = _lib.CrtxExpose(W, H, ptr, ao.data_ptr() if ao is not None else None, record.data_ptr(), float(ao_strength), _lib.CRTX_HEAL if heal else 0)
+        lib = _lib.meter()
+        rc = lib.crtx_expose(C.byref(e), result.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        if rc != 0:
+            raise CrtError(f"crtx_expose failed with {rc}: {lib.crtx_error_string(rc).decode()}")
+        return result
+
     def set_row_bands(self, band_rows, rank, n_ranks):
         self._wait_frame_readers()
         self.h.crth_set_row_bands(int(band_rows), int(rank), int(n_ranks))
